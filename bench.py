@@ -12,31 +12,39 @@
              contiguous id range, no data-path collective; the shared HRIR set + EQ table is broadcast
              once from rank 0 (RCCL over xGMI via torch.distributed "nccl").
 
-Launch:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Launch:  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+             a plain run sets up, warms up, times the K steps and prints the record of those steps; everything else
+             the benchmark measures (the fields listed below, the node-API leg, strong mode's one-GPU comparison) runs
+             only with --full.  --dump-outputs DIR writes what the last timed step returned (see dump_outputs)
              N > 1 without WORLD_SIZE in the environment: this process never touches the GPU -- it starts N child
              ranks of itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set), relays
              rank 0's line and exits with the worst child status
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                 --master-port P bench.py --gpus N --steps K --warmup W
 Rank 0 prints ONE JSON line.  At N > 1 it carries `ranks` (per rank: device index, PCI bus id / UUID, streams, ms per
-step -- gathered with all_gather_object), `rccl_world_size`, `distinct_devices`, and in strong mode
-`expected_strong_scaling`.  Beside the contract's fields it carries, at N = 1:
+step -- gathered with all_gather_object), `rccl_world_size`, `distinct_devices`, and in strong mode with --full
+`expected_strong_scaling`.  Beside the contract's fields it carries
   roofline      the dominant kernel (HIP-event time inside the timed region) against HBM and, when it is the
                 EQ's serial recurrence, against its instruction-issue floor; `conv` = the convolution kernel
-                against HBM by the bytes it really moves
+                against HBM by the bytes it really moves (with --full, `traffic` is measured live and
+                `conv_alone` times the convolution by itself)
+and with --full, at N = 1:
   saturation    the same step at 1024 and 2048 streams (where the chip, not one chain's recurrence, is the bound)
   pcie_inclusive  the headline step fed from / returned to pinned host memory (ohs_batch_process_host)
+  long_ir       BASELINE configs[3] under both blockings, and the plugin's own call on that response
   cpu_baseline  the CPU oracle on this box's host cores
 
-  node_batch    the same job through the C ABI's node API (ohs_node_batch_*: ONE process, N devices, device-resident
-                audio, the tables carried by the library's own RCCL broadcast) -- measured in a child run of
-                `bench.py --gpus N --node-batch` after the timed region (at N > 1 the other ranks wait on the CPU)
+  node_batch    (--full, any N) the same job through the C ABI's node API (ohs_node_batch_*: ONE process, N devices,
+                device-resident audio, the tables carried by the library's own RCCL broadcast) -- measured in a child
+                run of `bench.py --gpus N --node-batch --full` after the timed region (at N > 1 the other ranks wait
+                on the CPU)
 
-  python bench.py --gpus N --node-batch [--steps K --warmup W]
+  python bench.py --gpus N --node-batch [--steps K --warmup W] [--full]
          ONE process drives N devices through ohs_node_batch_create / _set_tables / _process / _sync only (no
          torch.distributed; torch owns the device buffers and generates the noise).  This is the path a Rust host binds
          (INTEGRATION.md section 7); its record carries `slots` (device, PCI bus id, first stream, streams, device ms per
-         step), `rccl_comm_size`, `value` (device-resident) and `pcie_inclusive` (ohs_node_batch_process_host).
+         step), `rccl_comm_size` and `value` (device-resident); with --full also `roofline` and `pcie_inclusive`
+         (ohs_node_batch_process_host).
 
 Rehearsal of the multi-rank plumbing on a one-GPU box: OHS_BENCH_DIST_BACKEND=gloo (CPU broadcast, every rank on
 cuda:0) -- see tests/test_gpu_bench_rehearsal.py.
@@ -276,6 +284,31 @@ def measure_traffic_live(frames: int, streams: int, timeout_s: float = 240.0):
     return {k: int(round(v)) for k, v in per.items()}, "measured in this run: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, two child runs of 2 steps"
 
 
+DUMP_BYTES = 48_000_000         # --dump-outputs: all files of all ranks / slots together (the option promises < 64 MB)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir: str, y, parts: int = 1, suffix: str = "") -> None:
+    """--dump-outputs: what the timed path returned in its last step (y = [streams, 2, frames] f32 on the device, the
+    array a caller of ohs_batch_process receives) as float32 .npy files, this rank's / slot's share of DUMP_BYTES:
+      y_head<suffix>    [streams, 2, K]  the first K frames of every stream and channel
+      y_tail<suffix>    [streams, 2, K]  the last K frames (the end of the step: state carried over the whole step)
+      y_sample<suffix>  [n]              a fixed sample of the whole array: flat indices drawn with DUMP_SEED
+    The indices depend only on the shape, so two builds run with the same arguments can be compared file for file."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    S, C, F = y.shape
+    budget = DUMP_BYTES // parts
+    k = max(1, min(F // 2, 8192, budget // 3 // (S * C * 4)))
+    np.save(os.path.join(out_dir, f"y_head{suffix}.npy"), y[:, :, :k].cpu().numpy())
+    np.save(os.path.join(out_dir, f"y_tail{suffix}.npy"), y[:, :, F - k:].cpu().numpy())
+    n = max(1, min(S * C * F, budget // 3 // 4))
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, S * C * F, n, dtype=np.int64))
+    flat = y.reshape(-1)
+    np.save(os.path.join(out_dir, f"y_sample{suffix}.npy"),
+            flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy())
+
+
 def make_processor(ohs, S, nb, irs, coeffs, enabled, device_index):
     bp = ohs.BatchProcessor(S, num_bands=nb, device=device_index)
     for p in range(4):
@@ -382,6 +415,9 @@ def node_batch_main(args) -> int:
         for i, (dev, first, cnt) in enumerate(shards):
             np.save(os.environ["OHS_BENCH_DUMP"] + f".slot{i}.npy",
                     np.concatenate([np.array([first, first + cnt], np.float32), ys[i][:, :, :4096].cpu().numpy().ravel()]))
+    if args.dump_outputs:
+        for i, y_ in enumerate(ys):
+            dump_outputs(args.dump_outputs, y_, parts=n, suffix=f"_slot{i}" if n > 1 else "")
     value = float(total_streams) * frames * args.steps / elapsed / 1e6
     handle0 = nb.device_batch(0)
     whole_model = sum(nb.device_batch(i).algorithmic_bytes(n_blocks) for i in range(n))
@@ -414,6 +450,9 @@ def node_batch_main(args) -> int:
         "slowest_slot_ms_per_step": round(max(slot_ms) / args.steps, 4),
         "finite": ok,
     }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return 0 if ok else 1
     # the dominant kernel of slot 0 (HIP events inside the library, a few steps after the timed region)
     try:
         handle0.set_profiling(True)
@@ -470,7 +509,7 @@ def node_batch_leg(n: int, args, frames: int, headline_value, timeout_s: float =
     import signal
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(n), "--node-batch", "--steps", str(args.steps),
-           "--warmup", str(args.warmup), "--frames", str(frames), "--no-cpu-baseline"]
+           "--warmup", str(args.warmup), "--frames", str(frames), "--no-cpu-baseline", "--full"]
     cmd += ["--total-streams", str(args.total_streams)] if args.total_streams > 0 else ["--streams", str(args.streams)]
     if n > 1:
         cmd.append("--no-extras")
@@ -531,6 +570,11 @@ def main() -> int:
     ap.add_argument("--streams", type=int, default=STREAMS_PER_GPU, help="streams per GPU (weak scaling)")
     ap.add_argument("--total-streams", type=int, default=0,
                     help="fix the whole job's stream count instead (strong scaling; BASELINE configs[4]: 2048)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else too (extras, node-API leg, CPU baseline, live PMC "
+                         "traffic, strong mode's one-GPU comparison); a plain run does only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, a fixed sample, < 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the saturation sweep and the PCIe-inclusive leg")
     ap.add_argument("--pipelined", action="store_true", help="pipeline consecutive steps (ohs_batch_process_deferred)")
@@ -544,6 +588,9 @@ def main() -> int:
 
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         return 2
     if args.node_batch:
         return node_batch_main(args)            # one process whatever --gpus says; no torch.distributed
@@ -700,6 +747,8 @@ def main() -> int:
     if os.environ.get("OHS_BENCH_DUMP"):        # rehearsal test: this rank's outputs, for the bit-for-bit comparison
         np.save(os.environ["OHS_BENCH_DUMP"] + f".rank{rank}.npy",
                 np.concatenate([np.array([ids.start, ids.stop], np.float32), y[:, :, :4096].cpu().numpy().ravel()]))
+    if args.dump_outputs:                       # before any extra reuses y
+        dump_outputs(args.dump_outputs, y, parts=world, suffix=f"_rank{rank}" if world > 1 else "")
     total_frames = float(total_streams) * frames * args.steps
     value = total_frames / elapsed / 1e6
 
@@ -726,8 +775,8 @@ def main() -> int:
         whole_design = eq_b + conv_b                              # bytes the kernels are built to move
         traffic, traffic_source = load_traffic(dom)
         conv_traffic, _ = load_traffic(conv_name)
-        if traffic_source is not None and (world > 1 or args.no_live_pmc or args.no_extras or strong):
-            # the counters are collected live only by the default one-GPU run (two rocprofv3 --pmc child runs)
+        if traffic_source is not None and (world > 1 or not args.full or args.no_live_pmc or args.no_extras or strong):
+            # the counters are collected live only by the one-GPU --full run (two rocprofv3 --pmc child runs)
             traffic_source = "FALLBACK, not measured in this run: " + traffic_source
         ns_per_sample = eq_ms / max(n_calls, 1) * 1e6 / frames
         eq_wave_ring = 2 * S <= 2 * torch.cuda.get_device_properties(device).multi_processor_count and frames // 6 >= 8192
@@ -821,7 +870,7 @@ def main() -> int:
             out["rccl_world_size"] = dist.get_world_size()
             out["ranks"] = rank_records
             out["distinct_devices"] = len({r["uuid"] or r["pci_bus_id"] or (r["device_index"],) for r in rank_records})
-        if strong:
+        if strong and args.full:
             # Strong scaling of this job cannot beat the ratio of two ONE-GPU step times: the whole job's streams on one
             # GPU against this rank's share -- per-GPU step time is one EQ chain's serial recurrence up to ~1000 streams
             # per GPU, a property of the IIR, not of the fabric.  Both are measured here: the share is the timed region
@@ -857,8 +906,8 @@ def main() -> int:
                             "(profiles/r03_step_by_streams.txt): " + str(e)[:120]})
             out["expected_strong_scaling"] = exp
 
-    # ---- extras, N = 1 only, after the timed region ----
-    if world == 1 and not args.no_extras and not strong:
+    # ---- extras (--full), N = 1 only, after the timed region ----
+    if world == 1 and args.full and not args.no_extras and not strong:
         # The convolution by itself (BASELINE config 3 without the EQ): 8 steps back to back.  In the headline step
         # it runs in six slices underneath the EQ and `roofline.conv` shows what it gets there; this is the kernel
         # with the chip to itself, against HBM by its design bytes.
@@ -1083,7 +1132,7 @@ def main() -> int:
             elif out is not None:
                 out["roofline"]["traffic_live_error"] = src
     # ---- the node API (ohs_node_batch_*) next to the headline: a child run over the same devices ----
-    want_leg = not args.no_node_batch_leg and not args.no_extras
+    want_leg = args.full and not args.no_node_batch_leg and not args.no_extras
     # (gloo rehearsal on a box with fewer GPUs than ranks: the child takes the devices there are)
     leg_n = world if backend != "gloo" else min(world, torch.cuda.device_count())
     if want_leg and world == 1 and rank == 0:
@@ -1110,7 +1159,7 @@ def main() -> int:
             if rank == 0 and out is not None:
                 out.setdefault("node_batch", {"error": str(e)[:200]})
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(frames)
         print(json.dumps(out), flush=True)
     if distributed:

@@ -1,7 +1,7 @@
 """CPU suite: the host-side parsers of untrusted files (SOFA / HDF5 subset, AutoEQ CSV) built with
 AddressSanitizer + UBSan (gcc, CPU only) and run over regression inputs and a short mutation fuzz
 (tools/fuzz_host_parsers.cpp).  The regression inputs are single-field patches of the reference's DATA asset
-data/hrtf/subject_003.sofa (a data file; `need_asset` skips where it is absent):
+data/hrtf/subject_003.sofa (a data file, kept as tests/golden/subject_003_subset.sofa.gz):
   * Data.Delay dataspace [1][2] -> [2][2] / [0][2]: the round-1 reader indexed values[m*R + r] for every
     m < M (heap over-read, advisor finding);
   * a chunk B-tree node pointing at itself with level > 0 (unbounded walk);
@@ -14,9 +14,14 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOFA = "/root/reference/data/hrtf/subject_003.sofa"
-need_asset = pytest.mark.skipif(not os.path.exists(SOFA), reason="reference data asset not present on this box")
 DELAY_DIMS_OFF = 8256          # Data.Delay dataspace message: version 2, rank 2, dims u64 (1, 2) at this offset
+
+
+@pytest.fixture(scope="module")
+def sofa_file(tmp_path_factory):
+    """the reference's data asset subject_003.sofa, from tests/golden (tests/util.py: cipic_subject_003)"""
+    from tests.util import cipic_subject_003
+    return cipic_subject_003(tmp_path_factory.mktemp("sofa"))
 
 
 @pytest.fixture(scope="module")
@@ -48,15 +53,13 @@ def _run(binary, *args):
     return r.stdout
 
 
-@need_asset
-def test_pristine_asset_opens(fuzz_bin):
-    assert "status 0" in _run(fuzz_bin, SOFA, "--open")
+def test_pristine_asset_opens(fuzz_bin, sofa_file):
+    assert "status 0" in _run(fuzz_bin, sofa_file, "--open")
 
 
-@need_asset
 @pytest.mark.parametrize("dim0", [2, 0, 3, 1 << 40])
-def test_data_delay_with_foreign_leading_dimension(fuzz_bin, tmp_path, dim0):
-    raw = bytearray(open(SOFA, "rb").read())
+def test_data_delay_with_foreign_leading_dimension(fuzz_bin, tmp_path, dim0, sofa_file):
+    raw = bytearray(open(sofa_file, "rb").read())
     assert struct.unpack_from("<QQ", raw, DELAY_DIMS_OFF) == (1, 2)
     struct.pack_into("<Q", raw, DELAY_DIMS_OFF, dim0)
     p = tmp_path / "delay.sofa"
@@ -65,9 +68,8 @@ def test_data_delay_with_foreign_leading_dimension(fuzz_bin, tmp_path, dim0):
     assert "open: status" in out
 
 
-@need_asset
-def test_self_referencing_btree_node_terminates(fuzz_bin, tmp_path):
-    raw = bytearray(open(SOFA, "rb").read())
+def test_self_referencing_btree_node_terminates(fuzz_bin, tmp_path, sofa_file):
+    raw = bytearray(open(sofa_file, "rb").read())
     hits = [i for i in range(len(raw) - 4) if raw[i:i + 4] == b"TREE" and raw[i + 4] == 1]
     assert hits
     for node in hits:
@@ -84,9 +86,8 @@ def test_self_referencing_btree_node_terminates(fuzz_bin, tmp_path):
         assert "open: status" in _run(fuzz_bin, str(p), "--open")
 
 
-@need_asset
-def test_huge_dataspace_is_rejected_not_allocated(fuzz_bin, tmp_path):
-    raw = bytearray(open(SOFA, "rb").read())
+def test_huge_dataspace_is_rejected_not_allocated(fuzz_bin, tmp_path, sofa_file):
+    raw = bytearray(open(sofa_file, "rb").read())
     struct.pack_into("<QQ", raw, DELAY_DIMS_OFF, 1 << 31, 1 << 31)
     # the same on every rank-3 dataspace whose dims read (1250, 2, 200) = Data.IR
     pat = struct.pack("<QQQ", 1250, 2, 200)
@@ -99,7 +100,6 @@ def test_huge_dataspace_is_rejected_not_allocated(fuzz_bin, tmp_path):
     assert "status 8" in out or "status 6" in out        # OHS_ERR_PARSE (or ALLOC), never an abort
 
 
-@need_asset
-def test_short_mutation_fuzz(fuzz_bin):
-    out = _run(fuzz_bin, SOFA, "160")
+def test_short_mutation_fuzz(fuzz_bin, tmp_path, sofa_file):
+    out = _run(fuzz_bin, sofa_file, "160", str(tmp_path / "mutant.sofa"))
     assert "no crash" in out

@@ -8,8 +8,12 @@ import zlib
 import numpy as np
 import pytest
 
-SOFA = "/root/reference/data/hrtf/subject_003.sofa"
-need_asset = pytest.mark.skipif(not os.path.exists(SOFA), reason="reference data asset not present on this box")
+
+@pytest.fixture(scope="module")
+def sofa_file(tmp_path_factory):
+    """the reference's data asset subject_003.sofa, from tests/golden (tests/util.py: cipic_subject_003)"""
+    from tests.util import cipic_subject_003
+    return cipic_subject_003(tmp_path_factory.mktemp("sofa"))
 
 
 def test_open_non_existent_file():
@@ -43,10 +47,9 @@ def test_coordinate_conversion_roundtrip():
     assert np.allclose(MySofa.spherical_to_cartesian([0.0, 90.0, 2.0]), [0, 0, 2], atol=1e-6)
 
 
-@need_asset
-def test_cipic_subject_003_shapes_and_positions():
+def test_cipic_subject_003_shapes_and_positions(sofa_file):
     from open_headstage_amd.sofa import MySofa
-    s = MySofa(SOFA)
+    s = MySofa(sofa_file)
     assert (s.num_measurements, s.num_receivers, s.filter_length) == (1250, 2, 200)
     assert s.source_samplerate == 44100.0
     pos = np.stack([s.position(m) for m in range(s.num_measurements)])
@@ -55,24 +58,22 @@ def test_cipic_subject_003_shapes_and_positions():
     assert np.allclose(s.position(308), [30, 0, 1]) and np.allclose(s.position(908), [330, 0, 1])
 
 
-@need_asset
-def test_data_ir_matches_independent_decoder():
+def test_data_ir_matches_independent_decoder(sofa_file):
     from open_headstage_amd.sofa import MySofa
-    raw = open(SOFA, "rb").read()
+    raw = open(sofa_file, "rb").read()
     # Data.IR is one deflate+shuffle chunk of 4,000,000 B at file offset 60771
     dec = zlib.decompressobj().decompress(raw[60771:])
     assert len(dec) == 1250 * 2 * 200 * 8
     unshuffled = np.frombuffer(dec, np.uint8).reshape(8, -1).T.copy().view("<f8").reshape(1250, 2, 200)
-    s = MySofa(SOFA)
+    s = MySofa(sofa_file)
     for m in (0, 1, 308, 908, 1249):
         for r in (0, 1):
             assert np.array_equal(s.ir(m, r), unshuffled[m, r].astype(np.float32)), (m, r)
 
 
-@need_asset
-def test_nearest_lookup_matches_brute_force():
+def test_nearest_lookup_matches_brute_force(sofa_file):
     from open_headstage_amd.sofa import MySofa
-    s = MySofa(SOFA)
+    s = MySofa(sofa_file)
     pos = np.stack([s.position(m) for m in range(s.num_measurements)]).astype(np.float64)
     az, el = np.radians(pos[:, 0]), np.radians(pos[:, 1])
     xyz = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], 1)
@@ -87,11 +88,10 @@ def test_nearest_lookup_matches_brute_force():
     assert s.nearest(30.0, 0.0) == 308 and s.nearest(-30.0, 0.0) == 908 and s.nearest(330.0, 0.0) == 908
 
 
-@need_asset
-def test_fixture_is_what_the_reader_returns_and_resampling_is_sane():
+def test_fixture_is_what_the_reader_returns_and_resampling_is_sane(sofa_file):
     from open_headstage_amd import sofa
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "cipic003_pm30.npz"))
-    s = sofa.MySofa(SOFA)
+    s = sofa.MySofa(sofa_file)
     irs = sofa.speaker_hrirs(s)
     assert np.array_equal(np.stack(irs), g["irs_44100"])
     # left speaker (az +30): the left ear is the near ear -- louder and earlier
@@ -106,13 +106,12 @@ def test_fixture_is_what_the_reader_returns_and_resampling_is_sane():
 
 
 # ---- pin against the reference's own processed_hrir.wav (fixture: tools/make_sofa_fixture.py) ----------------------
-@need_asset
-def test_get_ir_matches_the_references_processed_hrir_wav():
+def test_get_ir_matches_the_references_processed_hrir_wav(sofa_file):
     """data/hrtf/processed_hrir.wav holds measurements 355 and 171 of subject_003.sofa (receivers 0, 1) as
     16-bit PCM: every sample of ohs_sofa_get_ir, quantised the same way (clipping included), is within 1 LSB."""
     from open_headstage_amd.sofa import MySofa
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "processed_hrir_wav.npz"))
-    s = MySofa(SOFA)
+    s = MySofa(sofa_file)
     assert float(g["fs"]) == s.source_samplerate and g["pcm"].shape == (s.filter_length, 4)
     for ch in range(4):
         ir = s.ir(int(g["measurement"][ch]), int(g["receiver"][ch]))
@@ -124,11 +123,10 @@ def test_get_ir_matches_the_references_processed_hrir_wav():
 
 
 # ---- libmysofa-style conditioning (ohs_sofa_open_ex; parity unpinned, checked against independent numpy) -----------
-@need_asset
-def test_loudness_normalisation_as_mysofa_loudness():
+def test_loudness_normalisation_as_mysofa_loudness(sofa_file):
     from open_headstage_amd import sofa
-    raw = sofa.MySofa(SOFA)
-    s = sofa.MySofa(SOFA, sofa.SOFA_LOUDNESS)
+    raw = sofa.MySofa(sofa_file)
+    s = sofa.MySofa(sofa_file, sofa.SOFA_LOUDNESS)
     pos = np.stack([raw.position(m) for m in range(raw.num_measurements)])
     key = pos[:, 0] + pos[:, 1]
     frontal = int(np.argmin(key))                       # libmysofa: smallest azimuth + elevation (first on ties)
@@ -141,11 +139,10 @@ def test_loudness_normalisation_as_mysofa_loudness():
     assert raw.loudness_factor() == 1.0
 
 
-@need_asset
-def test_neighbours_and_interpolation_as_mysofa_getfilter():
+def test_neighbours_and_interpolation_as_mysofa_getfilter(sofa_file):
     from open_headstage_amd import sofa
-    s = sofa.MySofa(SOFA, sofa.SOFA_INTERPOLATE)
-    raw = sofa.MySofa(SOFA)
+    s = sofa.MySofa(sofa_file, sofa.SOFA_INTERPOLATE)
+    raw = sofa.MySofa(sofa_file)
     M = s.num_measurements
     pos = np.stack([s.position(m) for m in range(M)]).astype(np.float64)
     az, el = np.radians(pos[:, 0]), np.radians(pos[:, 1])
@@ -196,11 +193,10 @@ def test_neighbours_and_interpolation_as_mysofa_getfilter():
     assert np.allclose(l5, l1, atol=1e-7) and np.allclose(r5, r1, atol=1e-7)
 
 
-@need_asset
-def test_open_like_mysofa_resamples_everything_to_the_target_rate():
+def test_open_like_mysofa_resamples_everything_to_the_target_rate(sofa_file):
     from open_headstage_amd import sofa
-    raw = sofa.MySofa(SOFA)
-    s = sofa.MySofa.open_like_mysofa(SOFA, 48000.0)
+    raw = sofa.MySofa(sofa_file)
+    s = sofa.MySofa.open_like_mysofa(sofa_file, 48000.0)
     assert s.source_samplerate == 48000.0 and s.filter_length == 218          # ceil(200 * 48000 / 44100)
     f = np.float32(s.loudness_factor())
     want = sofa.resample_ir(raw.ir(308, 0), 44100.0, 48000.0)
@@ -208,7 +204,7 @@ def test_open_like_mysofa_resamples_everything_to_the_target_rate():
     irs = sofa.speaker_hrirs(s)                                              # no second resampling
     assert all(h.size == 218 for h in irs)
     with pytest.raises(Exception):
-        sofa.MySofa(SOFA, 64)                                               # unknown flag
+        sofa.MySofa(sofa_file, 64)                                               # unknown flag
 
 
 # ---- a SOFA file written from scratch (tests/util.py) + the speaker wiring's impulse responses (no device needed) -----
@@ -262,10 +258,9 @@ def test_speaker_irs_of_the_c_abi_equal_the_python_wiring_on_a_synthetic_file(tm
     _check_speaker_irs(MySofa(write_minimal_sofa(str(tmp_path / "g.sofa"), ir, pos, 44100.0)))
 
 
-@need_asset
-def test_speaker_irs_of_the_c_abi_equal_the_python_wiring_on_cipic_subject_003():
+def test_speaker_irs_of_the_c_abi_equal_the_python_wiring_on_cipic_subject_003(sofa_file):
     from open_headstage_amd import sofa
-    s = sofa.MySofa(SOFA)
+    s = sofa.MySofa(sofa_file)
     _check_speaker_irs(s)
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "cipic003_pm30.npz"))
     assert np.array_equal(np.stack(sofa.speaker_irs_plugin_angles(s, fs=48000.0)), g["irs_48000"])      # the plugin's default angles

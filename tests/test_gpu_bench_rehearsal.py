@@ -15,7 +15,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "2", "--warmup", "1", "--frames", "20480", "--no-cpu-baseline", "--no-extras"]
+COMMON = ["--steps", "2", "--warmup", "1", "--frames", "20480", "--full", "--no-cpu-baseline", "--no-extras"]
 
 
 def _run(tmp_path, tag, world, extra, port, launcher="torchrun"):
@@ -85,7 +85,7 @@ def test_node_batch_mode_is_the_headline_at_one_gpu(tmp_path):
     """`bench.py --gpus 1 --node-batch` -- ONE process through ohs_node_batch_* only (the C-ABI path a Rust host binds) --
     against the plain headline run on the same box: same bits, the same rate within 2 % (the verdict asks for 1 %; the
     measured ratio is printed and recorded in profiles/), and the record's device evidence."""
-    flags = ["--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-extras"]
+    flags = ["--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-extras"]
     plain = _bench(["--gpus", "1", *flags], {"OHS_BENCH_DUMP": str(tmp_path / "plain")})
     node = _bench(["--gpus", "1", "--node-batch", *flags], {"OHS_BENCH_DUMP": str(tmp_path / "node")})
     assert node["mode"] == "node_batch" and node["metric"] == plain["metric"] and node["unit"] == "Msamples/s"
@@ -107,10 +107,36 @@ def test_node_batch_mode_is_the_headline_at_one_gpu(tmp_path):
 def test_two_rank_record_carries_the_node_batch_leg(tmp_path):
     """At N > 1 rank 0 measures the node API in a child run while the other ranks wait on the rendezvous store (CPU side).
     Rehearsed at world size 2 over gloo on this one-GPU box: the child then drives the one device there is."""
-    rec = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "20480", "--streams", "6", "--no-cpu-baseline"],
+    rec = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "20480", "--streams", "6", "--full",
+                  "--no-cpu-baseline"],
                  {"OHS_BENCH_DIST_BACKEND": "gloo"})
     assert rec["n_gpus"] == 2 and rec["rccl_world_size"] == 2 and rec["launcher"] == "self"
     nbr = rec["node_batch"]
     assert "error" not in nbr, nbr
     assert nbr["rccl_comm_size"] == 1 and nbr["finite"] and nbr["value"] > 0 and len(nbr["slots"]) == 1
     assert nbr["slots"][0]["n_streams"] == 6
+
+
+def test_plain_run_measures_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """A plain run (no --full) times --steps steps and prints the contract's record without the extras; --dump-outputs
+    writes the last timed step's output, the same files bit for bit when the run is repeated with the same arguments."""
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "20480", "--streams", "12"]
+    recs, dumps = [], []
+    for i in range(2):
+        out = tmp_path / f"out{i}"
+        recs.append(_bench([*args, "--dump-outputs", str(out)], {"OHS_BENCH_DUMP": str(tmp_path / f"plain{i}")}))
+        dumps.append({f: np.load(str(out / f)) for f in sorted(os.listdir(out))})
+    rec = recs[0]
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["finite"]
+    assert rec["unit"] == "Msamples/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    for k in ("saturation", "pcie_inclusive", "long_ir", "cpu_baseline", "node_batch", "expected_strong_scaling"):
+        assert k not in rec, k
+    assert "conv_alone" not in rec["roofline"]
+    assert sorted(dumps[0]) == ["y_head.npy", "y_sample.npy", "y_tail.npy"]
+    assert all(v.dtype == np.float32 for v in dumps[0].values())
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f].view(np.uint32), dumps[1][f].view(np.uint32)), f
+    # the head is the step's output: the first 4 096 frames of every stream, as the rehearsal dump records them
+    a = np.load(str(tmp_path / "plain0") + ".rank0.npy")[2:].reshape(12, 2, 4096)
+    k = min(4096, dumps[0]["y_head.npy"].shape[2])
+    assert np.array_equal(dumps[0]["y_head.npy"][:, :, :k], a[:, :, :k])

@@ -1,7 +1,21 @@
 """Shared helpers for the parity tests."""
+import gzip
+import os
+
 import numpy as np
 
 RMS_TOL = 1e-6   # BASELINE.json north_star: <= 1e-6 RMS float error vs the reference CPU path
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def cipic_subject_003(dest_dir):
+    """The reference's data asset data/hrtf/subject_003.sofa (CIPIC subject 003) as the SOFA tests read it, unpacked from
+    tests/golden/subject_003_subset.sofa.gz into dest_dir: every byte of the original except the Data.IR values of the
+    measurements those tests never read, which are zero (tools/make_sofa_fixture.py).  -> path of the .sofa file"""
+    path = os.path.join(str(dest_dir), "subject_003.sofa")
+    with gzip.open(os.path.join(GOLDEN, "subject_003_subset.sofa.gz"), "rb") as f, open(path, "wb") as g:
+        g.write(f.read())
+    return path
 
 
 def rms(a):

@@ -9,7 +9,7 @@ root=$(pwd)
 out=$root/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-python3 bench.py --steps 10 --warmup 3 > "$out/bench.json" 2> "$out/bench.err"
+python3 bench.py --full --steps 10 --warmup 3 > "$out/bench.json" 2> "$out/bench.err"
 echo "bench done"; cat "$out/bench.json"
 python3 tools/bench_configs.py > "$out/other_configs.jsonl" 2> "$out/other_configs.err"
 # native latency harness: the JSON lines join the other configs, the whole output (with the device-side phases) is kept too

@@ -2,7 +2,7 @@
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude \\
 //       -Iopen_headstage_amd/csrc -o /tmp/ohs_fuzz tools/fuzz_host_parsers.cpp \\
 //       open_headstage_amd/csrc/sofa_reader.cpp open_headstage_amd/csrc/autoeq_parser.cpp -lz
-//   /tmp/ohs_fuzz <some.sofa> [iterations]
+//   /tmp/ohs_fuzz <some.sofa> [iterations [path of the mutated copy, default /tmp/ohs_fuzz_mut.sofa]]
 // Round 2: bounds-checked reads, B-tree visit limits, size caps and try/catch at the ABI after the advisor's
 // Data.Delay [2][R] over-read; `--open` mode runs single regression files (tests/test_cpu_parsers_asan.py).
 // Round 1: found one shift-by-corrupt-count (fixed, with a guard on corrupt heap headers); then 6 000 mutated
@@ -50,7 +50,7 @@ static int exercise(const char *path, bool resample = false)
 
 int main(int argc, char **argv)
 {
-    if (argc < 2) { printf("usage: %s <file.sofa> [iterations | --open]\n", argv[0]); return 2; }
+    if (argc < 2) { printf("usage: %s <file.sofa> [iterations [mutant path] | --open]\n", argv[0]); return 2; }
     const char *src = argv[1];
     if (argc > 2 && !strcmp(argv[2], "--open")) {      // regression inputs: one file, as it is
         const int rc = exercise(src, true);
@@ -58,6 +58,7 @@ int main(int argc, char **argv)
         return 0;
     }
     const int iters = argc > 2 ? atoi(argv[2]) : 300;
+    const char *mut = argc > 3 ? argv[3] : "/tmp/ohs_fuzz_mut.sofa";
     std::vector<unsigned char> good = slurp(src);
     if (good.empty()) { printf("cannot read %s\n", src); return 2; }
     std::mt19937_64 rng(12345);
@@ -89,8 +90,10 @@ int main(int argc, char **argv)
                 if (o + 8 < m.size()) { const unsigned long long v = rng() & 3 ? rng() % 70000 : ~0ull; memcpy(&m[o], &v, 1 + rng() % 8); }
             }
         }
-        FILE *f = fopen("/tmp/ohs_fuzz_mut.sofa", "wb"); fwrite(m.data(), 1, m.size(), f); fclose(f);
-        if (exercise("/tmp/ohs_fuzz_mut.sofa") == OHS_OK) ++ok; else ++bad;
+        FILE *f = fopen(mut, "wb");
+        if (!f) { printf("cannot write %s\n", mut); return 2; }
+        fwrite(m.data(), 1, m.size(), f); fclose(f);
+        if (exercise(mut) == OHS_OK) ++ok; else ++bad;
     }
     printf("sofa: %d mutated files opened, %d rejected, no crash\n", ok, bad);
     // AutoEQ CSV
