@@ -9,8 +9,9 @@
 // I/O port -- capture 4 outputs, inject 4 inputs -- runs every 4 steps: 6 + 2 / 4 = 6.5 instructions per sample.  gfx950
 // still executes gfx9's wave-wide DPP controls at the row controls' cost (wave_ror:1; tools/ubench_wave_dpp.hip,
 // profiles/r05_ubench_wave_dpp.txt).  With the ring closed over the wave, lanes 13 .. 63 pass samples on, rows 1 .. 3
-// are a conveyor of 48 samples, and the port -- two moves with row_mask 0xe, one store, one load -- runs every 48 steps:
-// 6 + 2 / 48 = 6.04 instructions per sample (prototype: tools/proto_eq_wave_ring.py, 11.02 against 11.49 ns).
+// are a conveyor of 48 samples, and the port -- one store, one inject move, one load (eq_ring64_groups) -- runs every 48 steps:
+// 6 + 1 / 48 = 6.02 VALU instructions per sample (prototype: tools/proto_eq_wave_ring.py, 11.02 against 11.49 ns with the
+// round-5 port of two moves).
 //
 // Lane roles and arithmetic are eq_ring2_body.hpp's (band L: pre lane L, post lane L + 1; O T A P N M per step), with
 // wave_ror:1 where that form has row_ror:1.  What differs is how a launch starts and ends.  The same six instructions
@@ -34,7 +35,7 @@ constexpr int kWaveRor1 = 0x13C;        // DPP_WF_RR1: lane l <- lane l - 1, lan
 constexpr int kR64Group = 48;           // samples per group = lanes of the conveyor
 
 struct Ring64Regs {
-    float X, st;        // v2, v3
+    float X, st;        // v2, st: the C++ form's outgoing samples (the asm stores from X)
     v2f u;              // v[4:5]   (b0, b1) * X of the pre lane
     float b2x;          // v7       b2 * X(wave_ror:1) of the post lane
     v2f s;              // v[10:11] (s1, s2)
@@ -53,6 +54,20 @@ __device__ __forceinline__ void ring64_pm(Ring64Regs &r, const RingLane &c)
     r.b2x = c.b2 * dpp_mov<kWaveRor1>(r.X, r.X);
 }
 
+// A raw buffer resource (V#) over `bytes` bytes from `base`: stride 0, no swizzle, DATA_FORMAT 32 (a gfx9 buffer with format 0
+// is invalid).  Wave-uniform: it lives in four scalar registers.
+typedef unsigned ring64_rsrc_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ ring64_rsrc_t ring64_rsrc(const void *base, unsigned bytes)
+{
+    const unsigned long long a = (unsigned long long)base;
+    ring64_rsrc_t v;
+    v.x = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a);
+    v.y = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xFFFFu));
+    v.z = (unsigned)__builtin_amdgcn_readfirstlane((int)bytes);
+    v.w = 0x00020000u;
+    return v;
+}
+
 #define R64_FULL "row_mask:0xf bank_mask:0xf\n"
 #define R64_O "v_add_f32_dpp v2, v4, v10 wave_ror:1 " R64_FULL
 #define R64_T "v_add_f32_dpp v6, v5, v11 wave_ror:1 " R64_FULL
@@ -67,63 +82,87 @@ __device__ __forceinline__ void ring64_pm(Ring64Regs &r, const RingLane &c)
 #define R64_X16(B) R64_X8(B) R64_X8(B)
 #define R64_X32(B) R64_X16(B) R64_X16(B)
 #define R64_STEPS47 R64_X32(R64_STEP) R64_X8(R64_STEP) R64_X4(R64_STEP) R64_X2(R64_STEP) R64_STEP
-#define R64_ROWS123 "quad_perm:[0,1,2,3] row_mask:0xe bank_mask:0xf\n"
 
-// One interior group as asm text: 47 plain steps, the port step (the input register REG is injected and refilled in place).
-#define R64_GROUP(REG) \
+// The port of one group: 4 issue slots.  The 48 outputs in rows 1 .. 3 of X leave straight from X (buffer_store_dword: a
+// store of 32 data bits needs no wait state before a VALU overwrites its data register -- only stores wider than 64 bits do,
+// and the s_waitcnt is between them anyway), then v_cndmask (VCC = rows 1 .. 3) injects the input register REG into rows
+// 1 .. 3, and REG is refilled three groups ahead.  Row 0 is kept out of the I/O by its offset, not by EXEC: v0 is
+// 0xFFFFF000 there, beyond any launch's num_records, so its store is dropped and its load returns 0 (never injected: VCC).
+// SOFF / LOFF: the group's store / load byte offsets from v0, which is this lane's store slot of the block's first group.
+#define R64_PORT(REG, SOFF, LOFF) \
+        "buffer_store_dword v2, v0, %[rout], 0 offen offset:" SOFF "\n" \
+        "s_waitcnt vmcnt(3)\n" \
+        "v_cndmask_b32_e32 v2, v2, " REG ", vcc\n" \
+        "buffer_load_dword " REG ", v0, %[rin], 0 offen offset:" LOFF "\n"
+// One interior group as asm text: 47 plain steps, the port step.  Group k (0 .. 3) of a block stores at 192 k and loads
+// group k + 3 at 192 k + 640 (the store slot of lane l >= 16 is sample 48 g + 47 - l, its input slot 48 g + 63 - l).
+#define R64_GROUP(REG, SOFF, LOFF) \
         R64_STEPS47 \
         R64_O R64_T R64_A \
-        "s_waitcnt vmcnt(2)\n" \
-        "s_nop 0\n" \
-        "v_mov_b32_dpp v3, v2 " R64_ROWS123 \
-        "v_mov_b32_dpp v2, " REG " " R64_ROWS123 \
-        "s_mov_b32 exec_lo, %[mlo]\n" \
-        "v_min_u32_e32 v18, %[maxo], v0\n" \
-        "global_store_dword v0, v3, %[dst] offset:-64\n" \
-        "global_load_dword " REG ", v18, %[src] offset:576\n" \
-        "s_mov_b32 exec_lo, -1\n" \
-        "v_add_u32_e32 v0, %[kg], v0\n" \
+        R64_PORT(REG, SOFF, LOFF) \
         R64_P R64_N R64_M
+#define R64_GROUP0 R64_GROUP("v16", "0", "640")
+#define R64_GROUP1 R64_GROUP("v17", "192", "832")
+#define R64_GROUP2 R64_GROUP("v16", "384", "1024")
+#define R64_GROUP3 R64_GROUP("v17", "576", "1216")
 
-// `pairs` >= 1 PAIRS of interior groups in ONE statement: every sample they filter and store exists, no band starts or
-// ends inside them.  The input register is double-buffered (v16: even groups, v17: odd ones): the port of group g injects
+// `groups` >= 1 interior groups (1, 2, ...) in ONE statement: every sample they filter and store exists, no band starts or
+// ends inside them.  The input register is double-buffered (v16: odd groups, v17: even ones): the port of group g injects
 // group g + 1, requested at port g - 2, and requests group g + 3 into the register it has just emptied -- 96 steps =
 // ~1.06 us between a load and its use (with one register and 48 steps the wave waited for memory at every port: the
-// prototype, alone on the chip, 11.05 -> 10.88 ns per sample; profiles/r05_proto_eq_wave_ring_ahead.txt).  In front of a
-// port the store and the load of the previous port may still be in flight: vmcnt(2) (they retire in issue order).
-// Loads may reach beyond the launch's last sample: the address is clamped to that sample's (`max_load_off`), so what
-// arrives there is a copy of it instead of the zero the C++ form puts -- harmless: every band's state has left its lane
-// before such a value reaches it, and outputs beyond n are never stored.
+// prototype, alone on the chip, 11.05 -> 10.88 ns per sample; profiles/r05_proto_eq_wave_ring_ahead.txt).  Behind a port's
+// store the store and the load of each of the two previous ports may still be in flight: vmcnt(3) (they retire in issue
+// order).
+// The I/O goes through buffer resources over the launch's n samples of the chain (`rin` / `rout`, num_records = 4 n).  Raw
+// buffer (stride 0) range check, gfx9 / CDNA MUBUF rule: an access is out of range when its offset -- VGPR offset plus the
+// instruction's offset field; the scalar soffset is NOT part of the check, so it is 0 here -- is >= num_records; an
+// out-of-range load returns 0, an out-of-range store is dropped.  So loads beyond the launch's last sample return 0, as in
+// the C++ form, and row 0 (v0 = 0xFFFFF000 >= 4 n: eq_ring2_addressable keeps 4 n + 4096 below 2^32, and row 0's v0 never
+// moves: `inc` is 0 there) neither stores nor loads anything.
+// Loop: four groups per iteration, immediate offsets inside it, one v0 advance (v_add of `inc` = 768 bytes in rows 1 .. 3)
+// and one counter step + branch; then a tail of groups % 4 groups (0 .. 3) that leaves where they end.  Issue slots per
+// group beyond the 288 step instructions: (4 x 4 + 3) / 4 = 4.75 (before: 6.04 ... 11.5 per group: DESIGN 4.5).
 // On entry: the first step's P and M have run (by the C++ form), v16 / v17 = the inputs of the two groups BEHIND the first
-// one here, v0 = this lane's byte offset of the first group's input slot; on exit v16 = the inputs of the group behind the
-// next one.  Every 8-byte encoding is 8-byte aligned (a lone wave pays for one that straddles a fetch line); the
-// vector-memory instructions run with row 0 masked.
-__device__ __forceinline__ void eq_ring64_groups(const RingLane &c, Ring64Regs &r, float &xnext, float xnext2, unsigned &lane_off,
-                                                 const float *src, float *dst, int pairs, unsigned max_load_off)
+// one here, v0 = this lane's store slot of the first group; on exit `xnext` = the inputs of the group behind the next one.
+// Every 8-byte encoding is 8-byte aligned (a lone wave pays for one that straddles a fetch line): the 4-byte instructions
+// come in pairs (s_waitcnt + v_cndmask, s_add + s_cbranch, s_cmp + s_cbranch; v_add_u32 in its 8-byte VOP3 form).
+__device__ __forceinline__ void eq_ring64_groups(const RingLane &c, Ring64Regs &r, float &xnext, float xnext2, unsigned lane_off,
+                                                 unsigned inc, ring64_rsrc_t rin, ring64_rsrc_t rout, int groups)
 {
     const v2f pb01 = {c.pb0, c.pb1}, a12 = {c.a1, c.a2};
-    unsigned cnt = (unsigned)__builtin_amdgcn_readfirstlane(pairs);
-    unsigned kg = kR64Group * 4;                        // (not const: the host pass of hipcc refuses constants as asm operands)
-    unsigned mlo = 0xFFFF0000u;                         // EXEC's low half with row 0 off (a 64-bit literal would reach the
-                                                        // scalar unit as its low 32 bits, zero-extended: rows 2 and 3 off as well)
+    const unsigned ng = (unsigned)__builtin_amdgcn_readfirstlane(groups);
+    unsigned cnt = 0u - (ng >> 2);                      // counts up to 0: s_add_u32's carry ends the loop
+    const unsigned tail = ng & 3u;
     asm volatile(
+        "s_mov_b32 vcc_lo, 0xffff0000\n"                // VCC = rows 1 .. 3 (the C++ form's last P and M are 2+ wait states
+        "s_mov_b32 vcc_hi, -1\n"                        // behind by the first DPP read of v4)
+        "s_cmp_eq_u32 %[cnt], 0\n"
+        "s_cbranch_scc1 2f\n"
         ".p2align 5\n"
-        "s_nop 1\n"
-        "s_nop 0\n"
         "1:\n"
-        R64_GROUP("v16")
-        R64_GROUP("v17")
-        "s_sub_u32 %[cnt], %[cnt], 1\n"
-        "s_cmp_lg_u32 %[cnt], 0\n"
-        "s_cbranch_scc1 1b\n"
-        "s_nop 0\n"
+        R64_GROUP0 R64_GROUP1 R64_GROUP2 R64_GROUP3
+        "v_add_u32_e64 v0, v0, v3\n"
+        "s_add_u32 %[cnt], %[cnt], 1\n"
+        "s_cbranch_scc0 1b\n"
+        "2:\n"
+        "s_cmp_eq_u32 %[tail], 0\n"
+        "s_cbranch_scc1 3f\n"
+        R64_GROUP0
+        "s_cmp_eq_u32 %[tail], 1\n"
+        "s_cbranch_scc1 3f\n"
+        R64_GROUP1
+        "s_cmp_eq_u32 %[tail], 2\n"
+        "s_cbranch_scc1 3f\n"
+        R64_GROUP2
+        "3:\n"
         "s_waitcnt vmcnt(0)\n"
         "s_nop 1\n"
-        : [X] "+{v2}"(r.X), [st] "+{v3}"(r.st), [u] "+{v[4:5]}"(r.u), [b2x] "+{v7}"(r.b2x), [s] "+{v[10:11]}"(r.s),
+        : [X] "+{v2}"(r.X), [u] "+{v[4:5]}"(r.u), [b2x] "+{v7}"(r.b2x), [s] "+{v[10:11]}"(r.s),
           [voff] "+{v0}"(lane_off), [xa] "+{v16}"(xnext), [xb] "+{v17}"(xnext2), [cnt] "+s"(cnt)
-        : [b2] "{v1}"(c.b2), [pb01] "{v[12:13]}"(pb01), [a12] "{v[14:15]}"(a12), [src] "s"(src), [dst] "s"(dst), [kg] "s"(kg),
-          [mlo] "s"(mlo), [maxo] "s"(max_load_off)
-        : "v6", "v8", "v9", "v18", "memory", "scc");
+        : [b2] "{v1}"(c.b2), [inc] "{v3}"(inc), [pb01] "{v[12:13]}"(pb01), [a12] "{v[14:15]}"(a12), [rin] "s"(rin),
+          [rout] "s"(rout), [tail] "s"(tail)
+        : "v6", "v8", "v9", "vcc", "memory", "scc");
+    if (ng & 1u) xnext = xnext2;                        // (an odd number of groups ends on v16's turn: v17 holds the next)
 }
 
 // PER_STREAM: the chain's stream owns its bands (parametric_eq.rs:125-129) -- constants, state slots and the NUMBER of enabled
@@ -166,7 +205,6 @@ __device__ __forceinline__ void eq_ring64_wave_t(const float *in, float *out, lo
     float *state0 = state + chain * (kEqStateSlots * 2);
     const unsigned state_off = (unsigned)(slot * 2) * 4u;
     const bool conv = lane >= 16;
-    unsigned lane_off = (unsigned)(63 - lane) * 4u;
     v2f s_init = {0.0f, 0.0f};
     if (band) { s_init.x = ring2_ld(state0, state_off); s_init.y = ring2_ld(state0, state_off + 4u); }
     v2f s_save = s_init;
@@ -209,14 +247,15 @@ __device__ __forceinline__ void eq_ring64_wave_t(const float *in, float *out, lo
     const int g_total = (n32 + 16 + G - 1) / G;
     group_cpp(0);
     int g = 1;
-    // groups 1 .. n / 48 - 1, two at a time (an odd one left over runs in the C++ form): every step filters existing samples
-    // (the last of them ends at step 48 (n / 48) <= n: the first state leaves behind step n + 1), every store lands below n
-    const int n_pairs = n32 >= 4 * G ? (n32 / G - 1) / 2 : 0;
-    if (n_pairs >= 1) {
-        const float xnext2 = load_group(3);         // (exists: n >= 192)
-        lane_off += (unsigned)(G * 4);
-        eq_ring64_groups(c, r, xnext, xnext2, lane_off, src0, dst0, n_pairs, (unsigned)(n32 - 1) * 4u - 576u);
-        g += 2 * n_pairs;
+    // groups 1 .. n / 48 - 1 in asm: every step filters existing samples (the last of them ends at step 48 (n / 48) <= n: the
+    // first state leaves behind step n + 1), every store lands below n; the one or two groups behind them run in the C++ form
+    const int n_full = n32 / G;
+    if (n_full >= 2) {
+        const float xnext2 = load_group(3);         // (zeros beyond n)
+        const unsigned bytes = (unsigned)n32 * 4u;
+        eq_ring64_groups(c, r, xnext, xnext2, conv ? (unsigned)(G + 47 - lane) * 4u : 0xFFFFF000u, conv ? 4u * G * 4u : 0u,
+                         ring64_rsrc(src0, bytes), ring64_rsrc(dst0, bytes), n_full - 1);
+        g = n_full;
     }
     for (; g < g_total; ++g) group_cpp(g);
     if (band) {

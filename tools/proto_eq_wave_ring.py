@@ -44,6 +44,12 @@ M = f"v_mul_f32_dpp v7, v2, v1 {RT} {FULL}"
 # PROTO_AHEAD=2: the input register is double-buffered (v16 / v17, two groups per loop iteration): a load is consumed two
 # ports = 96 steps = ~1.06 us after its issue instead of 48 steps = ~0.53 us
 AHEAD = int(os.environ.get("PROTO_AHEAD", "1"))
+# PROTO_PORT=buffer: the product's port since round 6 (csrc/eq_ring64_body.hpp): buffer resources over the chain's n samples
+# (row 0's offset beyond num_records: its store is dropped, its load returns 0 -- no EXEC writes, no clamp), the store straight
+# from X, v_cndmask (VCC = rows 1 .. 3) as the inject move, four groups per iteration with immediate offsets, one v0 advance
+# and one counter step + branch per iteration: 4.75 issue slots per group beyond the 288 step instructions (AHEAD=2's
+# double-buffered input registers, implied)
+PORT = os.environ.get("PROTO_PORT", "global")
 
 
 def group(reg="v16", wait="s_waitcnt vmcnt(0)", load_off=2 * G * 4):
@@ -65,8 +71,26 @@ def group(reg="v16", wait="s_waitcnt vmcnt(0)", load_off=2 * G * 4):
     return out
 
 
+def group_buf(reg, k):
+    """group k (0 .. 3) of a buffer-port iteration: the store at 192 k from v0, the load of three groups ahead at 576 + 192 k"""
+    out = []
+    for s in range(G):
+        out += [O, T, A]
+        if s == G - 1:
+            out += [f"buffer_store_dword v2, v0, %[rout], 0 offen offset:{192 * k}",
+                    "s_waitcnt vmcnt(3)",                   # behind this store: the two previous ports' store + load may fly
+                    f"v_cndmask_b32_e32 v2, v2, {reg}, vcc",
+                    f"buffer_load_dword {reg}, v0, %[rin], 0 offen offset:{576 + 192 * k}"]
+        out += [P, N, M]
+    return out
+
+
 def main():
-    if AHEAD == 2:
+    if PORT == "buffer":
+        four = group_buf("v16", 0) + group_buf("v17", 1) + group_buf("v16", 2) + group_buf("v17", 3)
+        body = (["s_mov_b32 vcc_lo, 0xffff0000", "s_mov_b32 vcc_hi, -1", ".p2align 5", "1:"] + four +
+                ["v_add_u32_e64 v0, v0, v3", "s_add_u32 %[cnt], %[cnt], 1", "s_cbranch_scc0 1b", "s_waitcnt vmcnt(0)", "s_nop 1"])
+    elif AHEAD == 2:
         # port g injects group g + 1 (loaded at port g - 2) and requests group g + 3 into the register it has just emptied;
         # in front of it the store and the load of port g - 1 may still be in flight: vmcnt(2)
         two = group("v16", "s_waitcnt vmcnt(2)", 3 * G * 4) + group("v17", "s_waitcnt vmcnt(2)", 3 * G * 4)
@@ -74,7 +98,7 @@ def main():
     else:
         body = [".p2align 5", "1:"] + group() + ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_lg_u32 %[cnt], 0", "s_cbranch_scc1 1b", "s_waitcnt vmcnt(0)", "s_nop 1"]
     asm = "\n".join('        "' + l + '\\n"' for l in body)
-    n_valu = sum(1 for l in group() if l.startswith("v_") and not l.startswith("v_add_u32"))
+    n_valu = sum(1 for l in (group_buf("v16", 0) if PORT == "buffer" else group()) if l.startswith("v_") and not l.startswith("v_add_u32"))
     src = r'''
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -82,7 +106,20 @@ def main():
 #include <cstring>
 #include <vector>
 typedef float v2f __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int G = %(G)d, NB = 10;
+constexpr bool BUF = %(buf)d;
+// raw buffer resource over `bytes` bytes (stride 0, DATA_FORMAT 32)
+__device__ u32x4 rsrc(const void *p, unsigned bytes)
+{
+    const unsigned long long a = (unsigned long long)p;
+    u32x4 v;
+    v.x = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a);
+    v.y = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xFFFFu));
+    v.z = (unsigned)__builtin_amdgcn_readfirstlane((int)bytes);
+    v.w = 0x00020000u;
+    return v;
+}
 struct Coef { float b0[NB], b1[NB], b2[NB], a1[NB], a2[NB]; };
 
 // one chain per wave (= per workgroup); chain c: src + c * stride, n = groups * G samples, zero state at entry
@@ -101,11 +138,16 @@ __global__ __launch_bounds__(64) void k(const float *src, float *dst, long long 
     float X = 0.f, st = 0.f, b2x = 0.f, xin;
     v2f u = {0.f, 0.f}, s = {0.f, 0.f};
     unsigned cnt = (unsigned)groups, kg = G * 4;
+    // PROTO_PORT=buffer: offsets from the chain's first sample, row 0 beyond num_records; v3 = the iteration's v0 advance
+    const u32x4 rin = rsrc(src + base, (unsigned)(groups * G * 4)), rout = rsrc(dst + base, (unsigned)(groups * G * 4));
+    const unsigned boff = lane >= 16 ? (unsigned)((63 - lane) * 4) : 0xFFFFF000u;
+    if (BUF) { st = __uint_as_float(lane >= 16 ? 4u * G * 4u : 0u); cnt = 0u - (unsigned)(groups / 4); }
     // prologue: group 0's inputs into the conveyor, group 1's requested; the first step's P and M
     xin = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(src) + off);
     float xin1 = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(src) + off + G * 4);
     float xin2 = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(src) + off + 2 * G * 4);
     X = lane >= 16 ? xin : 0.0f;
+    if (BUF) off = boff;
     // dst is written one group late (the outputs captured at the end of group g are those that entered rows 1 .. 3
     // during it); the host finds the lag
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
@@ -120,8 +162,9 @@ __global__ __launch_bounds__(64) void k(const float *src, float *dst, long long 
 %(asm)s
         : [X] "+{v2}"(X), [st] "+{v3}"(st), [u] "+{v[4:5]}"(u), [b2x] "+{v7}"(b2x), [s] "+{v[10:11]}"(s), [voff] "+{v0}"(off),
           [xin] "+{v16}"(xin1), [xin2] "+{v17}"(xin2), [cnt] "+s"(cnt)
-        : [b2] "{v1}"(b2), [pb01] "{v[12:13]}"(pb01), [a12] "{v[14:15]}"(a12), [src] "s"(src), [dst] "s"(dst), [kg] "s"(kg)
-        : "v6", "v8", "v9", "memory", "scc");
+        : [b2] "{v1}"(b2), [pb01] "{v[12:13]}"(pb01), [a12] "{v[14:15]}"(a12), [src] "s"(src), [dst] "s"(dst), [kg] "s"(kg),
+          [rin] "s"(rin), [rout] "s"(rout)
+        : "v6", "v8", "v9", "vcc", "memory", "scc");
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
     if (lane == 0 && ticks) ticks[blockIdx.x] = t1 - t0;
 }
@@ -151,7 +194,7 @@ int main()
         c.b0[b] = (float)((1.0 + al * A_) / a0); c.b1[b] = (float)(-2.0 * std::cos(w) / a0); c.b2[b] = (float)((1.0 - al * A_) / a0);
         c.a1[b] = (float)(-2.0 * std::cos(w) / a0); c.a2[b] = (float)((1.0 - al / A_) / a0);
     }
-    const int chains = 512, groups = (480256 / G + 2) & ~1;        // an even number of groups (PROTO_AHEAD=2 runs two per iteration)
+    const int chains = 512, groups = BUF ? (480256 / G + 3) & ~3 : (480256 / G + 2) & ~1;  // PROTO_AHEAD=2: two groups per iteration, PROTO_PORT=buffer: four
     const long long n = (long long)groups * G, stride = 2 * (n + 4 * G);
     std::vector<float> hx((size_t)chains * stride, 0.0f);
     unsigned long long sd = 0x0A5EAD00ull;
@@ -203,13 +246,13 @@ int main()
     printf("a lone wave: %%.3f s_memtime ticks per sample\n", (double)tk / (double)n);
     return bad_total ? 2 : 0;
 }
-''' % {"G": G, "asm": asm, "P": P.replace('"', '\\"'), "M": M.replace('"', '\\"'), "n_valu": n_valu}
+''' % {"G": G, "buf": PORT == "buffer", "asm": asm, "P": P.replace('"', '\\"'), "M": M.replace('"', '\\"'), "n_valu": n_valu}
     path = "/tmp/proto_eq_wave_ring.hip"
     open(path, "w").write(src)
     os.makedirs(os.path.join(HERE, "bin"), exist_ok=True)
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-w", "-ffp-contract=off", "--offload-arch=gfx950", "-o",
-                    os.path.join(HERE, "bin", "proto_eq_wave_ring" + ("" if VARIANT == "wave" else "_" + VARIANT) + ("_ahead2" if AHEAD == 2 else "")), path], check=True)
-    print("built tools/bin/proto_eq_wave_ring (variant", VARIANT + ");", n_valu, "VALU per", G, "samples")
+                    os.path.join(HERE, "bin", "proto_eq_wave_ring" + ("" if VARIANT == "wave" else "_" + VARIANT) + ("_ahead2" if AHEAD == 2 else "") + ("_buffer" if PORT == "buffer" else "")), path], check=True)
+    print("built tools/bin/proto_eq_wave_ring (variant", VARIANT + ", port", PORT + ");", n_valu, "VALU per", G, "samples")
 
 
 if __name__ == "__main__":
