@@ -70,10 +70,7 @@ def _units():
         # host-only C++ (RBJ coefficient formulas + the musl restatement of sinf / cosf / powf: every operation rounds
         # by itself)
         ("biquad_coeffs.cpp", ["-x", "hip", "-ffp-contract=off"]),
-    ] + ([
-        # experiments builds only: the block-8192 plan's first form (sixteen waves, pair image) -- parity-green, slower (LABNOTES.md)
-        ("experiments/conv_xb16_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),
-    ] if EXPERIMENTS else [])
+    ]
 
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",

@@ -1,7 +1,8 @@
 // api_conv.hip -- the convolution state of a handle (ConvState: one stream for ohs_engine, S streams for ohs_batch):
-// set_ir (convolution.rs:111-139), the ring of input spectra, and conv_launch, which picks the kernels that serve a call
-// (one partition: k_conv_p1 / k_conv_p1_os; several: the time-parallel kernels, k_conv_tp_old after a per-path set_ir,
-// k_conv_general as the fallback).
+// set_ir (convolution.rs:111-139), the ring of input spectra, and conv_launch.  conv_launch serves a call in three steps:
+// conv_choose_plan picks the kernel family (the whole rule: it reads the state and tuning() only), one runner per family
+// reserves and launches (conv_run_p1, conv_run_os, conv_lb_launch, conv_xb_launch, conv_run_tp, conv_run_sequential), and
+// one epilogue advances what every family shares (block counters, last plan, per-family counts, pending tails).
 #include "api_internal.h"
 
 using namespace ohs;
@@ -9,45 +10,23 @@ using namespace ohs_api;
 
 namespace ohs_api {
 
+// one convolution call: S streams of two channels, n_blocks * 512 frames (strides in floats)
+struct ConvCall {
+    const float *in; long long in_ss, in_cs;
+    float *out; long long out_ss, out_cs;
+    int n_blocks; float gain;
+};
+
+// right before the handle is deleted: the buffers only
 void conv_free(ConvState &c)
 {
-    DeviceWideSection dws;      // (frees / device-wide waits below: no resident kernel may be in their way)
-    for (int p = 0; p < 4; ++p) { if (c.d_H[p]) hipFree(c.d_H[p]); c.d_H[p] = nullptr; }
-    if (c.d_hist) hipFree(c.d_hist);
-    if (c.d_pre) hipFree(c.d_pre);
-    c.d_pre = nullptr; c.pre_cnt = ~0ull; c.pre_n = 0;
-    if (c.d_tails) hipFree(c.d_tails);
-    if (c.d_tails_alt) hipFree(c.d_tails_alt);
-    if (c.d_cd) hipFree(c.d_cd);
-    if (c.d_chunk_tails) hipFree(c.d_chunk_tails);
-    if (c.d_cdm) hipFree(c.d_cdm);
-    if (c.d_W) hipFree(c.d_W);
-    if (c.d_W1) hipFree(c.d_W1);
-    if (c.d_merged) hipFree(c.d_merged);
-    if (c.d_merged_alt) hipFree(c.d_merged_alt);
-    if (c.d_last_in) hipFree(c.d_last_in);
-    if (c.d_irt) hipFree(c.d_irt);
-    if (c.d_cd_os) hipFree(c.d_cd_os);
-    if (c.d_irl) hipFree(c.d_irl);
-    if (c.d_xhist) hipFree(c.d_xhist);
-    if (c.d_xhist_alt) hipFree(c.d_xhist_alt);
-    if (c.d_lb_ring) hipFree(c.d_lb_ring);
-    if (c.d_lb_cd) hipFree(c.d_lb_cd);
-    if (c.d_lb_ab) hipFree(c.d_lb_ab);
-    if (c.d_lb_cd_alt) hipFree(c.d_lb_cd_alt);
-    if (c.d_xb_cd) hipFree(c.d_xb_cd);
-    if (c.d_xb_ab) hipFree(c.d_xb_ab);
-    c.d_xb_cd = nullptr; c.d_xb_ab = nullptr; c.xb_p2 = 0; c.xb_cd_gen = 0;
-    if (c.d_ptail) hipFree(c.d_ptail);
-    if (c.d_ptail_alt) hipFree(c.d_ptail_alt);
-    c.d_lb_cd_alt = nullptr; c.lb_cd_alt_p2pad = 0; c.d_ptail = nullptr; c.d_ptail_alt = nullptr; c.pt_len = 0; c.pt_active = false;
-    c.d_irl = nullptr; c.irl_len = 0; c.d_xhist = nullptr; c.d_xhist_alt = nullptr; c.xh_len = 0; c.xh_valid = 0;
-    c.d_lb_ring = nullptr; c.lb_ring_cap = 0; c.lb_valid = 0; c.d_lb_cd = nullptr; c.d_lb_ab = nullptr; c.lb_p2pad = 0;
-    c.lb_cd_valid = false; c.lb_tables_gen++; c.lb_lazy = false;
-    c.d_irt = nullptr; c.d_cd_os = nullptr; c.cd_os_valid = false;
-    c.d_merged = nullptr; c.d_merged_alt = nullptr; c.d_last_in = nullptr; c.tails_lazy = false; c.lazy_ok = false;
-    c.d_cdm = nullptr; c.d_W = nullptr; c.d_W1 = nullptr;
-    c.d_hist = nullptr; c.d_tails = nullptr; c.d_tails_alt = nullptr; c.d_cd = nullptr; c.d_chunk_tails = nullptr;
+    DeviceWideSection dws;      // (frees below: no resident kernel may be in their way)
+    for (float2 *h : c.d_H) if (h) hipFree(h);
+    for (void *d : std::initializer_list<void *>{c.d_hist, c.d_pre, c.d_tails, c.d_tails_alt, c.d_cd, c.d_chunk_tails, c.d_cdm, c.d_W,
+                                                 c.d_W1, c.d_merged, c.d_merged_alt, c.d_last_in, c.d_irt, c.d_cd_os, c.d_irl,
+                                                 c.d_xhist, c.d_xhist_alt, c.d_lb_ring, c.d_lb_cd, c.d_lb_ab, c.d_lb_cd_alt,
+                                                 c.d_xb_cd, c.d_xb_ab, c.d_ptail, c.d_ptail_alt})
+        if (d) hipFree(d);
 }
 
 int conv_init(ConvState &c, size_t S, hipStream_t st)
@@ -101,9 +80,7 @@ int conv_enable_lazy_state(ConvState &c)
 static int conv_materialise_from_xhist(ConvState &c, DeviceCtx *ctx, hipStream_t st)
 {
     if (!c.lb_lazy) return OHS_OK;
-    int Pmax = 1;
-    for (int p = 0; p < 4; ++p) Pmax = std::max(Pmax, c.P[p]);
-    const long long R = std::min<long long>(std::min<long long>(Pmax, (long long)c.cnt), c.xh_len / BS);
+    const long long R = std::min<long long>(std::min<long long>(conv_max_p(c), (long long)c.cnt), c.xh_len / BS);
     if (R > 0) {
         int rc = conv_grow_ring(c, (int)R, st);
         if (rc) return rc;
@@ -179,6 +156,19 @@ int conv_grow_ring(ConvState &c, int need, hipStream_t st)
     return OHS_OK;
 }
 
+// a buffer whose contents may go, reallocated to `bytes`: the stream drained, the old buffer freed, the new one allocated
+// (null if that fails).  The caller records the new capacity on success only: a failed reserve leaves capacity 0, and the
+// next call tries again.
+template <class T> static int conv_realloc(T *&d, size_t bytes, hipStream_t st)
+{
+    DeviceWideSection dws;      // (frees / device-wide waits below: no resident kernel may be in their way)
+    HIP_TRY(hipStreamSynchronize(st));
+    if (d) hipFree(d);
+    d = nullptr;
+    HIP_TRY(hipMalloc(&d, bytes));
+    return OHS_OK;
+}
+
 // ---- block-2048 plan: the host side of its state (api_internal.h: ConvState) -----------------------------------------
 static long long lb_p2pad_for(int Pmax) { return ((((long long)Pmax + 3) / 4) + 3) / 4 * 4; }    // 2048-tap partitions, multiple of 4
 
@@ -222,8 +212,7 @@ int conv_lb_store_ir(ConvState &c, int path, const float *d_src, const float *h_
 int conv_lb_after_set_ir(ConvState &c, hipStream_t st)
 {
     if (!c.lazy_ok) return OHS_OK;
-    int Pmax = 1;
-    for (int p = 0; p < 4; ++p) Pmax = std::max(Pmax, c.P[p]);
+    const int Pmax = conv_max_p(c);
     const long long want = Pmax >= lb_min_p() ? lb_p2pad_for(Pmax) * kLbBlock : 0;
     if (want != c.xh_len) {
         DeviceWideSection dws;
@@ -254,7 +243,7 @@ int conv_lb_after_set_ir(ConvState &c, hipStream_t st)
         c.lb_valid = 0;         // (the ring's depth follows the partition count)
         c.lb_cd_valid = false; c.lb_tables_gen++;
     }
-    if (c.d_xhist && c.since[0] == 0 && c.since[1] == 0 && c.since[2] == 0 && c.since[3] == 0) {
+    if (c.d_xhist && conv_since_zero(c)) {
         // every path has forgotten its past (convolution.rs:135-137): so has the input history, and zeros are what every path
         // may see of it
         HIP_TRY(hipMemsetAsync(c.d_xhist, 0, c.S * 2 * (size_t)(2 * c.xh_len) * sizeof(float), st));
@@ -291,13 +280,10 @@ static int conv_lb_prepare(ConvState &c, DeviceCtx *ctx, hipStream_t st, ConvLbA
 {
     const int P2pad = (int)(c.xh_len / kLbBlock);
     if (!c.d_lb_cd || c.lb_p2pad != P2pad) {
-        DeviceWideSection dws;
-        HIP_TRY(hipStreamSynchronize(st));
-        if (c.d_lb_cd) hipFree(c.d_lb_cd);
-        if (c.d_lb_ab) hipFree(c.d_lb_ab);
-        c.d_lb_cd = nullptr; c.d_lb_ab = nullptr; c.lb_p2pad = 0; c.lb_cd_valid = false; c.lb_tables_gen++;
-        HIP_TRY(hipMalloc(&c.d_lb_cd, (size_t)P2pad * 2 * kLbBlock * sizeof(float4)));
-        HIP_TRY(hipMalloc(&c.d_lb_ab, (size_t)P2pad * 2 * kLbBlock * sizeof(float4)));
+        c.lb_p2pad = 0; c.lb_cd_valid = false; c.lb_tables_gen++;
+        int rc = conv_realloc(c.d_lb_cd, (size_t)P2pad * 2 * kLbBlock * sizeof(float4), st);
+        if (rc == OHS_OK) rc = conv_realloc(c.d_lb_ab, (size_t)P2pad * 2 * kLbBlock * sizeof(float4), st);
+        if (rc) return rc;
         c.lb_p2pad = P2pad;
     }
     std::memset(&a, 0, sizeof(a));
@@ -324,11 +310,9 @@ static int conv_lb_prepare(ConvState &c, DeviceCtx *ctx, hipStream_t st, ConvLbA
 static int conv_lb_ring_reserve(ConvState &c, int cap_need, hipStream_t st)
 {
     if (cap_need <= c.lb_ring_cap) return OHS_OK;
-    DeviceWideSection dws;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (c.d_lb_ring) hipFree(c.d_lb_ring);
-    c.d_lb_ring = nullptr; c.lb_ring_cap = 0; c.lb_valid = 0;
-    HIP_TRY(hipMalloc(&c.d_lb_ring, c.S * (size_t)cap_need * kLbBlock * sizeof(float4)));
+    c.lb_ring_cap = 0; c.lb_valid = 0;
+    const int rc = conv_realloc(c.d_lb_ring, c.S * (size_t)cap_need * kLbBlock * sizeof(float4), st);
+    if (rc) return rc;
     c.lb_ring_cap = cap_need;
     return OHS_OK;
 }
@@ -345,11 +329,8 @@ static int conv_lb_tail_route(ConvState &c, DeviceCtx *ctx, int path, hipStream_
 {
     *taken = false;
     if (!c.lazy_ok || !c.d_xhist) return OHS_OK;
-    if (c.since[0] == 0 && c.since[1] == 0 && c.since[2] == 0 && c.since[3] == 0) return OHS_OK;     // nothing processed since a full reset
-    bool deep = true;
-    for (int p = 0; p < 4; ++p) deep = deep && c.since[p] >= c.P[p] && c.xh_valid >= (long long)c.P[p] * BS;
-    const bool together = c.since[0] == c.since[1] && c.since[1] == c.since[2] && c.since[2] == c.since[3] && c.xh_valid >= c.xh_len;
-    if (!deep && !together) return OHS_OK;
+    if (conv_since_zero(c)) return OHS_OK;     // nothing processed since a full reset
+    if (!conv_history_covers_paths(c)) return OHS_OK;
     ConvLbArgs a;
     int rc = conv_lb_prepare(c, ctx, st, a);
     if (rc) return rc;
@@ -357,10 +338,9 @@ static int conv_lb_tail_route(ConvState &c, DeviceCtx *ctx, int path, hipStream_
     const long long Lt = c.xh_len;
     DeviceWideSection dws;
     if (c.lb_cd_alt_p2pad != P2pad) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (c.d_lb_cd_alt) hipFree(c.d_lb_cd_alt);
-        c.d_lb_cd_alt = nullptr; c.lb_cd_alt_p2pad = 0;
-        HIP_TRY(hipMalloc(&c.d_lb_cd_alt, (size_t)P2pad * 2 * kLbBlock * sizeof(float4)));
+        c.lb_cd_alt_p2pad = 0;
+        rc = conv_realloc(c.d_lb_cd_alt, (size_t)P2pad * 2 * kLbBlock * sizeof(float4), st);
+        if (rc) return rc;
         c.lb_cd_alt_p2pad = P2pad;
     }
     if (c.pt_len != Lt) {       // (a response of another length since the last tails: rows of the old length are re-cut below)
@@ -420,8 +400,7 @@ static int conv_lb_tail_route(ConvState &c, DeviceCtx *ctx, int path, hipStream_
     return OHS_OK;
 }
 
-static int conv_lb_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out,
-                          long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st)
+static int conv_lb_launch(ConvState &c, DeviceCtx *ctx, const ConvCall &k, hipStream_t st, int &ranges)
 {
     ConvLbArgs a;
     {
@@ -430,16 +409,16 @@ static int conv_lb_launch(ConvState &c, DeviceCtx *ctx, const float *in, long lo
     }
     const int P2pad = a.P2pad;
     const long long SEG = lb_segment_blocks(c.S);
-    const long long frames_total = (long long)n_blocks * BS;
+    const long long frames_total = (long long)k.n_blocks * BS;
     const long long nbig_total = ((long long)c.cnt * BS + frames_total - 1) / kLbBlock - (long long)c.cnt * BS / kLbBlock + 1;
     const int cap_need = (int)(std::min(SEG, (nbig_total + kLbTile - 1) / kLbTile * kLbTile) + P2pad - 1);
     {
         const int rcr = conv_lb_ring_reserve(c, cap_need, st);
         if (rcr) return rcr;
     }
-    a.n_streams = (int)c.S; a.gain = gain; a.cd = c.d_lb_cd;
+    a.n_streams = (int)c.S; a.gain = k.gain; a.cd = c.d_lb_cd;
     a.ring = c.d_lb_ring; a.ring_cap = c.lb_ring_cap;
-    a.in_stream_stride = in_ss; a.in_ch_stride = in_cs; a.out_stream_stride = out_ss; a.out_ch_stride = out_cs;
+    a.in_stream_stride = k.in_ss; a.in_ch_stride = k.in_cs; a.out_stream_stride = k.out_ss; a.out_ch_stride = k.out_cs;
     a.xh_len = c.xh_len;
     // The call's frames on the stream's absolute grid of 2048-frame blocks: [abs0, absE) touches blocks Ba .. Bl.  Segments of
     // at most SEG blocks; the first may start inside a block (its earlier frames come from the input history and its
@@ -455,7 +434,7 @@ static int conv_lb_launch(ConvState &c, DeviceCtx *ctx, const float *in, long lo
         // does the ring hold the complete windows in front of this segment?
         const bool cont = c.lb_end == Bs && c.lb_valid >= P2pad - 1;
         const int warm = cont ? 0 : P2pad - 1;
-        a.in = in + (f_lo - abs0); a.out = out + (f_lo - abs0);
+        a.in = k.in + (f_lo - abs0); a.out = k.out + (f_lo - abs0);
         a.io_frame0 = f_lo - Bs * kLbBlock; a.io_frames = f_hi - f_lo;
         // (the forward kernel appends the segment's last frames to the input history itself -- before the inverse kernel may
         // overwrite them in place --, into the half of the ring its windows do not read)
@@ -476,7 +455,7 @@ static int conv_lb_launch(ConvState &c, DeviceCtx *ctx, const float *in, long lo
     }
     c.xh_valid = std::min(c.xh_len, c.xh_valid + frames_total);
     c.lb_lazy = true;
-    c.last_kernel = OHS_CONV_KERNEL_BLOCK2048; c.last_ranges = tiles_last;
+    ranges = tiles_last;
     return OHS_OK;
 }
 
@@ -491,31 +470,15 @@ bool conv_plan_auto_is_xb(size_t S, long long n_blocks, int Pmax)
     return P2x <= 2 && Pmax >= tn.xb_min_p && n_blocks >= tn.xb_min_blocks && (P2x == 1 || (long long)S >= tn.xb_min_streams_p2);
 }
 
-static int conv_xb_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out,
-                          long long out_ss, long long out_cs, int n_blocks, int P2, float gain, hipStream_t st)
+static int conv_xb_launch(ConvState &c, DeviceCtx *ctx, const ConvCall &k, int P2, hipStream_t st, int &ranges)
 {
-#ifdef OHS_EXPERIMENTS
-    const int form = tuning().xb_form == 1 ? 1 : 2;     // (1: the sixteen-wave first form, experiments/conv_xb16_kernels.hip)
-#else
-    constexpr int form = 2;
-#endif
-    if (c.xb_form != form) { c.xb_cd_gen = 0; c.xb_form = form; }
     if (c.xb_p2 != P2 || !c.d_xb_cd) {
-        DeviceWideSection dws;
-        HIP_TRY(hipStreamSynchronize(st));
-        if (c.d_xb_cd) hipFree(c.d_xb_cd);
-        if (c.d_xb_ab) hipFree(c.d_xb_ab);
-        c.d_xb_cd = nullptr; c.d_xb_ab = nullptr; c.xb_p2 = 0; c.xb_cd_gen = 0;
-        HIP_TRY(hipMalloc(&c.d_xb_cd, (size_t)P2 * 2 * kXbBlock * sizeof(float4)));
-        HIP_TRY(hipMalloc(&c.d_xb_ab, (size_t)2 * P2 * kXbBlock * sizeof(float4)));
+        c.xb_p2 = 0; c.xb_cd_gen = 0;
+        int rc = conv_realloc(c.d_xb_cd, (size_t)P2 * 2 * kXbBlock * sizeof(float4), st);
+        if (rc == OHS_OK) rc = conv_realloc(c.d_xb_ab, (size_t)2 * P2 * kXbBlock * sizeof(float4), st);
+        if (rc) return rc;
         c.xb_p2 = P2;
     }
-    auto launch = [&](const ConvXbArgs &x) -> hipError_t {
-#ifdef OHS_EXPERIMENTS
-        if (form == 1) return launch_conv_xb16(x, st);
-#endif
-        return launch_conv_xb(x, st);
-    };
     ConvXbArgs a;
     std::memset(&a, 0, sizeof(a));
     a.tw = ctx->d_tw; a.tw16384 = ctx->d_tw16384; a.P2 = P2;
@@ -525,42 +488,32 @@ static int conv_xb_launch(ConvState &c, DeviceCtx *ctx, const float *in, long lo
         t.in = c.d_irl; t.in_stream_stride = 2 * c.irl_len; t.in_ch_stride = c.irl_len; t.io_frames = c.irl_len;
         t.n_streams = 2; t.n_blk = P2; t.run = 1; t.ab = c.d_xb_ab; t.tables_mode = 1;
         t.fp_mode = 0;      // (tables are built in IEEE arithmetic, like k_ir_spectrum's)
-        hipError_t e = launch(t);
-#ifdef OHS_EXPERIMENTS
-        if (e == hipSuccess && form == 1) e = launch_conv_xb16_build_cd(c.d_xb_ab, P2, c.d_xb_cd, st);
-        else
-#endif
+        hipError_t e = launch_conv_xb(t, st);
         if (e == hipSuccess) e = launch_conv_xb_build_cd(reinterpret_cast<const float2 *>(c.d_xb_ab), P2, c.d_xb_cd, st);
         if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("block-8192 tables: ") + hipGetErrorString(e));
         c.xb_cd_gen = c.lb_tables_gen;
     }
-    const long long frames = (long long)n_blocks * BS;
-    a.in = in; a.out = out;
-    a.in_stream_stride = in_ss; a.in_ch_stride = in_cs; a.out_stream_stride = out_ss; a.out_ch_stride = out_cs;
+    const long long frames = (long long)k.n_blocks * BS;
+    a.in = k.in; a.out = k.out;
+    a.in_stream_stride = k.in_ss; a.in_ch_stride = k.in_cs; a.out_stream_stride = k.out_ss; a.out_ch_stride = k.out_cs;
     a.xhist = c.d_xhist; a.xh_len = c.xh_len; a.xh_head = c.xh_head;
     a.io_frames = frames; a.n_streams = (int)c.S; a.n_blk = (int)((frames + kXbBlock - 1) / kXbBlock);
     a.run = conv_xb_run_for(a.n_streams, a.n_blk, P2, ctx->num_cus);
-    a.cd = c.d_xb_cd; a.gain = gain; a.fp_mode = c.fp_mode; a.stagger = tuning().xb_stagger;
+    a.cd = c.d_xb_cd; a.gain = k.gain; a.fp_mode = c.fp_mode; a.stagger = tuning().xb_stagger;
     // the call's last frames join the input history: appended by the kernel itself, into the half of the ring it does not read
     const long long xcnt = std::min(frames, c.xh_len);
-    bool own_append = form == 2;
-#ifdef OHS_EXPERIMENTS
-    if (tuning().xb_append_launch) own_append = false;     // (A/B: the append as a launch of its own behind the kernel)
-#endif
-    if (own_append) { a.xh_append = c.d_xhist; a.xh_cnt = xcnt; }
+    a.xh_append = c.d_xhist; a.xh_cnt = xcnt;
 #ifdef OHS_EXPERIMENTS
     if (tuning().xb_run > 0) a.run = std::min(tuning().xb_run, a.n_blk);
     a.debug_skip = tuning().xb_skip;
 #endif
-    hipError_t e = launch(a);
-    if (e == hipSuccess && !own_append)     // (the first form does not append: a launch behind it)
-        e = launch_conv_lb_xhist_append(in, in_ss, in_cs, c.d_xhist, c.xh_len, c.xh_head, frames, (int)c.S, st);
+    hipError_t e = launch_conv_xb(a, st);
     if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("block-8192 launch: ") + hipGetErrorString(e));
     c.xh_head = (c.xh_head + xcnt) % (2 * c.xh_len);
     c.xh_valid = std::min(c.xh_len, c.xh_valid + frames);
     c.lb_valid = 0;             // (the block-2048 window ring has not seen these blocks)
     c.lb_lazy = true;
-    c.last_kernel = OHS_CONV_KERNEL_BLOCK8192; c.last_ranges = (a.n_blk + a.run - 1) / a.run;
+    ranges = (a.n_blk + a.run - 1) / a.run;
     return OHS_OK;
 }
 
@@ -583,9 +536,7 @@ int conv_set_ir(ConvState &c, DeviceCtx *ctx, int path, const float *ir, size_t 
         int Pmax_after = P;
         for (int p = 0; p < 4; ++p)
             if (p != path) Pmax_after = std::max(Pmax_after, c.P[p]);
-        bool all_one = true;
-        for (int p = 0; p < 4; ++p) all_one = all_one && c.P[p] == 1;
-        if (all_one && Pmax_after >= lb_min_p()) {
+        if (conv_max_p(c) == 1 && Pmax_after >= lb_min_p()) {
             const long long want = lb_p2pad_for(Pmax_after) * kLbBlock;
             const size_t bytes = c.S * 2 * (size_t)want * sizeof(float);
             float *n = nullptr, *n2 = nullptr;
@@ -662,7 +613,7 @@ int conv_set_ir(ConvState &c, DeviceCtx *ctx, int path, const float *ir, size_t 
     c.cd_valid = false;
     c.cdm_valid = false;
     c.since[path] = 0;      // :135-137 that path's history is "all zero" again
-    if (c.since[0] == 0 && c.since[1] == 0 && c.since[2] == 0 && c.since[3] == 0) {
+    if (conv_since_zero(c)) {
         // every path has forgotten its past: the ring holds nothing any path may still see.  Zeroing
         // it lets the gate-free time-parallel kernels run right away (all `since` equal).
         HIP_TRY(hipMemsetAsync(c.d_hist, 0, c.S * (size_t)c.cap * NF * sizeof(float2), st));
@@ -763,17 +714,340 @@ int conv_os_chunks(const DeviceCtx *ctx, size_t S, long long n_blocks, bool in_p
     return K;
 }
 
-static int conv_launch_impl(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
-                            float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st,
-                            bool allow_fast, hipEvent_t ev_start, hipEvent_t ev_stop);
+// What conv_choose_plan decides for a call: the kernel family, and what is decided along with it
+struct ConvPlan {
+    int kernel = OHS_CONV_KERNEL_NONE;  // OHS_CONV_KERNEL_*
+    int K = 0;                  // one partition: time chunks (block 512) or hop ranges (hop 1536) per stream
+    int xcd_lo = 0, xcd_n = 8;  // block 512, one partition: the XCDs its launches may use
+    int P2x = 0;                // block 8192: partitions of 8192 taps
+    bool gated = false;         // time-parallel block 512: after a per-path set_ir (k_conv_tp_old)
+    long long SEG = 0;          // time-parallel block 512: blocks per segment
+};
+
+// The plan rule: which kernel family serves the call `k`.  It reads the state and tuning() only.
+static ConvPlan conv_choose_plan(const ConvState &c, const DeviceCtx *ctx, const ConvCall &k, bool allow_fast)
+{
+    const Tuning &tn = tuning();
+    const int Pmax = conv_max_p(c);
+    ConvPlan plan;
+    if (Pmax == 1 && allow_fast) {
+        // every path has one partition: time-parallel single-FFT-pair kernel
+        // Two plans for this case (ohs_batch_set_conv_plan): block 512 / FFT 1024 overlap-add (k_conv_p1: the plan whose
+        // output bits tests/golden/p1_output_sha256.txt holds) and hop 1536 / FFT 2048 overlap-save (k_conv_p1_os: a third
+        // less transform and product work per frame; batch objects only -- it hands the lazy state over).
+        const bool os_ok = c.lazy_ok && c.d_irt && k.n_blocks >= 3 && c.xcd_n == 8 && tn.p1_xcd_n == 0 &&
+                           ((k.in_ss | k.in_cs | k.out_ss | k.out_cs) & 1) == 0 &&
+                           ((reinterpret_cast<uintptr_t>(k.in) | reinterpret_cast<uintptr_t>(k.out)) & 7) == 0 &&
+                           (unsigned long long)k.n_blocks * BS + 1536ull < (1ull << 31);
+        if (os_ok && (c.conv_plan == 2 || (c.conv_plan == 0 && conv_plan_auto_is_os(c.S, k.n_blocks, k.in == k.out)))) {
+            plan.kernel = OHS_CONV_KERNEL_HOP1536_P1;
+            plan.K = conv_os_chunks(ctx, c.S, k.n_blocks, k.in == k.out);
+            return plan;
+        }
+        plan.kernel = OHS_CONV_KERNEL_BLOCK512_P1;
+        plan.xcd_lo = c.xcd_lo; plan.xcd_n = c.xcd_n;
+        if (tn.p1_xcd_n > 0) { plan.xcd_lo = tn.p1_xcd_lo; plan.xcd_n = tn.p1_xcd_n; }
+        plan.K = (int)conv_p1_chunks(ctx, c.S, k.n_blocks, tn.p1_target_waves, plan.xcd_n);
+        return plan;
+    }
+    if (allow_fast && c.d_xhist && Pmax >= lb_min_p()) {
+        // Block 2048 / FFT 4096 (conv_lb_kernels.hip).  It convolves the input history itself, so every path must be
+        // allowed to see all of its own response's reach of it (conv_history_covers_paths).
+        const bool lb_ok = conv_history_covers_paths(c) && ((k.in_ss | k.in_cs | k.out_ss | k.out_cs) & 3) == 0 &&
+                           ((reinterpret_cast<uintptr_t>(k.in) | reinterpret_cast<uintptr_t>(k.out)) & 15) == 0;
+        if (lb_ok && (c.conv_plan == 2 || (c.conv_plan == 0 && conv_plan_auto_is_lb(c.S, k.n_blocks, Pmax)))) {
+            // Long out-of-place calls on responses of at most two 8192-tap partitions: block 8192 / FFT 16384, one kernel (the
+            // buffers must not overlap at all: a run's first windows read frames in front of its own blocks).  Where it pays
+            // (profiles/r05_xb_vs_lb_shapes.txt): calls of 128 blocks or more; with two partitions, on 32 streams or more.
+            const int P2x = (Pmax + 15) / 16;
+            const long long call_frames = (long long)k.n_blocks * BS;
+            const float *in_end = k.in + (c.S - 1) * k.in_ss + k.in_cs + call_frames;
+            const float *out_end = k.out + (c.S - 1) * k.out_ss + k.out_cs + call_frames;
+            const bool apart = in_end <= k.out || out_end <= k.in;
+            const bool xb = apart && conv_plan_auto_is_xb(c.S, k.n_blocks, Pmax) &&
+                            c.xh_len >= (long long)P2x * kXbBlock && call_frames < (1ll << 29);
+            plan.kernel = xb ? OHS_CONV_KERNEL_BLOCK8192 : OHS_CONV_KERNEL_BLOCK2048;
+            plan.P2x = P2x;
+            return plan;
+        }
+    }
+    bool since_old = true;
+    for (int p = 0; p < 4; ++p) since_old = since_old && c.since[p] >= c.P[p] - 1;
+    // gate-free condition of the time-parallel kernels: no path may have blocks in the ring that
+    // it must not see (either every path is older than its own IR -- path p reads P[p] - 1 blocks back --, or all
+    // were reset together: conv_set_ir zeroed the ring then)
+    const bool gate_free = since_old || conv_since_equal(c);
+    // Otherwise -- a per-path set_ir in mid-stream -- the same three kernels run on a ring whose old blocks they
+    // cannot reach (the call starts Ppad - 1 zeroed slots further on) and k_conv_tp_old adds what each path may
+    // still see of them to the first Pmax - 1 blocks.  The first segment must reach beyond every old block
+    // (n_blocks >= Pmax): the state it leaves behind is computed gate-free.  Shorter calls take the general kernel
+    // (one wave per stream, blocks in sequence: 290 x slower on BASELINE config 4, which is why long calls do not).
+    // (calls of 1 .. 3 blocks too: until round 5 they went through the sequential kernel -- one wave per stream, 93 us per
+    // block on BASELINE config 4's shape, whatever the number of streams: profiles/r05_short_calls_before.jsonl)
+    plan.gated = allow_fast && !gate_free && k.n_blocks >= Pmax;
+    if (!allow_fast || !(gate_free || plan.gated)) {
+        plan.kernel = OHS_CONV_KERNEL_SEQUENTIAL;
+        return plan;
+    }
+    plan.kernel = OHS_CONV_KERNEL_BLOCK512_TP;
+    // segment size: keep the MAC scratch around 128 MiB
+    plan.SEG = std::max<long long>(8, std::min<long long>(16384 / (long long)c.S, 1024));
+    if (plan.gated) plan.SEG = std::max<long long>(plan.SEG, Pmax);
+    return plan;
+}
+
+// the (C, D) tables of k_conv_p1, kept current ahead of either one-partition plan
+static int conv_p1_build_cd(ConvState &c, hipStream_t st)
+{
+    if (c.cd_valid) return OHS_OK;
+    hipError_t e = launch_build_cd(c.d_H[0], c.d_H[1], c.d_H[2], c.d_H[3], c.d_cd, st);
+    if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("build_cd: ") + hipGetErrorString(e));
+    c.cd_valid = true;
+    return OHS_OK;
+}
+
+// block 512 / FFT 1024, one partition (k_conv_p1); the events ride in its dispatch
+static int conv_run_p1(ConvState &c, DeviceCtx *ctx, const ConvCall &k, const ConvPlan &plan, hipStream_t st,
+                       hipEvent_t ev_start, hipEvent_t ev_stop, int &ranges)
+{
+    int rc = conv_p1_build_cd(c, st);
+    if (rc) return rc;
+    const Tuning &tn = tuning();
+    const int K = plan.K;
+    if ((size_t)K > c.chunk_tails_cap) {
+        c.chunk_tails_cap = 0;
+        rc = conv_realloc(c.d_chunk_tails, c.S * (size_t)K * 512 * sizeof(float2), st);
+        if (rc) return rc;
+        c.chunk_tails_cap = (size_t)K;
+    }
+    ConvP1Args a;
+    a.in = k.in; a.out = k.out;
+    a.in_stream_stride = k.in_ss; a.in_ch_stride = k.in_cs;
+    a.out_stream_stride = k.out_ss; a.out_ch_stride = k.out_cs;
+    a.n_blocks = k.n_blocks; a.n_streams = (int)c.S; a.chunks = K;
+    a.CD = c.d_cd;
+    for (int p = 0; p < 4; ++p) a.H[p] = c.d_H[p];
+    a.tails = c.d_tails; a.tails_out = c.d_tails_alt; a.chunk_tails = c.d_chunk_tails;
+    a.merged_in = c.tails_lazy ? c.d_merged : nullptr;
+    a.merged_out = c.lazy_ok ? c.d_merged_alt : nullptr;
+    a.last_in = c.lazy_ok ? c.d_last_in : nullptr;
+    a.tw = ctx->d_tw; a.gain = k.gain; a.fp_mode = c.fp_mode;
+    a.xcd_lo = plan.xcd_lo; a.xcd_n = plan.xcd_n;
+    {   // boundary tails by the chunks' own waves where a stream's chunks share a workgroup (else: the pre-pass)
+        const bool allowed = conv_p1_waves_per_cu() == 16 && (K == 2 || K == 4 || K == 8 || K == 16);
+        a.own_tails = (allowed && tn.p1_own_tails) ? 1 : 0;
+    }
+    a.stagger = tn.p1_stagger;
+    a.prio_mode = tn.p1_prio;
+    // Chunk lengths by the age rank of the wave that runs a chunk (p1_chunk_begin), equal lengths when chunks are
+    // short.  In the plans that do not spread a stream's chunks over the ranks, ALL of a stream's chunks can sit on
+    // heavy ranks: its shortest chunk is then n * wmin / (K * wmax) blocks, and that one must keep >= 2 blocks (a
+    // chunk of zero blocks would make the boundary-tail code index block b0 - 1 = -1).
+    const int *kw = tn.p1_weights;
+    const int wmin = std::min(std::min(kw[0], kw[1]), std::min(kw[2], kw[3]));
+    const int wmax = std::max(std::max(kw[0], kw[1]), std::max(kw[2], kw[3]));
+    const bool weighted = (long long)k.n_blocks * wmin >= 2ll * K * wmax;
+    for (int g = 0; g < 4; ++g) a.weights[g] = weighted ? kw[g] : 1;
+    hipError_t e = launch_conv_p1(a, st, ev_start, ev_stop);
+    if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1 launch: ") + hipGetErrorString(e));
+    if (c.lazy_ok) {
+        std::swap(c.d_merged, c.d_merged_alt);
+        c.tails_lazy = true;
+    } else {
+        std::swap(c.d_tails, c.d_tails_alt);
+    }
+    ranges = K;
+    return OHS_OK;
+}
+
+// hop 1536 / FFT 2048, one partition (k_conv_p1_os); the events ride in its dispatch
+static int conv_run_os(ConvState &c, DeviceCtx *ctx, const ConvCall &k, int K, hipStream_t st, hipEvent_t ev_start,
+                       hipEvent_t ev_stop, int &ranges)
+{
+    const int rc = conv_p1_build_cd(c, st);
+    if (rc) return rc;
+    if (!c.cd_os_valid) {
+        hipError_t e = launch_os_tables(c.d_irt, ctx->d_tw, ctx->d_tw2048, c.d_cd_os, st);
+        if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("os tables: ") + hipGetErrorString(e));
+        c.cd_os_valid = true;
+    }
+    ConvOsArgs o;
+    o.in = k.in; o.out = k.out;
+    o.in_stream_stride = k.in_ss; o.in_ch_stride = k.in_cs; o.out_stream_stride = k.out_ss; o.out_ch_stride = k.out_cs;
+    o.n_blocks = k.n_blocks; o.n_streams = (int)c.S; o.chunks = K;
+    o.CD = c.d_cd_os; o.tw2048 = ctx->d_tw2048;
+    o.tails = c.d_tails; o.merged_in = c.tails_lazy ? c.d_merged : nullptr;
+    o.merged_out = c.d_merged_alt; o.last_in = c.d_last_in;
+    o.tw = ctx->d_tw; o.gain = k.gain; o.fp_mode = c.fp_mode;
+    hipError_t e = launch_conv_p1_os(o, st, ev_start, ev_stop);
+    if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_os launch: ") + hipGetErrorString(e));
+    std::swap(c.d_merged, c.d_merged_alt);
+    c.tails_lazy = true;
+    ranges = K;
+    return OHS_OK;
+}
+
+// The call's frames join the input history of the block-2048 plan (what it starts from when a later call takes it): the
+// time-parallel forward kernel appends them itself, the sequential kernel's calls get a launch for it (`append`) -- in front
+// of anything that overwrites them in place.  Then the history's head moves past the call.
+static int conv_xh_follow(ConvState &c, const ConvCall &k, bool append, hipStream_t st)
+{
+    if (!c.d_xhist) return OHS_OK;
+    const long long frames = (long long)k.n_blocks * BS;
+    if (append) {
+        if (((k.in_ss | k.in_cs) & 3) != 0 || (reinterpret_cast<uintptr_t>(k.in) & 15) != 0) {
+            c.xh_valid = 0;     // (buffers the 16-byte copy cannot read: the history no longer follows the stream)
+            return OHS_OK;
+        }
+        hipError_t e = launch_conv_lb_xhist_append(k.in, k.in_ss, k.in_cs, c.d_xhist, c.xh_len, c.xh_head, frames, (int)c.S, st);
+        if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("input history update: ") + hipGetErrorString(e));
+    }
+    c.xh_head = (c.xh_head + std::min(frames, c.xh_len)) % (2 * c.xh_len);
+    c.xh_valid = std::min(c.xh_len, c.xh_valid + frames);
+    return OHS_OK;
+}
+
+// block 512, several partitions, one wave per stream and the blocks in sequence (k_conv_general)
+static int conv_run_sequential(ConvState &c, DeviceCtx *ctx, const ConvCall &k, hipStream_t st, int &ranges)
+{
+    int rc = conv_materialise_state(c, ctx, st);        // (this kernel reads and writes the per-path overlaps)
+    if (rc) return rc;
+    c.lb_valid = 0;         // (the block-2048 ring does not see the blocks of this call)
+    rc = conv_xh_follow(c, k, true, st);
+    if (rc) return rc;
+    ConvGeneralArgs a;
+    a.in = k.in; a.out = k.out;
+    a.in_stream_stride = k.in_ss; a.in_ch_stride = k.in_cs;
+    a.out_stream_stride = k.out_ss; a.out_ch_stride = k.out_cs;
+    a.n_blocks = k.n_blocks;
+    for (int p = 0; p < 4; ++p) { a.H[p] = c.d_H[p]; a.P[p] = c.P[p]; a.since[p] = c.since[p]; }
+    a.hist = c.d_hist; a.cap = c.cap; a.cnt = c.cnt;
+    a.tails = c.d_tails; a.tails_out = c.d_tails;
+    a.skip_store = 0; a.zero_tails_in = 0;
+    a.tw = ctx->d_tw; a.gain = k.gain; a.fp_mode = c.fp_mode;
+    hipError_t e = launch_conv_general(a, (int)c.S, st);
+    if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv launch: ") + hipGetErrorString(e));
+    ranges = 1;
+    return OHS_OK;
+}
+
+// block 512, several partitions, time-parallel: k_conv_tp_forward / _mac / _inverse per segment of plan.SEG blocks; gated
+// (after a per-path set_ir) behind a zeroed gap in the ring, with k_conv_tp_old in the first segment
+static int conv_run_tp(ConvState &c, DeviceCtx *ctx, const ConvCall &k, const ConvPlan &plan, hipStream_t st, int &ranges)
+{
+    int rc = conv_materialise_state(c, ctx, st);        // (these kernels read and write the per-path overlaps)
+    if (rc) return rc;
+    c.lb_valid = 0;         // (the block-2048 ring does not see the blocks of this call)
+    const int Pmax = conv_max_p(c);
+    const long long seg_max = std::min<long long>(plan.SEG, k.n_blocks);
+    const int Ppad = Ppad_for_ring(Pmax);
+    // (gated: old blocks + the zeroed gap + the segment live in the ring together)
+    rc = conv_grow_ring(c, (int)(seg_max + (plan.gated ? 2 : 1) * (Ppad - 1) + (plan.gated ? Pmax : 0)), st);
+    if (rc) return rc;
+    const unsigned long long cnt_old = c.cnt;
+    if (plan.gated) {
+        // the zeroed gap: ring slots cnt .. cnt + Ppad - 2 of every stream (two strided memsets when it wraps)
+        const unsigned long long gap = (unsigned long long)(Ppad - 1), cap = (unsigned long long)c.cap;
+        const unsigned long long s0 = c.cnt & (cap - 1), n0 = std::min(gap, cap - s0);
+        const size_t pitch = (size_t)c.cap * NF * sizeof(float2);
+        HIP_TRY(hipMemset2DAsync(c.d_hist + s0 * NF, pitch, 0, (size_t)n0 * NF * sizeof(float2), c.S, st));
+        if (n0 < gap)
+            HIP_TRY(hipMemset2DAsync(c.d_hist, pitch, 0, (size_t)(gap - n0) * NF * sizeof(float2), c.S, st));
+        c.cnt += gap;
+    }
+    if (!c.d_cdm || c.cdm_ppad != Ppad) {       // (a set_ir that keeps Ppad re-uses the buffer: no wait, no malloc)
+        c.cdm_valid = false;
+        rc = conv_realloc(c.d_cdm, (size_t)Ppad * 2 * NF * sizeof(float2), st);
+        if (rc) return rc;
+        c.cdm_ppad = Ppad;
+    }
+    if (!c.cdm_valid) {
+        hipError_t e = launch_build_cd_multi(c.d_H[0], c.d_H[1], c.d_H[2], c.d_H[3], c.P[0], c.P[1],
+                                             c.P[2], c.P[3], Ppad, c.d_cdm, st);
+        if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("build_cd_multi: ") + hipGetErrorString(e));
+        c.cdm_ppad = Ppad; c.cdm_valid = true;
+    }
+    if ((size_t)seg_max > c.w_blocks) {
+        c.w_blocks = 0;
+        rc = conv_realloc(c.d_W, c.S * (size_t)seg_max * NF * sizeof(float2), st);
+        if (rc) return rc;
+        c.w_blocks = (size_t)seg_max;
+    }
+    if (!c.d_W1) HIP_TRY(hipMalloc(&c.d_W1, c.S * (size_t)NF * sizeof(float2)));
+    const long long call_frames = (long long)k.n_blocks * BS;
+    const long long xh_cnt = c.d_xhist ? std::min(call_frames, c.xh_len) : 0;
+    long long done = 0;
+    while (done < k.n_blocks) {
+        const int seg = (int)std::min<long long>(plan.SEG, k.n_blocks - done);
+        ConvTpArgs a;
+        a.in = k.in + done * BS; a.out = k.out + done * BS;
+        a.in_stream_stride = k.in_ss; a.in_ch_stride = k.in_cs;
+        a.out_stream_stride = k.out_ss; a.out_ch_stride = k.out_cs;
+        a.n_streams = (int)c.S; a.seg_blocks = seg; a.n_mac = seg; a.Ppad = Ppad;
+        a.CD = c.d_cdm; a.hist = c.d_hist; a.cap = c.cap; a.cnt = c.cnt + (unsigned long long)done;
+        a.W = c.d_W; a.W1 = c.d_W1; a.tails = c.d_tails; a.tails_out = c.d_tails_alt;
+        a.pairs = ctx->d_pairs; a.n_pairs = ctx->n_pairs;
+        a.tw = ctx->d_tw; a.gain = k.gain; a.fp_mode = c.fp_mode;
+        // (frame i of the segment is frame done * 512 + i of the call; the call's last xh_cnt frames are appended)
+        a.xh_ring = c.d_xhist; a.xh_len = c.xh_len; a.xh_head = c.xh_head;
+        a.xh_frame0 = done * BS - (call_frames - xh_cnt);
+        hipError_t e = launch_conv_tp_forward(a, st);
+        if (e == hipSuccess) e = launch_conv_tp_mac(a, st);
+        if (e == hipSuccess && plan.gated && done == 0 && Pmax > 1) {
+            ConvTpOldArgs o;
+            o.n_streams = (int)c.S; o.n_old = Pmax - 1; o.Pmax = Pmax;
+            for (int p = 0; p < 4; ++p) { o.H[p] = c.d_H[p]; o.P[p] = c.P[p]; o.since[p] = c.since[p]; }
+            o.hist = c.d_hist; o.cap = c.cap; o.cnt_old = cnt_old;
+            o.W = c.d_W; o.n_mac = seg; o.fp_mode = c.fp_mode;
+            e = launch_conv_tp_old(o, st);
+        }
+        if (e == hipSuccess) e = launch_conv_tp_inverse(a, st);   // block 0 reads the OLD state; new state -> the other slab
+        if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_tp: ") + hipGetErrorString(e));
+        std::swap(c.d_tails, c.d_tails_alt);
+        done += seg;
+        ranges = seg;
+    }
+    return conv_xh_follow(c, k, false, st);
+}
 
 int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
                 float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st,
                 bool allow_fast, hipEvent_t ev_start, hipEvent_t ev_stop)
 {
-    const int rc = conv_launch_impl(c, ctx, in, in_ss, in_cs, out, out_ss, out_cs, n_blocks, gain, st, allow_fast, ev_start, ev_stop);
-    if (rc == OHS_OK && n_blocks > 0 && c.last_kernel >= 0 && c.last_kernel < 8) c.kernel_calls[c.last_kernel]++;
-    if (rc == OHS_OK && n_blocks > 0 && c.pt_active) {
+    // (ev_start / ev_stop: recorded at the start / completion of the call's launches)
+    if (n_blocks <= 0) {                    // nothing to do (the pre-pass would index block -1)
+        if (ev_start) HIP_TRY(hipEventRecord(ev_start, st));
+        if (ev_stop) HIP_TRY(hipEventRecord(ev_stop, st));
+        return OHS_OK;
+    }
+    const ConvCall k{in, in_ss, in_cs, out, out_ss, out_cs, n_blocks, gain};
+    const ConvPlan plan = conv_choose_plan(c, ctx, k, allow_fast);
+    int ranges = 0, rc;
+    if (plan.kernel == OHS_CONV_KERNEL_BLOCK512_P1) {
+        rc = conv_run_p1(c, ctx, k, plan, st, ev_start, ev_stop, ranges);
+    } else if (plan.kernel == OHS_CONV_KERNEL_HOP1536_P1) {
+        rc = conv_run_os(c, ctx, k, plan.K, st, ev_start, ev_stop, ranges);
+    } else {
+        struct EvScope {    // the plans that do not carry the events in a dispatch: recorded around their launches
+            hipStream_t st; hipEvent_t stop;
+            ~EvScope() { if (stop) hipEventRecord(stop, st); }
+        };
+        if (ev_start) HIP_TRY(hipEventRecord(ev_start, st));
+        const EvScope ev_scope{st, ev_stop};
+        switch (plan.kernel) {
+        case OHS_CONV_KERNEL_BLOCK2048: rc = conv_lb_launch(c, ctx, k, st, ranges); break;
+        case OHS_CONV_KERNEL_BLOCK8192: rc = conv_xb_launch(c, ctx, k, plan.P2x, st, ranges); break;
+        case OHS_CONV_KERNEL_BLOCK512_TP: rc = conv_run_tp(c, ctx, k, plan, st, ranges); break;
+        default: rc = conv_run_sequential(c, ctx, k, st, ranges); break;
+        }
+    }
+    if (rc) return rc;
+    // the epilogue of every plan
+    c.cnt += (unsigned long long)n_blocks;
+    for (int p = 0; p < 4; ++p) c.since[p] += n_blocks;
+    c.last_kernel = plan.kernel; c.last_ranges = ranges;
+    c.kernel_calls[plan.kernel]++;
+    if (c.pt_active) {
         // what the frames in front of a per-path set_ir still owe these frames (conv_lb_tail_route)
         const long long n = (long long)n_blocks * BS;
         hipError_t e = launch_conv_lb_tails_add(out, out_ss, out_cs, n, c.d_ptail, c.pt_len, c.pt_pos, gain, (int)c.S, st);
@@ -781,293 +1055,6 @@ int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, 
         c.pt_pos += n;
         if (c.pt_pos >= c.pt_len) c.pt_active = false;
     }
-    return rc;
-}
-
-static int conv_launch_impl(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
-                            float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st,
-                            bool allow_fast, hipEvent_t ev_start, hipEvent_t ev_stop)
-{
-    // (ev_start / ev_stop: recorded at the start / completion of the call's launches)
-    struct EvScope {        // the paths that do not carry the events in a dispatch: recorded around their launches
-        hipStream_t st; hipEvent_t stop; bool armed;
-        ~EvScope() { if (armed && stop) hipEventRecord(stop, st); }
-    } ev_scope{st, ev_stop, false};
-    if (n_blocks <= 0) {                    // nothing to do (the pre-pass would index block -1)
-        if (ev_start) HIP_TRY(hipEventRecord(ev_start, st));
-        if (ev_stop) HIP_TRY(hipEventRecord(ev_stop, st));
-        return OHS_OK;
-    }
-    const bool p1 = c.P[0] == 1 && c.P[1] == 1 && c.P[2] == 1 && c.P[3] == 1;
-    if (p1 && allow_fast) {
-        // every path has one partition: time-parallel single-FFT-pair kernel
-        if (!c.cd_valid) {
-            hipError_t e = launch_build_cd(c.d_H[0], c.d_H[1], c.d_H[2], c.d_H[3], c.d_cd, st);
-            if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("build_cd: ") + hipGetErrorString(e));
-            c.cd_valid = true;
-        }
-        const Tuning &tn = tuning();
-        // Two plans for this case (ohs_batch_set_conv_plan): block 512 / FFT 1024 overlap-add (k_conv_p1: the plan whose
-        // output bits tests/golden/p1_output_sha256.txt holds) and hop 1536 / FFT 2048 overlap-save (k_conv_p1_os: a third
-        // less transform and product work per frame; batch objects only -- it hands the lazy state over).
-        const bool os_ok = c.lazy_ok && c.d_irt && n_blocks >= 3 && c.xcd_n == 8 && tn.p1_xcd_n == 0 &&
-                           ((in_ss | in_cs | out_ss | out_cs) & 1) == 0 &&
-                           ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 7) == 0 &&
-                           (unsigned long long)n_blocks * BS + 1536ull < (1ull << 31);
-        const bool use_os = os_ok && (c.conv_plan == 2 || (c.conv_plan == 0 && conv_plan_auto_is_os(c.S, n_blocks, in == out)));
-        if (use_os) {
-            if (!c.cd_os_valid) {
-                hipError_t e = launch_os_tables(c.d_irt, ctx->d_tw, ctx->d_tw2048, c.d_cd_os, st);
-                if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("os tables: ") + hipGetErrorString(e));
-                c.cd_os_valid = true;
-            }
-            const int K = conv_os_chunks(ctx, c.S, n_blocks, in == out);
-            ConvOsArgs o;
-            o.in = in; o.out = out;
-            o.in_stream_stride = in_ss; o.in_ch_stride = in_cs; o.out_stream_stride = out_ss; o.out_ch_stride = out_cs;
-            o.n_blocks = n_blocks; o.n_streams = (int)c.S; o.chunks = K;
-            o.CD = c.d_cd_os; o.tw2048 = ctx->d_tw2048;
-            o.tails = c.d_tails; o.merged_in = c.tails_lazy ? c.d_merged : nullptr;
-            o.merged_out = c.d_merged_alt; o.last_in = c.d_last_in;
-            o.tw = ctx->d_tw; o.gain = gain; o.fp_mode = c.fp_mode;
-            hipError_t e = launch_conv_p1_os(o, st, ev_start, ev_stop);
-            if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_os launch: ") + hipGetErrorString(e));
-            std::swap(c.d_merged, c.d_merged_alt);
-            c.tails_lazy = true;
-            c.cnt += (unsigned long long)n_blocks;
-            for (int p = 0; p < 4; ++p) c.since[p] += n_blocks;
-            c.last_kernel = OHS_CONV_KERNEL_HOP1536_P1; c.last_ranges = K;
-            return OHS_OK;
-        }
-        const long long target_override = tn.p1_target_waves;
-        int xcd_lo = c.xcd_lo, xcd_n = c.xcd_n;
-        if (tn.p1_xcd_n > 0) { xcd_lo = tn.p1_xcd_lo; xcd_n = tn.p1_xcd_n; }
-        const long long K = conv_p1_chunks(ctx, c.S, n_blocks, target_override, xcd_n);
-        if ((size_t)K > c.chunk_tails_cap) {
-            DeviceWideSection dws;
-            HIP_TRY(hipStreamSynchronize(st));
-            if (c.d_chunk_tails) hipFree(c.d_chunk_tails);
-            c.d_chunk_tails = nullptr; c.chunk_tails_cap = 0;
-            HIP_TRY(hipMalloc(&c.d_chunk_tails, c.S * (size_t)K * 512 * sizeof(float2)));
-            c.chunk_tails_cap = (size_t)K;
-        }
-        ConvP1Args a;
-        a.in = in; a.out = out;
-        a.in_stream_stride = in_ss; a.in_ch_stride = in_cs;
-        a.out_stream_stride = out_ss; a.out_ch_stride = out_cs;
-        a.n_blocks = n_blocks; a.n_streams = (int)c.S; a.chunks = (int)K;
-        a.CD = c.d_cd;
-        for (int p = 0; p < 4; ++p) a.H[p] = c.d_H[p];
-        a.tails = c.d_tails; a.tails_out = c.d_tails_alt; a.chunk_tails = c.d_chunk_tails;
-        a.merged_in = c.tails_lazy ? c.d_merged : nullptr;
-        a.merged_out = c.lazy_ok ? c.d_merged_alt : nullptr;
-        a.last_in = c.lazy_ok ? c.d_last_in : nullptr;
-        a.tw = ctx->d_tw; a.gain = gain; a.fp_mode = c.fp_mode;
-        a.xcd_lo = xcd_lo; a.xcd_n = xcd_n;
-        {   // boundary tails by the chunks' own waves where a stream's chunks share a workgroup (else: the pre-pass)
-            const bool allowed = conv_p1_waves_per_cu() == 16 && (K == 2 || K == 4 || K == 8 || K == 16);
-            a.own_tails = (allowed && tn.p1_own_tails) ? 1 : 0;
-        }
-        a.stagger = tn.p1_stagger;
-        a.prio_mode = tn.p1_prio;
-        // Chunk lengths by the age rank of the wave that runs a chunk (p1_chunk_begin), equal lengths when chunks are
-        // short.  In the plans that do not spread a stream's chunks over the ranks, ALL of a stream's chunks can sit on
-        // heavy ranks: its shortest chunk is then n * wmin / (K * wmax) blocks, and that one must keep >= 2 blocks (a
-        // chunk of zero blocks would make the boundary-tail code index block b0 - 1 = -1).
-        const int *kw = tn.p1_weights;
-        const int wmin = std::min(std::min(kw[0], kw[1]), std::min(kw[2], kw[3]));
-        const int wmax = std::max(std::max(kw[0], kw[1]), std::max(kw[2], kw[3]));
-        const bool weighted = (long long)n_blocks * wmin >= 2ll * K * wmax;
-        for (int g = 0; g < 4; ++g) a.weights[g] = weighted ? kw[g] : 1;
-        hipError_t e = launch_conv_p1(a, st, ev_start, ev_stop);
-        if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1 launch: ") + hipGetErrorString(e));
-        if (c.lazy_ok) {
-            std::swap(c.d_merged, c.d_merged_alt);
-            c.tails_lazy = true;
-        } else {
-            std::swap(c.d_tails, c.d_tails_alt);
-        }
-        c.last_kernel = OHS_CONV_KERNEL_BLOCK512_P1; c.last_ranges = (int)K;
-    } else {
-        if (ev_start) HIP_TRY(hipEventRecord(ev_start, st));
-        ev_scope.armed = true;
-        int Pmax = 1;
-        for (int p = 0; p < 4; ++p) Pmax = std::max(Pmax, c.P[p]);
-        if (allow_fast && c.d_xhist && Pmax >= lb_min_p()) {
-            // Block 2048 / FFT 4096 (conv_lb_kernels.hip).  It convolves the input history itself, so every path must be
-            // allowed to see all of its own response's reach of it: older than its response (and the history that deep),
-            // or reset together with all the others (the history was zeroed then).
-            bool deep = true;
-            for (int p = 0; p < 4; ++p) deep = deep && c.since[p] >= c.P[p] && c.xh_valid >= (long long)c.P[p] * BS;
-            const bool together = c.since[0] == c.since[1] && c.since[1] == c.since[2] && c.since[2] == c.since[3] &&
-                                  c.xh_valid >= c.xh_len;
-            const bool lb_ok = (deep || together) && ((in_ss | in_cs | out_ss | out_cs) & 3) == 0 &&
-                               ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-            if (lb_ok && (c.conv_plan == 2 || (c.conv_plan == 0 && conv_plan_auto_is_lb(c.S, n_blocks, Pmax)))) {
-                // Long out-of-place calls on responses of at most two 8192-tap partitions: block 8192 / FFT 16384, one kernel (the
-                // buffers must not overlap at all: a run's first windows read frames in front of its own blocks).  Where it pays
-                // (profiles/r05_xb_vs_lb_shapes.txt): calls of 128 blocks or more; with two partitions, on 32 streams or more.
-                const int P2x = (Pmax + 15) / 16;
-                const long long call_frames = (long long)n_blocks * BS;
-                const float *in_end = in + (c.S - 1) * in_ss + in_cs + call_frames;
-                const float *out_end = out + (c.S - 1) * out_ss + out_cs + call_frames;
-                const bool apart = in_end <= out || out_end <= in;
-                const bool xb = apart && conv_plan_auto_is_xb(c.S, n_blocks, Pmax) &&
-                                c.xh_len >= (long long)P2x * kXbBlock && call_frames < (1ll << 29);
-                const int rcl = xb ? conv_xb_launch(c, ctx, in, in_ss, in_cs, out, out_ss, out_cs, n_blocks, P2x, gain, st)
-                                   : conv_lb_launch(c, ctx, in, in_ss, in_cs, out, out_ss, out_cs, n_blocks, gain, st);
-                if (rcl) return rcl;
-                c.cnt += (unsigned long long)n_blocks;
-                for (int p = 0; p < 4; ++p) c.since[p] += n_blocks;
-                return OHS_OK;
-            }
-        }
-        {   // these kernels read and write the per-path overlaps
-            const int rcm = conv_materialise_state(c, ctx, st);
-            if (rcm) return rcm;
-        }
-        c.lb_valid = 0;         // (the block-2048 ring does not see the blocks of this call)
-        // The call's frames join the input history of the block-2048 plan (what it starts from when a later call takes it): the
-        // time-parallel forward kernel appends them itself, the sequential kernel's calls get a launch for it -- in front of
-        // anything that overwrites them in place.
-        const long long call_frames = (long long)n_blocks * BS;
-        const bool xh_on = c.d_xhist != nullptr;
-        const bool xh_ok = xh_on && ((in_ss | in_cs) & 3) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
-        const long long xh_cnt = xh_on ? std::min(call_frames, c.xh_len) : 0;
-        const long long xh_head0 = c.xh_head;
-        bool xh_lost = false;
-        auto xh_append_launch = [&]() -> int {
-            if (!xh_on) return OHS_OK;
-            if (!xh_ok) { xh_lost = true; return OHS_OK; }      // (buffers the 16-byte copy cannot read: the history no longer follows the stream)
-            hipError_t e = launch_conv_lb_xhist_append(in, in_ss, in_cs, c.d_xhist, c.xh_len, xh_head0, call_frames, (int)c.S, st);
-            if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("input history update: ") + hipGetErrorString(e));
-            return OHS_OK;
-        };
-        auto xh_advance = [&]() {
-            if (!xh_on) return;
-            if (xh_lost) { c.xh_valid = 0; return; }
-            c.xh_head = (xh_head0 + xh_cnt) % (2 * c.xh_len);
-            c.xh_valid = std::min(c.xh_len, c.xh_valid + call_frames);
-        };
-        const bool since_equal = c.since[0] == c.since[1] && c.since[1] == c.since[2] && c.since[2] == c.since[3];
-        bool since_old = true;
-        for (int p = 0; p < 4; ++p) since_old = since_old && c.since[p] >= c.P[p] - 1;
-        // gate-free condition of the time-parallel kernels: no path may have blocks in the ring that
-        // it must not see (either every path is older than its own IR -- path p reads P[p] - 1 blocks back --, or all
-        // were reset together: conv_set_ir zeroed the ring then)
-        const bool gate_free = since_old || since_equal;
-        // Otherwise -- a per-path set_ir in mid-stream -- the same three kernels run on a ring whose old blocks they
-        // cannot reach (the call starts Ppad - 1 zeroed slots further on) and k_conv_tp_old adds what each path may
-        // still see of them to the first Pmax - 1 blocks.  The first segment must reach beyond every old block
-        // (n_blocks >= Pmax): the state it leaves behind is computed gate-free.  Shorter calls take the general kernel
-        // (one wave per stream, blocks in sequence: 290 x slower on BASELINE config 4, which is why long calls do not).
-        // (calls of 1 .. 3 blocks too: until round 5 they went through the sequential kernel -- one wave per stream, 93 us per
-        // block on BASELINE config 4's shape, whatever the number of streams: profiles/r05_short_calls_before.jsonl)
-        const bool tp_gated = allow_fast && !gate_free && n_blocks >= Pmax;
-        const bool tp = allow_fast && (gate_free || tp_gated);
-        auto general = [&](const float *gin, float *gout, int nb, unsigned long long cnt, int since_add,
-                           int skip_store, int zero_in, float2 *tails_out) -> int {
-            ConvGeneralArgs a;
-            a.in = gin; a.out = gout;
-            a.in_stream_stride = in_ss; a.in_ch_stride = in_cs;
-            a.out_stream_stride = out_ss; a.out_ch_stride = out_cs;
-            a.n_blocks = nb;
-            for (int p = 0; p < 4; ++p) { a.H[p] = c.d_H[p]; a.P[p] = c.P[p]; a.since[p] = c.since[p] + since_add; }
-            a.hist = c.d_hist; a.cap = c.cap; a.cnt = cnt;
-            a.tails = c.d_tails; a.tails_out = tails_out;
-            a.skip_store = skip_store; a.zero_tails_in = zero_in;
-            a.tw = ctx->d_tw; a.gain = gain; a.fp_mode = c.fp_mode;
-            hipError_t e = launch_conv_general(a, (int)c.S, st);
-            if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv launch: ") + hipGetErrorString(e));
-            return OHS_OK;
-        };
-        if (!tp) {
-            int rc = xh_append_launch();
-            if (rc) return rc;
-            xh_advance();
-            rc = general(in, out, n_blocks, c.cnt, 0, 0, 0, c.d_tails);
-            if (rc) return rc;
-            c.last_kernel = OHS_CONV_KERNEL_SEQUENTIAL; c.last_ranges = 1;
-        } else {
-            // segment size: keep the MAC scratch around 128 MiB
-            long long SEG = 16384 / (long long)c.S;
-            SEG = std::max<long long>(8, std::min<long long>(SEG, 1024));
-            if (tp_gated) SEG = std::max<long long>(SEG, Pmax);
-            const long long seg_max = std::min<long long>(SEG, n_blocks);
-            const int Ppad = Ppad_for_ring(Pmax);
-            // (gated: old blocks + the zeroed gap + the segment live in the ring together)
-            int rc = conv_grow_ring(c, (int)(seg_max + (tp_gated ? 2 : 1) * (Ppad - 1) + (tp_gated ? Pmax : 0)), st);
-            if (rc) return rc;
-            const unsigned long long cnt_old = c.cnt;
-            if (tp_gated) {
-                // the zeroed gap: ring slots cnt .. cnt + Ppad - 2 of every stream (two strided memsets when it wraps)
-                const unsigned long long gap = (unsigned long long)(Ppad - 1), cap = (unsigned long long)c.cap;
-                const unsigned long long s0 = c.cnt & (cap - 1), n0 = std::min(gap, cap - s0);
-                const size_t pitch = (size_t)c.cap * NF * sizeof(float2);
-                HIP_TRY(hipMemset2DAsync(c.d_hist + s0 * NF, pitch, 0, (size_t)n0 * NF * sizeof(float2), c.S, st));
-                if (n0 < gap)
-                    HIP_TRY(hipMemset2DAsync(c.d_hist, pitch, 0, (size_t)(gap - n0) * NF * sizeof(float2), c.S, st));
-                c.cnt += gap;
-            }
-            if (!c.d_cdm || c.cdm_ppad != Ppad) {       // (a set_ir that keeps Ppad re-uses the buffer: no wait, no malloc)
-                DeviceWideSection dws;
-                HIP_TRY(hipStreamSynchronize(st));
-                if (c.d_cdm) hipFree(c.d_cdm);
-                c.d_cdm = nullptr; c.cdm_valid = false;
-                HIP_TRY(hipMalloc(&c.d_cdm, (size_t)Ppad * 2 * NF * sizeof(float2)));
-                c.cdm_ppad = Ppad;
-            }
-            if (!c.cdm_valid) {
-                hipError_t e = launch_build_cd_multi(c.d_H[0], c.d_H[1], c.d_H[2], c.d_H[3], c.P[0], c.P[1],
-                                                     c.P[2], c.P[3], Ppad, c.d_cdm, st);
-                if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("build_cd_multi: ") + hipGetErrorString(e));
-                c.cdm_ppad = Ppad; c.cdm_valid = true;
-            }
-            if ((size_t)seg_max > c.w_blocks) {
-                DeviceWideSection dws;
-                HIP_TRY(hipStreamSynchronize(st));
-                if (c.d_W) hipFree(c.d_W);
-                c.d_W = nullptr; c.w_blocks = 0;
-                HIP_TRY(hipMalloc(&c.d_W, c.S * (size_t)seg_max * NF * sizeof(float2)));
-                c.w_blocks = (size_t)seg_max;
-            }
-            if (!c.d_W1) HIP_TRY(hipMalloc(&c.d_W1, c.S * (size_t)NF * sizeof(float2)));
-            long long done = 0;
-            while (done < n_blocks) {
-                const int seg = (int)std::min<long long>(SEG, n_blocks - done);
-                ConvTpArgs a;
-                a.in = in + done * BS; a.out = out + done * BS;
-                a.in_stream_stride = in_ss; a.in_ch_stride = in_cs;
-                a.out_stream_stride = out_ss; a.out_ch_stride = out_cs;
-                a.n_streams = (int)c.S; a.seg_blocks = seg; a.n_mac = seg; a.Ppad = Ppad;
-                a.CD = c.d_cdm; a.hist = c.d_hist; a.cap = c.cap; a.cnt = c.cnt + (unsigned long long)done;
-                a.W = c.d_W; a.W1 = c.d_W1; a.tails = c.d_tails; a.tails_out = c.d_tails_alt;
-                a.pairs = ctx->d_pairs; a.n_pairs = ctx->n_pairs;
-                a.tw = ctx->d_tw; a.gain = gain; a.fp_mode = c.fp_mode;
-                // (frame i of the segment is frame done * 512 + i of the call; the call's last xh_cnt frames are appended)
-                a.xh_ring = xh_on ? c.d_xhist : nullptr; a.xh_len = c.xh_len; a.xh_head = xh_head0;
-                a.xh_frame0 = done * BS - (call_frames - xh_cnt);
-                hipError_t e = launch_conv_tp_forward(a, st);
-                if (e == hipSuccess) e = launch_conv_tp_mac(a, st);
-                if (e == hipSuccess && tp_gated && done == 0 && Pmax > 1) {
-                    ConvTpOldArgs o;
-                    o.n_streams = (int)c.S; o.n_old = Pmax - 1; o.Pmax = Pmax;
-                    for (int p = 0; p < 4; ++p) { o.H[p] = c.d_H[p]; o.P[p] = c.P[p]; o.since[p] = c.since[p]; }
-                    o.hist = c.d_hist; o.cap = c.cap; o.cnt_old = cnt_old;
-                    o.W = c.d_W; o.n_mac = seg; o.fp_mode = c.fp_mode;
-                    e = launch_conv_tp_old(o, st);
-                }
-                if (e == hipSuccess) e = launch_conv_tp_inverse(a, st);   // block 0 reads the OLD state; new state -> the other slab
-                if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_tp: ") + hipGetErrorString(e));
-                std::swap(c.d_tails, c.d_tails_alt);
-                done += seg;
-                c.last_kernel = OHS_CONV_KERNEL_BLOCK512_TP; c.last_ranges = seg;
-            }
-            xh_advance();
-        }
-    }
-    c.cnt += (unsigned long long)n_blocks;
-    for (int p = 0; p < 4; ++p) c.since[p] += n_blocks;
     return OHS_OK;
 }
 

@@ -183,7 +183,7 @@ struct ConvState {
     // block 8192 / FFT 16384 (conv_xb_kernels.hip): tables of the response's one or two 8192-tap partitions; valid with lb_cd_valid's
     // generation (every place that invalidates the block-2048 tables bumps lb_tables_gen)
     float4 *d_xb_cd = nullptr, *d_xb_ab = nullptr;
-    int xb_p2 = 0, xb_form = 0;
+    int xb_p2 = 0;
     unsigned long long lb_tables_gen = 1, xb_cd_gen = 0;
     // Engines (one stream) with a response of more than one partition: the next call's sums over the partitions behind it
     // (kernels.h: ConvGeneralArgs::pre), computed by the kernel that served the previous call.  They belong to the state
@@ -203,6 +203,16 @@ struct ConvState {
 
 void conv_free(ConvState &c);
 inline int conv_max_p(const ConvState &c) { return std::max(std::max(c.P[0], c.P[1]), std::max(c.P[2], c.P[3])); }
+inline bool conv_since_equal(const ConvState &c) { return c.since[0] == c.since[1] && c.since[1] == c.since[2] && c.since[2] == c.since[3]; }
+inline bool conv_since_zero(const ConvState &c) { return conv_since_equal(c) && c.since[0] == 0; }     // every path reset since the last block
+// the input history holds all of every path's own response's reach of the past that the path may see: each path older than
+// its response (and the history that deep), or all reset together with the others (the history was zeroed then)
+inline bool conv_history_covers_paths(const ConvState &c)
+{
+    bool deep = true;
+    for (int p = 0; p < 4; ++p) deep = deep && c.since[p] >= c.P[p] && c.xh_valid >= (long long)c.P[p] * OHS_BLOCK_SIZE;
+    return deep || (conv_since_equal(c) && c.xh_valid >= c.xh_len);
+}
 // the `pre` fields of an engine kernel's arguments for a call that completes k blocks (<= 8)
 inline void conv_pre_args(const ConvState &c, ConvGeneralArgs &a, int k)
 {

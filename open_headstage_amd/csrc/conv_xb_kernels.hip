@@ -33,7 +33,7 @@
 // Three workgroup barriers per block.  256 VGPRs (two partitions: 243 used, no scratch).
 //
 // Measured (profiles/r05_xb_*, LABNOTES.md round 5): BASELINE config 4 0.118 ms per step against 0.135-0.140 for block 2048
-// (0.152-0.165 for a first form with sixteen waves and a pair image in LDS: experiments/conv_xb16_kernels.hip); 1024 blocks
+// (0.152-0.165 for a first form with sixteen waves and a pair image in LDS, since retired: LABNOTES.md); 1024 blocks
 // per call 0.38 against 0.55; 256 streams 0.41 against 0.56.  What bounds it: one workgroup per CU means the CUs' window
 // loads come as bursts (18-27 us of a step are pure load time); the vector unit is ~40 % busy.
 #include "kernels.h"

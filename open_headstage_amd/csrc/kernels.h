@@ -389,11 +389,6 @@ hipError_t launch_conv_xb_build_cd(const float2 *ab, int P2, float4 *cd, hipStre
 int conv_xb_run_for(int n_streams, int n_blk, int P2, int num_cus);
 void conv_xb_build_twiddles(float2 *out);       // host: [15][1024]
 constexpr int kXbBlock = 8192;                  // frames per block of this plan
-#ifdef OHS_EXPERIMENTS
-// the plan's first form (experiments/conv_xb16_kernels.hip): sixteen waves, pair tables [P2][2 planes][8192] as the block-2048 plan's
-hipError_t launch_conv_xb16(const ConvXbArgs &a, hipStream_t st);
-hipError_t launch_conv_xb16_build_cd(const float4 *ab, int P2, float4 *cd, hipStream_t st);
-#endif
 
 // IR chunk -> spectrum: dst[part][16][64], one wave per partition.
 hipError_t launch_ir_spectrum(const float *d_ir, int len, int n_parts, float2 *dst,

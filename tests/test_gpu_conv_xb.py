@@ -1,7 +1,6 @@
 """The block-8192 / FFT-16384 kernel for long out-of-place calls on long impulse responses (csrc/conv_xb_kernels.hip: the library's
 choice for responses of 2 .. 32 partitions of 512 taps on calls of 128 blocks or more -- with more than 16 partitions on 32 streams
-or more), and its sixteen-wave first form (csrc/experiments/conv_xb16_kernels.hip, experiments build, Tuning::xb_form = 1), checked
-against the oracle -- the restatement of the reference's uniform block-512 partitioning
+or more), checked against the oracle -- the restatement of the reference's uniform block-512 partitioning
 (src/dsp/convolution.rs:120-132,236-289) -- and against f64 direct convolution: one and two partitions of 8192 taps, calls that
 end inside an 8192-frame block, calls that follow calls served by the other plans (the state at rest is the input history all of
 them share), a per-path set_ir in mid-stream, paths of different lengths and a muted one."""
@@ -23,38 +22,20 @@ def _oracle_engines(oracle, irs, S):
     return engs
 
 
-_LIB = {"library": None}
-
-
-@pytest.fixture(autouse=True, params=["product", "sixteen_waves"])
-def _form(exp_tuning, request):
-    """product: libohs_hip.so as shipped; sixteen_waves: the experiments library with the first form selected.  Both with the
-    two-partition kernel allowed on any number of streams (the tests use 2 .. 3)."""
-    from open_headstage_amd import _ffi
-    if request.param == "product":
-        _LIB["library"] = None
-    else:
-        _LIB["library"] = _ffi.experiments_lib()
-        exp_tuning("xb_form", 1)
-        exp_tuning("xb_min_streams_p2", 1)
-    yield
-    _LIB["library"] = None
+@pytest.fixture(autouse=True, params=["product"])
+def _library():
+    """every test runs on the product library, libohs_hip.so as shipped (the parameter keeps the ids these tests have
+    always had)"""
 
 
 def _make(ohs, S, irs, plan=0, gain=1.0):
-    bp = ohs.BatchProcessor(S, num_bands=10, library=_LIB["library"])
+    bp = ohs.BatchProcessor(S, num_bands=10)
     for p in range(4):
         bp.set_ir(p, irs[p])
     bp.set_eq_enabled(False)
     bp.set_gain(gain)
     bp.set_conv_plan(plan)
     return bp
-
-
-def _streams(taps):
-    """the library takes the kernel for two partitions of 8192 taps from 32 streams on: 34 streams that repeat three signals
-    (the experiments library of the sixteen-wave form has that threshold lowered: 3 streams do)"""
-    return 34 if taps > 8192 and _LIB["library"] is None else 3
 
 
 def _signals(synth, S, first_id, frames):
@@ -70,7 +51,7 @@ def test_block_8192_kernel_matches_the_oracle_and_f64(oracle, taps, blocks):
     import torch
     import open_headstage_amd as ohs
     from open_headstage_amd import synth
-    S = _streams(taps)
+    S = 34 if taps > 8192 else 3        # (the kernel for two partitions of 8192 taps: from 32 streams on)
     irs = synth.hrir_set(taps)
     bp = _make(ohs, S, irs, 0, gain=0.9)
     engs = _oracle_engines(oracle, irs, 3)
@@ -101,8 +82,6 @@ def test_what_the_library_does_not_give_the_kernel(oracle):
     import torch
     import open_headstage_amd as ohs
     from open_headstage_amd import synth
-    if _LIB["library"] is not None:
-        pytest.skip("the product's rule")
     for taps, S, nb, in_place, want in ((16384, 34, 160, True, "block2048"), (16384, 34, 127, False, "block2048"),
                                         (16384, 8, 160, False, "block2048"), (16385, 34, 160, False, "block2048"),
                                         (8192, 2, 160, False, "block8192"), (16384, 32, 128, False, "block8192")):
@@ -122,7 +101,7 @@ def test_different_lengths_a_muted_path_and_a_midstream_set_ir(oracle):
     import torch
     import open_headstage_amd as ohs
     from open_headstage_amd import synth
-    S = _streams(16384)
+    S = 34
     hb = synth.hrir_set(16384)
     irs = [hb[0], hb[1][:700], hb[2][:0], hb[3][:9000]]
     bp = _make(ohs, S, irs)
