@@ -396,7 +396,42 @@ int  ohs_batch_reset(ohs_batch *b);
  * d_in may equal d_out. Strides are in floats. */
 int  ohs_batch_process(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
                        size_t stream_stride, size_t channel_stride, void *hip_stream);
-/* The same, but `hip_stream` is NOT made to wait for the last time chunk's convolution (it runs on an
+/* ---- a schedule of EQ tables and gains inside one call ----
+ * The reference refreshes all bands' coefficients and reads a new master gain once per host block (lib.rs:1180-1207).  A scheduled
+ * call does that inside ONE call: it is cut into segments of seg_blocks * 512 frames, and every segment names the EQ table it is
+ * filtered with and the gain its frames leave the convolution with.  At a segment boundary every band takes its new five
+ * constants and keeps s1, s2 (update_coefficients, parametric_eq.rs:85-114), and the enabled flags become the new table's (a
+ * disabled band hands its input on and keeps its state).  The result is what ohs_batch_set_eq_band_coeffs for every band +
+ * ohs_batch_set_gain + ohs_batch_process per segment produce (bit for bit under plan 1 with taps <= 512).
+ *
+ * ohs_batch_set_schedule_tables: n_tables tables of the handle's num_bands bands, coeffs[n_tables][num_bands][5] =
+ * {b0, b1, b2, a1, a2}, enabled[n_tables][num_bands].  Host arrays, copied before return.  Replaces any earlier set; n_tables == 0
+ * frees it.  Not on the audio path: it waits for the device. */
+int  ohs_batch_set_schedule_tables(ohs_batch *b, size_t n_tables, const float *coeffs, const uint8_t *enabled);
+/* ohs_batch_process with a schedule: segment k = frames [k * seg_blocks * 512, (k + 1) * seg_blocks * 512) of the call (the last one
+ * may be short); n_segments = ceil(n_blocks / seg_blocks).  table_idx[k] < n_tables (32-bit entries), gain[k] any float.  Host arrays of n_segments
+ * entries, reusable on return.  gain == NULL: the handle's gain throughout; table_idx == NULL: the handle's current table
+ * throughout.  Asynchronous on `hip_stream` like ohs_batch_process; d_in may equal d_out.
+ * After the call the handle's shared table and gain ARE the last segment's, as if the setters had been called: a following
+ * ohs_batch_process continues with them.  EQ state, history and overlaps carry over in both directions; scheduled and plain
+ * calls may be mixed freely.
+ * OHS_ERR_INVALID_ARG, before anything is queued (the handle stays usable): an index out of range, seg_blocks == 0, table_idx given
+ * with no tables uploaded, a handle with per-stream tables (ohs_batch_set_stream_eq_band_coeffs; until ohs_batch_share_eq_table).
+ * Where the wave-ring EQ form serves the call (ohs_batch_last_eq_form), a change of coefficients under the same enabled flags
+ * happens inside the EQ launch; a change of the flags, and every other EQ form, is one EQ launch per run of equal tables. */
+int  ohs_batch_process_scheduled(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
+                                 size_t channel_stride, size_t seg_blocks, const unsigned *table_idx, const float *gain,
+                                 void *hip_stream);
+/* which form of the EQ cascade served the handle's last EQ launch, and whether it was the scheduled kernel (tables changing
+ * inside the launch) */
+enum {
+    OHS_EQ_FORM_NONE = 0,       /* no EQ launch yet */
+    OHS_EQ_FORM_ROW_RING = 1,   /* ring form, four chains per wave in 16-lane rows */
+    OHS_EQ_FORM_WAVE_RING = 2,  /* ring form, one chain per wave */
+    OHS_EQ_FORM_CONVEYOR = 3    /* conveyor form (more than 12 bands per pass, exact-specials mode, far strides) */
+};
+int  ohs_batch_last_eq_form(const ohs_batch *b, int *form, int *scheduled);
+/* The same as ohs_batch_process, but `hip_stream` is NOT made to wait for the last time chunk's convolution (it runs on an
  * internal stream underneath the EQ): d_out is complete on `hip_stream` only after ohs_batch_join (a
  * stream-side wait, asynchronous) or ohs_batch_sync.  Back-to-back deferred calls with the same buffers
  * pipeline: the next call's EQ starts while the previous call's last convolution finishes; every other

@@ -111,6 +111,26 @@ class BatchProcessor:
         self._check(self._lib.ohs_batch_conv_plan_counts(self._h, c, int(bool(reset))))
         return {self.CONV_KERNELS[k]: int(c[k]) for k in range(1, 7) if c[k]}
 
+    EQ_FORMS = {0: "none", 1: "row_ring", 2: "wave_ring", 3: "conveyor"}
+
+    def last_eq_form(self):
+        """(form name, scheduled) of the most recent EQ launch: `scheduled` is True when the tables changed INSIDE the launch
+        (the wave ring's scheduled kernel), False for a plain launch (ohs_batch_last_eq_form)"""
+        f, sc = C.c_int(), C.c_int()
+        self._check(self._lib.ohs_batch_last_eq_form(self._h, C.byref(f), C.byref(sc)))
+        return self.EQ_FORMS.get(int(f.value), str(f.value)), bool(sc.value)
+
+    def set_schedule_tables(self, coeffs, enabled) -> None:
+        """The EQ tables a scheduled call chooses from: coeffs [n_tables][num_bands][5] = {b0, b1, b2, a1, a2}, enabled
+        [n_tables][num_bands]; replaces any earlier set, n_tables == 0 frees it (ohs_batch_set_schedule_tables)."""
+        c = np.ascontiguousarray(coeffs, dtype=np.float32)
+        e = np.ascontiguousarray(np.asarray(enabled) != 0, dtype=np.uint8)
+        n = 0 if c.size == 0 else c.shape[0]
+        if n and (c.shape != (n, self.num_bands, 5) or e.shape != (n, self.num_bands)):
+            raise ValueError(f"expected coeffs [n][{self.num_bands}][5] and enabled [n][{self.num_bands}]")
+        self._check(self._lib.ohs_batch_set_schedule_tables(self._h, n, c.ctypes.data_as(fp) if n else None,
+                                                            e.ctypes.data_as(C.POINTER(C.c_uint8)) if n else None))
+
     def reset(self) -> None:
         self._check(self._lib.ohs_batch_reset(self._h))
 
@@ -120,6 +140,46 @@ class BatchProcessor:
         fn = self._lib.ohs_batch_process_deferred if deferred else self._lib.ohs_batch_process
         self._check(fn(self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(stream_stride),
                  int(channel_stride), C.c_void_p(hip_stream) if hip_stream else None))
+
+    def process_scheduled_ptr(self, d_in: int, d_out: int, n_blocks: int, stream_stride: int, channel_stride: int,
+                              seg_blocks: int, table_idx=None, gains=None, hip_stream: int = 0) -> None:
+        """ohs_batch_process_scheduled: segment k = blocks [k seg_blocks, (k + 1) seg_blocks) of the call is filtered with table
+        table_idx[k] (set_schedule_tables) and leaves with gain gains[k]; None = the handle's table / gain throughout"""
+        n_segs = -(-int(n_blocks) // int(seg_blocks)) if seg_blocks else 0
+        t = g = None
+        if table_idx is not None:
+            t = np.ascontiguousarray(table_idx, dtype=np.uint32).ravel()
+            if t.size < n_segs:
+                raise ValueError(f"table_idx needs {n_segs} entries")
+        if gains is not None:
+            g = np.ascontiguousarray(gains, dtype=np.float32).ravel()
+            if g.size < n_segs:
+                raise ValueError(f"gains needs {n_segs} entries")
+        self._check(self._lib.ohs_batch_process_scheduled(
+            self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(stream_stride), int(channel_stride), int(seg_blocks),
+            t.ctypes.data_as(C.POINTER(C.c_uint32)) if t is not None else None, g.ctypes.data_as(fp) if g is not None else None,
+            C.c_void_p(hip_stream) if hip_stream else None))
+
+    def process_scheduled(self, x, seg_blocks: int, table_idx=None, gains=None, out=None, hip_stream: int | None = None):
+        """process() with a schedule of EQ tables and gains, one entry per segment of seg_blocks * 512 frames: what the reference
+        does when its host refreshes the bands and the master gain in front of every block.  x, out as in process()."""
+        import torch
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, 2, frames]")
+        S, ch, frames = x.shape
+        if S != self.n_streams or ch != 2 or frames % BLOCK_SIZE:
+            raise ValueError(f"expected [{self.n_streams}, 2, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
+        if x.device.index != self.device:
+            raise ValueError("tensor is on a different device than the BatchProcessor")
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+            raise ValueError("out must match x")
+        if hip_stream is None:
+            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+        self.process_scheduled_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, 2 * frames, frames, seg_blocks,
+                                   table_idx, gains, hip_stream)
+        return out
 
     def join(self, hip_stream: int | None = None) -> None:
         """Make `hip_stream` (default: torch's current stream) wait for a pending deferred call."""

@@ -75,6 +75,11 @@ void ohs_batch_destroy(ohs_batch *b)
     for (hipEvent_t e : b->ev_pool) hipEventDestroy(e);
     for (hipEvent_t e : b->ev_inflight) hipEventDestroy(e);
     for (hipEvent_t e : b->chunk_done) hipEventDestroy(e);
+    for (auto &sl : b->sched_slot) {
+        if (sl.h) hipHostFree(sl.h);
+        if (sl.d) hipFree(sl.d);
+        if (sl.done) hipEventDestroy(sl.done);
+    }
     for (int k = 0; k < ohs_batch::kHostSlots; ++k) {
         if (b->d_slot[k]) hipFree(b->d_slot[k]);
         if (b->ev_h2d[k]) hipEventDestroy(b->ev_h2d[k]);
@@ -237,17 +242,20 @@ int ohs_batch_reset(ohs_batch *b)
 }
 
 static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
-                              size_t stream_stride, size_t channel_stride, void *hip_stream, bool deferred);
+                              size_t stream_stride, size_t channel_stride, void *hip_stream, bool deferred,
+                              const BatchSchedule *sc);
 
+// sc (optional): the schedule of ohs_batch_process_scheduled, its device copies already queued on hip_stream
 static int batch_process_impl(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
-                              size_t stream_stride, size_t channel_stride, void *hip_stream, bool deferred)
+                              size_t stream_stride, size_t channel_stride, void *hip_stream, bool deferred,
+                              const BatchSchedule *sc = nullptr)
 {
     if (!b || !d_in || !d_out) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
     if (b->failed)
         return fail(OHS_ERR_HIP, "this batch failed in the middle of an earlier call (" + b->fail_msg +
                                      "): its per-stream state is half-advanced; ohs_batch_reset starts it afresh");
     const size_t spans_before = b->spans.size();
-    const int rc = batch_process_body(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, deferred);
+    const int rc = batch_process_body(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, deferred, sc);
     if (rc == OHS_OK || rc == OHS_ERR_INVALID_ARG) return rc;      // (argument errors are found before anything is queued)
     // A HIP call failed with part of the work queued.  Keep the message, then leave nothing dangling:
     const std::string why = g_err;
@@ -277,7 +285,8 @@ static int batch_process_impl(ohs_batch *b, const float *d_in, float *d_out, siz
 }
 
 static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
-                              size_t stream_stride, size_t channel_stride, void *hip_stream, bool deferred)
+                              size_t stream_stride, size_t channel_stride, void *hip_stream, bool deferred,
+                              const BatchSchedule *sc)
 {
     if (n_blocks == 0) return OHS_OK;
     if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
@@ -315,7 +324,16 @@ static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, siz
     };
     if (b->profiling) b->prof_calls++;
 
-    const bool eq_active = b->eq_enable && eq_any_enabled(b->eq);
+    // a schedule of tables: the EQ runs if any segment's table has a band enabled; a schedule of gains: every convolution launch
+    // gets the table and where its first block lies in the call
+    const bool sched_tabs = sc != nullptr && sc->tab != nullptr;
+    bool eq_active = b->eq_enable && eq_any_enabled(b->eq);
+    if (sched_tabs) {
+        eq_active = false;
+        for (size_t k = 0; k < sc->n_segs && b->eq_enable && !eq_active; ++k) eq_active = eq_schedule_table_any_enabled(b->eq, sc->tab[k]);
+    }
+    ConvGains cg;
+    if (sc && sc->d_gain) { cg.tab = sc->d_gain; cg.seg_blocks = (int)sc->seg_blocks; }
 
     const long long ss = (long long)stream_stride, cs = (long long)channel_stride;
     int rc;
@@ -338,7 +356,7 @@ static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, siz
             return fail(OHS_ERR_HIP, "injected failure (ohs_debug_inject_batch_failure)");
 #endif
         rc = span_begin(st, 1); if (rc) return rc;
-        rc = conv_launch(b->conv, b->ctx, d_in, ss, cs, d_out, ss, cs, (int)n_blocks, b->gain, st);
+        rc = conv_launch(b->conv, b->ctx, d_in, ss, cs, d_out, ss, cs, (int)n_blocks, b->gain, st, true, nullptr, nullptr, &cg);
         if (rc) return rc;
         return span_end(st);
     }
@@ -397,7 +415,9 @@ static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, siz
             rc = get_event(&ev_b); if (rc) return rc;
             b->ev_inflight.push_back(ev_b);
         }
-        rc = eq_launch(b->eq, d_in + off, d_out + off, ss, cs, (long long)nb_i * BS, st, nullptr, ev_a, ev_b);
+        // (the time chunks cut at block positions that need not be segment boundaries: every launch is told where it starts)
+        if (sched_tabs) rc = eq_launch_scheduled(b->eq, *sc, blk0, (size_t)nb_i, d_in + off, d_out + off, ss, cs, st, ev_a, ev_b);
+        else rc = eq_launch(b->eq, d_in + off, d_out + off, ss, cs, (long long)nb_i * BS, st, nullptr, ev_a, ev_b);
         if (rc) return rc;
         hipStream_t cst = st;
         // The LAST chunk's convolution has nothing to hide under: it runs on the caller's stream right behind its EQ
@@ -424,7 +444,8 @@ static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, siz
                 b->spans.push_back(sp);
                 cv_a = sp.a; cv_b = sp.b;
             }
-            rc = conv_launch(b->conv, b->ctx, d_out + off, ss, cs, d_out + off, ss, cs, nb_i, b->gain, cst, true, cv_a, cv_b);
+            cg.blk_off = (int)blk0;
+            rc = conv_launch(b->conv, b->ctx, d_out + off, ss, cs, d_out + off, ss, cs, nb_i, b->gain, cst, true, cv_a, cv_b, &cg);
             if (rc) return rc;
         }
         if (nch > 1 && deferred) {
@@ -455,6 +476,104 @@ int ohs_batch_process(ohs_batch *b, const float *d_in, float *d_out, size_t n_bl
                       size_t stream_stride, size_t channel_stride, void *hip_stream)
 {
     return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
+}
+
+int ohs_batch_set_schedule_tables(ohs_batch *b, size_t n_tables, const float *coeffs, const uint8_t *enabled)
+{
+    if (!b) return fail(OHS_ERR_INVALID_ARG, "batch is NULL");
+    if (n_tables > 0 && (!coeffs || !enabled)) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    if (n_tables > ((size_t)1 << 24)) return fail(OHS_ERR_INVALID_ARG, "n_tables too large");
+    HIP_TRY(hipSetDevice(b->device));
+    return eq_set_schedule_tables(b->eq, n_tables, coeffs, enabled, b->st);
+}
+
+int ohs_batch_last_eq_form(const ohs_batch *b, int *form, int *scheduled)
+{
+    if (!b || !form || !scheduled) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    *form = b->eq.last_form;
+    *scheduled = b->eq.last_scheduled ? 1 : 0;
+    return OHS_OK;
+}
+
+int ohs_batch_process_scheduled(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
+                                size_t channel_stride, size_t seg_blocks, const unsigned *table_idx, const float *gain,
+                                void *hip_stream)
+{
+    if (!b || !d_in || !d_out) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    if (seg_blocks == 0) return fail(OHS_ERR_INVALID_ARG, "seg_blocks is 0");
+    if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
+    if (b->eq.per_stream)
+        return fail(OHS_ERR_INVALID_ARG, "a scheduled call on a handle with per-stream EQ tables is not supported "
+                                         "(ohs_batch_share_eq_table goes back to the one shared table)");
+    if (table_idx && b->eq.sched_n == 0)
+        return fail(OHS_ERR_INVALID_ARG, "table_idx given, but no tables uploaded (ohs_batch_set_schedule_tables)");
+    seg_blocks = std::min(seg_blocks, std::max<size_t>(n_blocks, 1));
+    const size_t n_segs = (n_blocks + seg_blocks - 1) / seg_blocks;
+    if (table_idx)
+        for (size_t k = 0; k < n_segs; ++k)
+            if (table_idx[k] >= b->eq.sched_n) return fail(OHS_ERR_INVALID_ARG, "table_idx entry out of range");
+    if (b->failed || n_blocks == 0)     // (the plain call's answers)
+        return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
+    {
+        const size_t frames = n_blocks * BS;
+        if (channel_stride < frames || (b->conv.S > 1 && stream_stride < 2 * frames && stream_stride < channel_stride + frames))
+            return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
+    }
+    // the handle's table / gain become those of segment k (what the setters do)
+    auto adopt_table = [&](unsigned t) {
+        for (size_t band = 0; band < b->eq.nb; ++band)
+            eq_set_shared_band(b->eq, band, &b->eq.sched_coeffs[((size_t)t * b->eq.nb + band) * 5], b->eq.sched_en[(size_t)t * b->eq.nb + band]);
+    };
+    // A constant schedule is the plain call: same launches, same bits.
+    bool tabs_vary = false, gains_vary = false;
+    for (size_t k = 1; k < n_segs; ++k) {
+        tabs_vary = tabs_vary || (table_idx && table_idx[k] != table_idx[0]);
+        gains_vary = gains_vary || (gain && std::memcmp(&gain[k], &gain[0], sizeof(float)) != 0);
+    }
+    if (table_idx && !tabs_vary) { adopt_table(table_idx[0]); table_idx = nullptr; }
+    if (gain && !gains_vary) { b->gain = gain[0]; gain = nullptr; }
+    if (!table_idx && !gain)
+        return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
+
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    // the schedule's staging slot: free once the call that used it last has completed
+    ohs_batch::SchedSlot &slot = b->sched_slot[b->sched_next];
+    b->sched_next = (b->sched_next + 1) % ohs_batch::kSchedSlots;
+    if (slot.in_use) HIP_TRY(hipEventSynchronize(slot.done));
+    slot.in_use = false;
+    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    if (slot.cap < n_segs) {
+        if (slot.h) hipHostFree(slot.h);
+        if (slot.d) {
+            DeviceWideSection dws;
+            hipFree(slot.d);
+        }
+        slot.h = nullptr; slot.d = nullptr; slot.cap = 0;
+        const size_t cap = std::max<size_t>(1024, n_segs + n_segs / 2);
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&slot.h), 2 * cap * sizeof(unsigned), hipHostMallocDefault));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&slot.d), 2 * cap * sizeof(unsigned)));
+        slot.cap = cap;
+    }
+    BatchSchedule sc;
+    sc.seg_blocks = seg_blocks; sc.n_segs = n_segs; sc.tab = table_idx; sc.gain = gain;
+    if (table_idx) {
+        std::memcpy(slot.h, table_idx, n_segs * sizeof(unsigned));
+        HIP_TRY(hipMemcpyAsync(slot.d, slot.h, n_segs * sizeof(unsigned), hipMemcpyHostToDevice, st));
+        sc.d_tab = slot.d;
+    }
+    if (gain) {
+        std::memcpy(slot.h + slot.cap, gain, n_segs * sizeof(float));
+        HIP_TRY(hipMemcpyAsync(slot.d + slot.cap, slot.h + slot.cap, n_segs * sizeof(float), hipMemcpyHostToDevice, st));
+        sc.d_gain = reinterpret_cast<const float *>(slot.d + slot.cap);
+    }
+    const int rc = batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false, &sc);
+    if (hipEventRecord(slot.done, st) == hipSuccess) slot.in_use = true;
+    else hipStreamSynchronize(st);
+    if (rc) return rc;
+    if (table_idx) adopt_table(table_idx[n_segs - 1]);
+    if (gain) b->gain = gain[n_segs - 1];
+    return OHS_OK;
 }
 
 int ohs_batch_process_deferred(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,

@@ -15,6 +15,8 @@ struct ConvCall {
     const float *in; long long in_ss, in_cs;
     float *out; long long out_ss, out_cs;
     int n_blocks; float gain;
+    // a gain per segment instead (ConvGains; device memory): frames of block t leave with tab[(off + t) / seg]
+    const float *gain_tab = nullptr; int gain_seg = 1, gain_off = 0;
 };
 
 // right before the handle is deleted: the buffers only
@@ -832,6 +834,7 @@ static int conv_run_p1(ConvState &c, DeviceCtx *ctx, const ConvCall &k, const Co
     a.merged_out = c.lazy_ok ? c.d_merged_alt : nullptr;
     a.last_in = c.lazy_ok ? c.d_last_in : nullptr;
     a.tw = ctx->d_tw; a.gain = k.gain; a.fp_mode = c.fp_mode;
+    a.gain_tab = k.gain_tab; a.gain_seg = k.gain_seg; a.gain_off = k.gain_off;     // (k_conv_p1_gains looks the gain up itself)
     a.xcd_lo = plan.xcd_lo; a.xcd_n = plan.xcd_n;
     {   // boundary tails by the chunks' own waves where a stream's chunks share a workgroup (else: the pre-pass)
         const bool allowed = conv_p1_waves_per_cu() == 16 && (K == 2 || K == 4 || K == 8 || K == 16);
@@ -1012,7 +1015,7 @@ static int conv_run_tp(ConvState &c, DeviceCtx *ctx, const ConvCall &k, const Co
 
 int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
                 float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st,
-                bool allow_fast, hipEvent_t ev_start, hipEvent_t ev_stop)
+                bool allow_fast, hipEvent_t ev_start, hipEvent_t ev_stop, const ConvGains *gains)
 {
     // (ev_start / ev_stop: recorded at the start / completion of the call's launches)
     if (n_blocks <= 0) {                    // nothing to do (the pre-pass would index block -1)
@@ -1020,10 +1023,15 @@ int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, 
         if (ev_stop) HIP_TRY(hipEventRecord(ev_stop, st));
         return OHS_OK;
     }
-    const ConvCall k{in, in_ss, in_cs, out, out_ss, out_cs, n_blocks, gain};
+    // A gain per segment (ohs_batch_process_scheduled): k_conv_p1 looks it up at its store; every other family runs with gain 1
+    // and is followed by k_scale_segments (x * 1.0f is exact: the same bits, except where the pending-tails add below folds the
+    // gain in -- there (a + b) * g instead of a * g + b * g).  The plan is chosen exactly as for the plain call.
+    const bool seg_gains = gains != nullptr && gains->tab != nullptr;
+    ConvCall k{in, in_ss, in_cs, out, out_ss, out_cs, n_blocks, seg_gains ? 1.0f : gain};
     const ConvPlan plan = conv_choose_plan(c, ctx, k, allow_fast);
     int ranges = 0, rc;
     if (plan.kernel == OHS_CONV_KERNEL_BLOCK512_P1) {
+        if (seg_gains && !c.pt_active) { k.gain_tab = gains->tab; k.gain_seg = gains->seg_blocks; k.gain_off = gains->blk_off; }
         rc = conv_run_p1(c, ctx, k, plan, st, ev_start, ev_stop, ranges);
     } else if (plan.kernel == OHS_CONV_KERNEL_HOP1536_P1) {
         rc = conv_run_os(c, ctx, k, plan.K, st, ev_start, ev_stop, ranges);
@@ -1050,10 +1058,17 @@ int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, 
     if (c.pt_active) {
         // what the frames in front of a per-path set_ir still owe these frames (conv_lb_tail_route)
         const long long n = (long long)n_blocks * BS;
-        hipError_t e = launch_conv_lb_tails_add(out, out_ss, out_cs, n, c.d_ptail, c.pt_len, c.pt_pos, gain, (int)c.S, st);
+        // (with a gain table in k_conv_p1: tail * gain[segment] is not what this launch computes -- it adds with gain 1 in front of
+        // the scale pass below, so such a call takes the scale pass for the tails' sake)
+        hipError_t e = launch_conv_lb_tails_add(out, out_ss, out_cs, n, c.d_ptail, c.pt_len, c.pt_pos, k.gain, (int)c.S, st);
         if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("pending tails: ") + hipGetErrorString(e));
         c.pt_pos += n;
         if (c.pt_pos >= c.pt_len) c.pt_active = false;
+    }
+    if (seg_gains && !k.gain_tab) {
+        hipError_t e = launch_scale_segments(out, out_ss, out_cs, n_blocks, (int)c.S, gains->tab, gains->seg_blocks, gains->blk_off, st,
+                                             c.fp_mode);
+        if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("segment gains: ") + hipGetErrorString(e));
     }
     return OHS_OK;
 }

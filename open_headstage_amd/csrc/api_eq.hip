@@ -57,7 +57,8 @@ void eq_free(EqState &e)
     if (e.d_state) hipFree(e.d_state);
     if (e.d_stabs) hipFree(e.d_stabs);
     if (e.d_stamps) hipFree(e.d_stamps);
-    e.d_state = nullptr; e.d_stabs = nullptr; e.stabs_passes = 0; e.d_stamps = nullptr;
+    if (e.d_sched_lanes) hipFree(e.d_sched_lanes);
+    e.d_state = nullptr; e.d_stabs = nullptr; e.stabs_passes = 0; e.d_stamps = nullptr; e.d_sched_lanes = nullptr; e.sched_n = 0;
 }
 
 bool eq_any_enabled(const EqState &e)
@@ -142,8 +143,9 @@ static int eq_launch_table(EqState &e, const float *coeffs, const unsigned char 
         if (tuning().eq_xcd_n > 0) { xcd_lo = tuning().eq_xcd_lo; xcd_n = tuning().eq_xcd_n; }
         const bool first = p0 == 0, last = p0 + 16 >= on.size();
         hipError_t err = launch_eq_pass(src, out, ss, cs, n, (int)chains, t, nbp, d_state, st, e.exact_specials, e.fp_mode,
-                                        xcd_lo, xcd_n, first ? ev_start : nullptr, last ? ev_stop : nullptr, e.d_stamps);
+                                        xcd_lo, xcd_n, first ? ev_start : nullptr, last ? ev_stop : nullptr, e.d_stamps, &e.last_form);
         if (err != hipSuccess) return fail(OHS_ERR_HIP, std::string("eq launch: ") + hipGetErrorString(err));
+        e.last_scheduled = false;
         src = out;
         did = true;
     }
@@ -224,7 +226,8 @@ int eq_launch(EqState &e, const float *in, float *out, long long ss, long long c
             for (size_t pk = 0; pk < passes; ++pk) {
                 hipError_t err = launch_eq_ring_streams(pk ? out : in, out, ss, cs, n, (int)e.chains, e.d_stabs + pk * S, e.d_state, st,
                                                         e.fp_mode, xcd_lo, xcd_n, pk == 0 ? ev_start : nullptr,
-                                                        pk + 1 == passes ? ev_stop : nullptr);
+                                                        pk + 1 == passes ? ev_stop : nullptr, &e.last_form);
+                e.last_scheduled = false;
                 if (err != hipSuccess) return fail(OHS_ERR_HIP, std::string("eq launch (per-stream tables): ") + hipGetErrorString(err));
             }
             did = true;
@@ -257,6 +260,146 @@ int eq_launch(EqState &e, const float *in, float *out, long long ss, long long c
         if (ev_stop) HIP_TRY(hipEventRecord(ev_stop, st));
     }
     if (did_anything) *did_anything = did;
+    return OHS_OK;
+}
+
+// ---- schedule tables (ohs_batch_set_schedule_tables / ohs_batch_process_scheduled) ------------------------------------------
+// Not on the audio path: waits for what the stream has queued (a launch in flight may still read the old lane tables).
+int eq_set_schedule_tables(EqState &e, size_t n_tables, const float *coeffs, const uint8_t *enabled, hipStream_t st)
+{
+    DeviceWideSection dws;
+    HIP_TRY(hipDeviceSynchronize());
+    if (e.d_sched_lanes) hipFree(e.d_sched_lanes);
+    e.d_sched_lanes = nullptr; e.sched_n = 0;
+    e.sched_coeffs.clear(); e.sched_en.clear();
+    if (n_tables == 0) return OHS_OK;
+    e.sched_coeffs.assign(coeffs, coeffs + n_tables * e.nb * 5);
+    e.sched_en.assign(enabled, enabled + n_tables * e.nb);
+    for (unsigned char &v : e.sched_en) v = v != 0;
+    // lane constants per table: lane l is pre lane of enabled band l and post lane of enabled band l - 1 (eq_ring64_body.hpp)
+    std::vector<float> lanes(n_tables * 5 * 16);
+    for (size_t t = 0; t < n_tables; ++t) {
+        float *L = &lanes[t * 5 * 16];
+        for (int l = 0; l < 16; ++l) { L[l] = 1.0f; L[16 + l] = 0.0f; L[32 + l] = 0.0f; L[48 + l] = 0.0f; L[64 + l] = 0.0f; }
+        std::vector<size_t> on;
+        for (size_t b = 0; b < e.nb; ++b)
+            if (e.sched_en[t * e.nb + b]) on.push_back(b);
+        if (on.empty() || on.size() > 12) continue;
+        for (size_t j = 0; j < on.size(); ++j) {
+            const float *c = &e.sched_coeffs[(t * e.nb + on[j]) * 5];
+            L[j] = c[0]; L[16 + j] = c[1];
+            L[32 + j + 1] = c[2]; L[48 + j + 1] = c[3]; L[64 + j + 1] = c[4];
+        }
+    }
+    HIP_TRY(hipMalloc(&e.d_sched_lanes, lanes.size() * sizeof(float)));
+    HIP_TRY(hipMemcpy(e.d_sched_lanes, lanes.data(), lanes.size() * sizeof(float), hipMemcpyHostToDevice));
+    e.sched_n = n_tables;
+    (void)st;
+    return OHS_OK;
+}
+
+bool eq_schedule_table_any_enabled(const EqState &e, size_t table)
+{
+    for (size_t b = 0; b < e.nb; ++b)
+        if (e.sched_en[table * e.nb + b]) return true;
+    return false;
+}
+
+// Blocks [blk0, blk0 + n_blocks) of a scheduled call.  Consecutive segments with one table index are a RUN.  Consecutive runs
+// whose tables have the same enabled flags (1 .. 12 of them) are ONE launch of k_eq_ring_sched where launch_eq_pass would take
+// the wave ring for those frames: the coefficients change inside the kernel.  Everything else -- a change of the flags (the
+// lanes' roles change; state travels through the state slots, a disabled band's stays frozen in its slot), the row form, the
+// conveyor form, more than 12 bands, launches under 8 192 samples -- is one plain launch sequence per run with that run's table,
+// exactly what the per-segment call loop launches.  A lone run is the plain call's launch.
+int eq_launch_scheduled(EqState &e, const BatchSchedule &sc, size_t blk0, size_t n_blocks, const float *in, float *out,
+                        long long ss, long long cs, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop)
+{
+    struct Run { size_t b0, b1; unsigned tab; };
+    std::vector<Run> runs;
+    for (size_t blk = blk0; blk < blk0 + n_blocks;) {
+        const size_t seg = blk / sc.seg_blocks;
+        const size_t end = std::min(blk0 + n_blocks, (seg + 1) * sc.seg_blocks);
+        const unsigned t = sc.tab[seg];
+        if (!runs.empty() && runs.back().tab == t) runs.back().b1 = end;
+        else runs.push_back({blk, end, t});
+        blk = end;
+    }
+    auto same_flags = [&](unsigned a, unsigned b) {
+        return std::memcmp(&e.sched_en[a * e.nb], &e.sched_en[b * e.nb], e.nb) == 0;
+    };
+    auto count_on = [&](unsigned t) {
+        size_t k = 0;
+        for (size_t b = 0; b < e.nb; ++b) k += e.sched_en[t * e.nb + b];
+        return k;
+    };
+    // groups of runs with equal flags
+    struct Group { size_t r0, r1; };
+    std::vector<Group> groups;
+    for (size_t r = 0; r < runs.size(); ++r) {
+        if (!groups.empty() && same_flags(runs[groups.back().r0].tab, runs[r].tab)) groups.back().r1 = r + 1;
+        else groups.push_back({r, r + 1});
+    }
+    // the events ride in the dispatch when the chunk is exactly one kernel launch sequence (as the plain call's); else around
+    const bool single = groups.size() == 1 && count_on(runs[0].tab) > 0 &&
+                        (groups[0].r1 - groups[0].r0 == 1 ||
+                         (sc.seg_blocks * BS < ((size_t)1 << 30) &&
+                          eq_pass_takes_wave_ring(ss, cs, (long long)n_blocks * BS, (int)e.chains, (int)count_on(runs[0].tab), e.exact_specials)));
+    if (!single && ev_start) HIP_TRY(hipEventRecord(ev_start, st));
+    for (const Group &g : groups) {
+        const unsigned t0 = runs[g.r0].tab;
+        const size_t on = count_on(t0);
+        const size_t gb0 = runs[g.r0].b0, gb1 = runs[g.r1 - 1].b1;
+        const long long off = (long long)(gb0 - blk0) * BS, n = (long long)(gb1 - gb0) * BS;
+        if (on == 0) {      // identity: the frames still have to arrive in `out`
+            if (out != in) {
+                if (e.chains == 2 || ss == 2 * cs) {
+                    HIP_TRY(hipMemcpy2DAsync(out + off, (size_t)cs * sizeof(float), in + off, (size_t)cs * sizeof(float),
+                                             (size_t)n * sizeof(float), e.chains, hipMemcpyDeviceToDevice, st));
+                } else {
+                    for (size_t s = 0; s < e.chains / 2; ++s)
+                        HIP_TRY(hipMemcpy2DAsync(out + (long long)s * ss + off, (size_t)cs * sizeof(float), in + (long long)s * ss + off,
+                                                 (size_t)cs * sizeof(float), (size_t)n * sizeof(float), 2, hipMemcpyDeviceToDevice, st));
+                }
+            }
+            continue;
+        }
+        if (g.r1 - g.r0 > 1 && sc.seg_blocks * BS < ((size_t)1 << 30) &&
+            eq_pass_takes_wave_ring(ss, cs, n, (int)e.chains, (int)on, e.exact_specials)) {
+            EqPassTable t;
+            std::memset(&t, 0, sizeof(t));
+            int nbp = 0;
+            size_t last = 0;
+            for (size_t b = 0; b < e.nb; ++b) {
+                if (!e.sched_en[t0 * e.nb + b]) continue;
+                const float *c = &e.sched_coeffs[(t0 * e.nb + b) * 5];
+                t.slot[nbp] = (int)b;
+                t.b0[nbp] = c[0]; t.b1[nbp] = c[1]; t.b2[nbp] = c[2]; t.a1[nbp] = c[3]; t.a2[nbp] = c[4];
+                last = b; ++nbp;
+            }
+            for (int j = nbp; j < 16; ++j) t.slot[j] = (int)last;      // (unused lanes shadow the last band's slot, never stored)
+            EqRingSched sch;
+            sch.lane_tabs = e.d_sched_lanes; sch.seg_tab = sc.d_tab; sch.n_segs = (int)sc.n_segs;
+            sch.seg_len = (int)(sc.seg_blocks * BS);
+            sch.seg0 = (int)(gb0 / sc.seg_blocks); sch.off0 = (int)((gb0 % sc.seg_blocks) * BS);
+            int xcd_lo = e.xcd_lo, xcd_n = e.xcd_n;
+            if (tuning().eq_xcd_n > 0) { xcd_lo = tuning().eq_xcd_lo; xcd_n = tuning().eq_xcd_n; }
+            hipError_t err = launch_eq_ring_sched(in + off, out + off, ss, cs, n, (int)e.chains, t, nbp, e.d_state, sch, st, e.fp_mode,
+                                                  xcd_lo, xcd_n, single ? ev_start : nullptr, single ? ev_stop : nullptr, e.d_stamps);
+            if (err != hipSuccess) return fail(OHS_ERR_HIP, std::string("eq launch (scheduled): ") + hipGetErrorString(err));
+            e.last_form = OHS_EQ_FORM_WAVE_RING;
+            e.last_scheduled = true;
+            continue;
+        }
+        for (size_t r = g.r0; r < g.r1; ++r) {
+            const long long roff = (long long)(runs[r].b0 - blk0) * BS, rn = (long long)(runs[r].b1 - runs[r].b0) * BS;
+            const unsigned t = runs[r].tab;
+            int rc = eq_launch_table(e, &e.sched_coeffs[(size_t)t * e.nb * 5], &e.sched_en[(size_t)t * e.nb], nullptr, e.chains, e.d_state,
+                                     in + roff, out + roff, ss, cs, rn, st, nullptr, single ? ev_start : nullptr,
+                                     single ? ev_stop : nullptr);
+            if (rc) return rc;
+        }
+    }
+    if (!single && ev_stop) HIP_TRY(hipEventRecord(ev_stop, st));
     return OHS_OK;
 }
 

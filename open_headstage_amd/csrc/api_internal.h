@@ -242,9 +242,16 @@ bool conv_plan_auto_is_xb(size_t S, long long n_blocks, int Pmax);      // ... a
 int conv_os_chunks(const DeviceCtx *ctx, size_t S, long long n_blocks, bool in_place);
 // time chunks per stream of the one-partition kernel's launch plan (also what ohs_batch_kernel_bytes prices)
 long long conv_p1_chunks(const DeviceCtx *ctx, size_t S, long long n_blocks, long long target_override, int xcd_n = 8);
+// a gain per segment of seg_blocks blocks (device memory): block t of the launch, block blk_off + t of the call, leaves with
+// tab[(blk_off + t) / seg_blocks].  NULL (or tab == NULL): the scalar `gain`.
+struct ConvGains {
+    const float *tab = nullptr;
+    int seg_blocks = 1, blk_off = 0;
+};
 int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
                 float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st,
-                bool allow_fast = true, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+                bool allow_fast = true, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
+                const ConvGains *gains = nullptr);
 
 // ---- speaker angles -> four set_ir (the wiring the reference leaves open; speakers.cpp) ---------
 template <class SetIr>
@@ -288,6 +295,26 @@ struct EqState {
     bool stabs_dirty = true;
     size_t max_enabled = 0;              // largest number of enabled bands of any stream (as of the last upload scan)
     unsigned long long *d_stamps = nullptr;     // [4] clock stamps of the last ring launch's wave 0 (ohs_batch_set_profiling)
+    // what served the last EQ launch (ohs_batch_last_eq_form): OHS_EQ_FORM_*, and whether it was k_eq_ring_sched
+    int last_form = 0;
+    bool last_scheduled = false;
+    // Schedule tables (ohs_batch_set_schedule_tables): host copies [n][nb][5] / [n][nb], and for the scheduled wave ring every
+    // table's lane constants, compacted by its own enabled flags (kernels.h: EqRingSched::lane_tabs, [n][5][16]; a table with
+    // no or more than 12 enabled bands never reaches that kernel, its entry is the pass-on lane's constants)
+    size_t sched_n = 0;
+    std::vector<float> sched_coeffs;
+    std::vector<unsigned char> sched_en;
+    float *d_sched_lanes = nullptr;
+};
+
+// One scheduled batch call, as the launches see it: segment k = blocks [k seg_blocks, (k + 1) seg_blocks) of the call.  tab / gain
+// are the caller's host arrays (either may be NULL: the handle's table / gain throughout), d_tab / d_gain their device copies.
+struct BatchSchedule {
+    size_t seg_blocks = 1, n_segs = 0;
+    const unsigned *tab = nullptr;
+    const float *gain = nullptr;
+    const unsigned *d_tab = nullptr;
+    const float *d_gain = nullptr;
 };
 
 
@@ -301,6 +328,11 @@ void eq_share_table(EqState &e);            // back to the one shared table
 void eq_free(EqState &e);
 int eq_launch(EqState &e, const float *in, float *out, long long ss, long long cs, long long n,
               hipStream_t st, bool *did_anything = nullptr, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+int eq_set_schedule_tables(EqState &e, size_t n_tables, const float *coeffs, const uint8_t *enabled, hipStream_t st);
+bool eq_schedule_table_any_enabled(const EqState &e, size_t table);
+// the cascade over blocks [blk0, blk0 + n_blocks) of a scheduled call (shared table only; sc.tab != NULL); in / out point at blk0
+int eq_launch_scheduled(EqState &e, const BatchSchedule &sc, size_t blk0, size_t n_blocks, const float *in, float *out,
+                        long long ss, long long cs, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);
 
 // ---- growable planar device FIFO [2][cap] (api_engine.hip) -----------------------------
 struct DevFifo {
@@ -406,4 +438,16 @@ struct ohs_batch {
     hipStream_t st_h2d = nullptr, st_comp = nullptr, st_d2h = nullptr;
     hipEvent_t ev_h2d[kHostSlots] = {nullptr, nullptr, nullptr}, ev_comp[kHostSlots] = {nullptr, nullptr, nullptr},
                ev_d2h[kHostSlots] = {nullptr, nullptr, nullptr};
+    // ohs_batch_process_scheduled: the call's schedule travels through one of kSchedSlots staging slots -- pinned host memory
+    // (the caller's arrays are free on return, the copy to the device is asynchronous) and its device copy, [cap] table indices
+    // then [cap] gains; `done` is recorded behind the call that used the slot and waited for before the slot is filled again
+    static constexpr int kSchedSlots = 4;
+    struct SchedSlot {
+        unsigned *h = nullptr, *d = nullptr;
+        size_t cap = 0;
+        hipEvent_t done = nullptr;
+        bool in_use = false;
+    };
+    SchedSlot sched_slot[kSchedSlots];
+    int sched_next = 0;
 };

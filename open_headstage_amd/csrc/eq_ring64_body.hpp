@@ -25,6 +25,21 @@
 //   sample i is in lane 0 at step i + 1, filtered by band L (post lane L + 1) at step i + L + 2, whatever the number of
 //   bands it reaches lane 16 + m at step i + 17 + m; the port behind step 48 (g + 1) finds sample 48 g + 47 - l in lane
 //   l >= 16: outputs leave 16 samples behind the inputs that replace them.
+//
+// Coefficient boundaries inside a launch (the SCHED form: k_eq_ring_sched, ohs_batch_process_scheduled).  Sample B is the first
+// one of a new table: every band takes five new constants and keeps s1, s2 (update_coefficients, parametric_eq.rs:85-114).
+// The ring is systolic, so the boundary reaches the lanes one after the other.  Band L filters sample B in step B + L + 2 on
+// its post lane L + 1 (O T A N); the P that feeds that step ran in step B + L + 1 on its pre lane L, the M in step B + L + 1 on
+// lane L + 1.  Per lane l:
+//   a1, a2    new from the A of step B + l + 1
+//   pb0, pb1  new from the P of step B + l + 1
+//   b2        new from the M of step B + l
+// i.e. in step t lane t - B - 1 takes its new (pb0, pb1, a1, a2) in front of A, and lane t - B its new b2 in front of M.  Lane 0
+// has no b2, so all of it happens in steps B + 1 .. B + 13, and with B a multiple of 512 (B mod 48 = 0, 16 or 32) these lie in
+// ONE group, group B / 48, which runs in the C++ form; the groups around it run through eq_ring64_groups unchanged (its
+// constants are asm inputs).  tools/model_eq_wave_ring.py is the lane-level CPU model that confirms the rule bit for bit
+// against the oracle refreshed per segment (tests/test_cpu_schedule.py).  Segments are >= 512 samples: at most one boundary
+// is in the ring at a time.  The next table's constants are requested in front of the asm run that leads up to the boundary.
 #pragma once
 #include "kernels.h"
 #include "eq_ring2_body.hpp"    // v2f, dpp helpers, RingLane, ring2_ld / ring2_st
@@ -167,10 +182,12 @@ __device__ __forceinline__ void eq_ring64_groups(const RingLane &c, Ring64Regs &
 
 // PER_STREAM: the chain's stream owns its bands (parametric_eq.rs:125-129) -- constants, state slots and the NUMBER of enabled
 // bands come from stabs[chain / 2] (kernels.h: EqStreamTable) instead of the launch's one table.
-template <bool PER_STREAM>
+// SCHED: the launch's table changes at segment boundaries (kernels.h: EqRingSched; the rule in the header comment).
+template <bool PER_STREAM, bool SCHED = false>
 __device__ __forceinline__ void eq_ring64_wave_t(const float *in, float *out, long long stream_stride, long long ch_stride,
                                                  long long n, int n_chains, int nb_shared, const EqPassTable &tab,
-                                                 const EqStreamTable *__restrict__ stabs, float *__restrict__ state, long long chain)
+                                                 const EqStreamTable *__restrict__ stabs, float *__restrict__ state, long long chain,
+                                                 const EqRingSched *sch = nullptr)
 {
     constexpr int G = kR64Group;
     if (chain >= n_chains) return;
@@ -220,9 +237,15 @@ __device__ __forceinline__ void eq_ring64_wave_t(const float *in, float *out, lo
     ring64_pm(r, c);
     // one group in the C++ form: the launch's first group (the bands' states arrive), its last ones (they leave; loads
     // and stores are checked against n)
+    constexpr int kNoBoundary = 0x3fffffff;
+    [[maybe_unused]] int bnd = kNoBoundary;         // SCHED: the boundary the group meets (its sample index), c_new its constants
+    [[maybe_unused]] RingLane c_new = c;
     auto group_cpp = [&](int g) {
         auto step = [&](int k, bool port) {
             const int stp = g * G + k + 1;
+            if constexpr (SCHED) {
+                if (lane == stp - bnd - 1) { c.pb0 = c_new.pb0; c.pb1 = c_new.pb1; c.a1 = c_new.a1; c.a2 = c_new.a2; }
+            }
             const float o = dpp_mov<kWaveRor1>(r.u.x, r.u.x) + r.s.x;           // O
             const float t2 = dpp_mov<kWaveRor1>(r.u.y, r.u.y) + r.s.y;          // T
             r.X = o;
@@ -235,6 +258,9 @@ __device__ __forceinline__ void eq_ring64_wave_t(const float *in, float *out, lo
                 xnext = load_group(g + 2);
             }
             const v2f sn = {t2 - ao.x, r.b2x - ao.y};                           // N (with the previous step's M)
+            if constexpr (SCHED) {
+                if (lane == stp - bnd) c.b2 = c_new.b2;
+            }
             ring64_pm(r, c);                                                    // P, M
             r.s = sn;
             if (band && lane == stp) r.s = s_init;          // behind step L + 1: band L's first sample is next
@@ -250,7 +276,40 @@ __device__ __forceinline__ void eq_ring64_wave_t(const float *in, float *out, lo
     // groups 1 .. n / 48 - 1 in asm: every step filters existing samples (the last of them ends at step 48 (n / 48) <= n: the
     // first state leaves behind step n + 1), every store lands below n; the one or two groups behind them run in the C++ form
     const int n_full = n32 / G;
-    if (n_full >= 2) {
+    if constexpr (SCHED) {
+        // groups g .. g_end - 1 (1 <= g, g_end <= n_full) in asm; xnext holds group g + 1's inputs on entry and g_end + 1's on exit
+        auto run_asm = [&](int g_end) {
+            if (g_end <= g) return;
+            const float xnext2 = load_group(g + 2);
+            const unsigned bytes = (unsigned)n32 * 4u;
+            eq_ring64_groups(c, r, xnext, xnext2, conv ? (unsigned)(g * G + 47 - lane) * 4u : 0xFFFFF000u, conv ? 4u * G * 4u : 0u,
+                             ring64_rsrc(src0, bytes), ring64_rsrc(dst0, bytes), g_end - g);
+            g = g_end;
+        };
+        // the launch starts off0 samples into segment seg0; segment seg0 + j starts at sample j * seg_len - off0
+        const int n_segs = sch->n_segs, seg_len = sch->seg_len;
+        unsigned cur = (unsigned)__builtin_amdgcn_readfirstlane((int)sch->seg_tab[sch->seg0]);
+        int B = seg_len - sch->off0;
+#pragma unroll 1
+        for (int seg = sch->seg0 + 1; seg < n_segs && B < n32; ++seg, B += seg_len) {
+            const unsigned t = (unsigned)__builtin_amdgcn_readfirstlane((int)sch->seg_tab[seg]);
+            if (t == cur) continue;             // (consecutive segments with one table are one run)
+            cur = t;
+            const int gb = B / G;               // the group of steps B + 1 .. B + 13
+            if (gb < g || gb + 1 > n_full) continue;    // (never: boundaries are multiples of 512 in [512, n - 512])
+            if (lane < 16) {                    // requested here, needed behind the asm run
+                const float *lt = sch->lane_tabs + (size_t)t * (5 * 16) + lane;
+                c_new.pb0 = lt[0]; c_new.pb1 = lt[16]; c_new.b2 = lt[32]; c_new.a1 = lt[48]; c_new.a2 = lt[64];
+            }
+            run_asm(gb);
+            bnd = B;
+            group_cpp(gb);
+            bnd = kNoBoundary;
+            c = c_new;
+            g = gb + 1;
+        }
+        run_asm(n_full);
+    } else if (n_full >= 2) {
         const float xnext2 = load_group(3);         // (zeros beyond n)
         const unsigned bytes = (unsigned)n32 * 4u;
         eq_ring64_groups(c, r, xnext, xnext2, conv ? (unsigned)(G + 47 - lane) * 4u : 0xFFFFF000u, conv ? 4u * G * 4u : 0u,

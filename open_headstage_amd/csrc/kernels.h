@@ -40,6 +40,18 @@ struct EqStreamTable {
     int nb;                     // enabled bands, 0 .. 12
     int pad[3];
 };
+// A launch of the wave ring whose table changes at segment boundaries (ohs_batch_process_scheduled; eq_ring64_body.hpp).
+// lane_tabs: device [n_tables][5][16], the constants of lanes 0 .. 15 per table -- {pb0, pb1} of the enabled band the lane is pre
+// lane of, {b2, a1, a2} of the one it is post lane of, (1, 0, 0, 0, 0) where it is neither -- i.e. every table compacted by its
+// own enabled mask; all tables a launch meets have the SAME mask (the host ends a launch where the mask changes).
+// seg_tab: device [n_segs], the table index of every segment of the call.  The launch starts off0 samples into segment seg0.
+struct EqRingSched {
+    const float *lane_tabs;
+    const unsigned *seg_tab;
+    int n_segs;
+    int seg_len;                // samples per segment, a multiple of 512
+    int seg0, off0;             // off0 a multiple of 512, < seg_len
+};
 constexpr int kEqStateSlots = 64;       // = OHS_MAX_EQ_BANDS
 // chains = streams * 2 (L, R); chain c -> stream c>>1, channel c&1.
 // state: [chain][kEqStateSlots][2] (s1, s2), indexed by the band's own index.
@@ -50,7 +62,18 @@ constexpr int kEqStateSlots = 64;       // = OHS_MAX_EQ_BANDS
 hipError_t launch_eq_pass(const float *in, float *out, long long stream_stride, long long ch_stride,
                           long long n, int n_chains, const EqPassTable &tab, int n_bands, float *state,
                           hipStream_t st, bool exact_specials = false, int fp_mode = 0, int xcd_lo = 0, int xcd_n = 8,
-                          hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, unsigned long long *stamps = nullptr);
+                          hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, unsigned long long *stamps = nullptr,
+                          int *form = nullptr);
+// (form, optional: which form served the launch, OHS_EQ_FORM_* of ohs_hip.h)
+// whether launch_eq_pass serves such a launch with the wave ring (one chain per wave, eq_ring64_body.hpp)
+bool eq_pass_takes_wave_ring(long long stream_stride, long long ch_stride, long long n, int n_chains, int n_bands,
+                             bool exact_specials);
+// The wave ring with a table schedule (k_eq_ring_sched): `tab` is the table of the launch's first sample, the others come from
+// `sch`.  Only where eq_pass_takes_wave_ring holds and n is a multiple of 512; everything else about the launch as launch_eq_pass.
+hipError_t launch_eq_ring_sched(const float *in, float *out, long long stream_stride, long long ch_stride, long long n,
+                                int n_chains, const EqPassTable &tab, int n_bands, float *state, const EqRingSched &sch,
+                                hipStream_t st, int fp_mode, int xcd_lo, int xcd_n, hipEvent_t ev_start, hipEvent_t ev_stop,
+                                unsigned long long *stamps);
 // (stamps, optional, device memory [4]: wave 0 of a RING launch writes {real-time counter at start, at end, shader-clock
 // counter at start, at end}: s_memrealtime runs at 100 MHz, s_memtime at the shader clock)
 // (ev_start / ev_stop: recorded at the start / completion of THIS launch.  The ring kernel's dispatch carries them
@@ -60,7 +83,8 @@ hipError_t launch_eq_pass(const float *in, float *out, long long stream_stride, 
 // the ring form with one table per stream: d_tabs[n_chains / 2] in device memory (every stream <= 12 enabled bands)
 hipError_t launch_eq_ring_streams(const float *in, float *out, long long stream_stride, long long ch_stride, long long n,
                                   int n_chains, const EqStreamTable *d_tabs, float *state, hipStream_t st, int fp_mode = 0,
-                                  int xcd_lo = 0, int xcd_n = 8, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+                                  int xcd_lo = 0, int xcd_n = 8, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
+                                  int *form = nullptr);
 bool eq_ring_addressable(long long stream_stride, long long ch_stride, long long n);     // the strides the ring form reaches
 
 // |H(f)| of the enabled bands (parametric_eq.rs:190-209); coeffs [nb][5], en [nb]
@@ -186,6 +210,11 @@ struct ConvP1Args {
     float *last_in;
     int own_tails;              // 1: no boundary-tail pre-pass, every wave runs one dry block in front of its chunk (chunks 2, 4, 8 or
                                 // 16: all chunks of a stream in one workgroup -- p1_wave_job); 0: k_conv_p1_edges fills chunk_tails
+    // (behind the fields k_conv_p1 has always had, whose offsets stay)  A gain per segment (ohs_batch_process_scheduled): gain_tab != nullptr -- block t of the launch is stored with
+    // gain_tab[(gain_off + t) / gain_seg] (device memory; gain_off = the launch's first block within the call, gain_seg = blocks per
+    // segment) by k_conv_p1_gains; nullptr: `gain`, by k_conv_p1
+    const float *gain_tab = nullptr;
+    int gain_seg = 1, gain_off = 0;
 };
 // (ev_start / ev_stop, optional: recorded at the start / completion of the launches; carried by the dispatch itself when
 // the call is a single kernel -- see launch_eq_pass)
@@ -402,6 +431,10 @@ hipError_t launch_zero_tail_component(float2 *tails, long long n_streams, int wh
 hipError_t launch_debug_fft(const float2 *in, float2 *out, int inverse, int batch, const float2 *tw,
                             hipStream_t st);
 
+// the families without a gain table of their own: out (s, ch, i) *= gain_tab[(gain_off + i / 512) / gain_seg] for the n_blocks * 512
+// frames of every chain, behind a launch that ran with gain 1
+hipError_t launch_scale_segments(float *out, long long stream_stride, long long ch_stride, int n_blocks, int n_streams,
+                                 const float *gain_tab, int gain_seg, int gain_off, hipStream_t st, int fp_mode = 0);
 // dst[i] = src[i] * gain  (n floats)
 hipError_t launch_scale_copy(const float *src, float *dst, long long n, float gain, hipStream_t st, int fp_mode = 0);
 hipError_t launch_scale_copy_done(const float *src, float *dst, long long n, float gain, unsigned *counter, unsigned *done,

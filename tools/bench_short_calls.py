@@ -5,6 +5,10 @@ events around a run of back-to-back calls on one stream (so launch gaps between 
 enqueue time does not unless it is the bound), and host wall time per call beside it.  One JSON line per call size.
 
     python tools/bench_short_calls.py [--streams 64] [--taps 16384] [--plan 0]
+
+--eq: the reference's cadence through the existing setters -- ten bands on, and in front of EVERY call a changed table (ten
+ohs_batch_set_eq_band_coeffs) and a changed gain (ohs_batch_set_gain), as a host that refreshes per block does.  The per-segment
+call loop ohs_batch_process_scheduled replaces; `--streams 256 --taps 512 --sizes 2 --eq` is the headline's shape.
 """
 import argparse
 import json
@@ -26,6 +30,7 @@ def main():
     ap.add_argument("--taps", type=int, default=16384)
     ap.add_argument("--plan", type=int, default=0)
     ap.add_argument("--sizes", type=str, default="1,2,3,4,8,32,256")
+    ap.add_argument("--eq", action="store_true", help="ten bands on; a changed table and gain in front of every call")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     S = a.streams
@@ -33,8 +38,25 @@ def main():
     irs = synth.hrir_set(a.taps)
     for p in range(4):
         bp.set_ir(p, irs[p])
-    bp.set_eq_enabled(False)
+    bp.set_eq_enabled(a.eq)
     bp.set_conv_plan(a.plan)
+    tables = []
+    if a.eq:        # six ten-band tables whose coefficients all differ
+        bands = synth.eq_table()
+        for t in range(6):
+            tables.append([ohs.biquad_coefficients(b.filter_type, synth.FS, b.center_freq * (1.0 + 0.01 * t), b.q, b.gain_db - 0.1 * t)
+                           for b in bands])
+        for i, c in enumerate(tables[0]):
+            bp.set_band_coeffs(i, c, True)
+    turn = [0]
+
+    def call(xs, ys):
+        if a.eq:
+            turn[0] += 1
+            for i, c in enumerate(tables[turn[0] % 6]):
+                bp.set_band_coeffs(i, c, True)
+            bp.set_gain(0.5 + 0.01 * (turn[0] % 32))
+        bp.process(xs, out=ys)
     frames_total = 256 * 512
     x = synth.white_noise_torch(0, S, frames_total, dev)
     y = torch.empty_like(x)
@@ -49,19 +71,20 @@ def main():
         xs = x[:, :, :n].contiguous()
         ys = torch.empty_like(xs)
         for _ in range(3):
-            bp.process(xs, out=ys)
+            call(xs, ys)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
         e0.record(st)
         for _ in range(calls):
-            bp.process(xs, out=ys)
+            call(xs, ys)
         e1.record(st)
         t_host = time.perf_counter() - t0
         torch.cuda.synchronize()
         t_wall = time.perf_counter() - t0
         dev_us = e0.elapsed_time(e1) * 1e3 / calls
-        rec = {"streams": S, "taps": a.taps, "plan": a.plan, "blocks_per_call": nb, "calls": calls,
+        rec = {"streams": S, "taps": a.taps, "plan": a.plan, "eq": bool(a.eq), "blocks_per_call": nb, "calls": calls,
+               "msamples_per_s": round(S * n / dev_us, 1),
                "device_us_per_call": round(dev_us, 2), "host_enqueue_us_per_call": round(t_host * 1e6 / calls, 2),
                "wall_us_per_call": round(t_wall * 1e6 / calls, 2),
                "us_per_block": round(dev_us / nb, 3)}
