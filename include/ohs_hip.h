@@ -422,7 +422,30 @@ int  ohs_batch_set_schedule_tables(ohs_batch *b, size_t n_tables, const float *c
 int  ohs_batch_process_scheduled(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
                                  size_t channel_stride, size_t seg_blocks, const unsigned *table_idx, const float *gain,
                                  void *hip_stream);
-/* which form of the EQ cascade served the handle's last EQ launch, and whether it was the scheduled kernel (tables changing
+/* The same with a schedule PER STREAM: every stream of the batch is a plugin instance of its own, with its own automation.
+ * Segments as above.  Stream s filters segment k with table table_idx[s * idx_stride + k] (of the set uploaded by
+ * ohs_batch_set_schedule_tables) and its frames leave the convolution with gain[s * gain_stride + k].  Host arrays, reusable on
+ * return.  A stride is 0 (one row of n_segments entries for all streams) or >= n_segments.  table_idx == NULL: the handle's
+ * current table(s) throughout -- also on a handle with static per-stream tables (ohs_batch_set_stream_eq_band_coeffs): a gain
+ * schedule per stream over those tables; gain == NULL: the handle's gain throughout.  At a boundary a band takes its five new
+ * constants and keeps s1, s2; the enabled flags become the new table's; a disabled band hands its input on and keeps its state
+ * -- the semantics of ohs_batch_process_scheduled, per stream, with the same result as one handle per stream driven by the
+ * setters and ohs_batch_process per segment (bit for bit under plan 1 with taps <= 512).
+ * The schedule governs THIS call only: afterwards the handle's own table(s) and gain are what they were before the call (there
+ * is no per-stream gain on the handle to adopt into) -- unlike ohs_batch_process_scheduled.  EQ state, history, overlaps and
+ * pending tails carry over in both directions; plain, scheduled and per-stream scheduled calls may be mixed freely.
+ * idx_stride == 0 with gain_stride == 0 computes the bits of ohs_batch_process_scheduled for the same rows.
+ * OHS_ERR_INVALID_ARG, before anything is queued (the handle stays usable): NULL handle or buffers, seg_blocks == 0, an index out
+ * of range in any row, a non-zero stride below n_segments, table_idx with no tables uploaded, table_idx on a handle with static
+ * per-stream tables, strides smaller than the processed region.
+ * Where the wave-ring EQ form serves the call, one EQ launch covers a span of segments in which no stream's enabled flags
+ * change: every stream's coefficients change inside it at that stream's own boundaries (ohs_batch_last_eq_form: scheduled = 1).
+ * Where any stream's flags change the launch ends for all streams; every other EQ form is one launch sequence for all streams
+ * per span of segments in which no stream's index changes. */
+int  ohs_batch_process_scheduled_streams(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
+                                         size_t channel_stride, size_t seg_blocks, const unsigned *table_idx, size_t idx_stride,
+                                         const float *gain, size_t gain_stride, void *hip_stream);
+/* which form of the EQ cascade served the handle's last EQ launch, and whether it was one of the two scheduled kernels (tables changing
  * inside the launch) */
 enum {
     OHS_EQ_FORM_NONE = 0,       /* no EQ launch yet */

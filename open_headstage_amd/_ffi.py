@@ -129,6 +129,8 @@ PROTOTYPES = {
     "ohs_batch_set_schedule_tables": (C.c_int, [vp, C.c_size_t, fp, C.POINTER(C.c_uint8)]),
     "ohs_batch_process_scheduled": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                               C.POINTER(C.c_uint32), fp, vp]),
+    "ohs_batch_process_scheduled_streams": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                    C.POINTER(C.c_uint32), C.c_size_t, fp, C.c_size_t, vp]),
     "ohs_batch_last_eq_form": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ohs_batch_join": (C.c_int, [vp, vp]),
     "ohs_batch_sync": (C.c_int, [vp, vp]),

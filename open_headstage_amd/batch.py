@@ -181,6 +181,53 @@ class BatchProcessor:
                                    table_idx, gains, hip_stream)
         return out
 
+    def process_scheduled_streams_ptr(self, d_in: int, d_out: int, n_blocks: int, stream_stride: int, channel_stride: int,
+                                      seg_blocks: int, table_idx=None, gains=None, hip_stream: int = 0) -> None:
+        """ohs_batch_process_scheduled_streams: a schedule per stream.  table_idx [n_streams][n_segs] (or [n_segs]: one row for
+        all streams), likewise gains; stream s filters segment k with table table_idx[s][k] and leaves with gains[s][k].  None =
+        the handle's table(s) / gain throughout.  The handle's own table(s) and gain are unchanged by the call."""
+        n_segs = -(-int(n_blocks) // int(seg_blocks)) if seg_blocks else 0
+
+        def rows(a, dtype, what):
+            if a is None:
+                return None, 0
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.ndim == 1:
+                if a.size < n_segs:
+                    raise ValueError(f"{what} needs {n_segs} entries")
+                return a, 0
+            if a.ndim != 2 or a.shape[0] != self.n_streams or a.shape[1] < n_segs:
+                raise ValueError(f"{what}: expected [{self.n_streams}][>= {n_segs}] or [>= {n_segs}], got {a.shape}")
+            return a, int(a.shape[1])
+
+        t, ts = rows(table_idx, np.uint32, "table_idx")
+        g, gs = rows(gains, np.float32, "gains")
+        self._check(self._lib.ohs_batch_process_scheduled_streams(
+            self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(stream_stride), int(channel_stride), int(seg_blocks),
+            t.ctypes.data_as(C.POINTER(C.c_uint32)) if t is not None else None, ts,
+            g.ctypes.data_as(fp) if g is not None else None, gs, C.c_void_p(hip_stream) if hip_stream else None))
+
+    def process_scheduled_streams(self, x, seg_blocks: int, table_idx=None, gains=None, out=None, hip_stream: int | None = None):
+        """process() with a schedule of EQ tables and gains per stream and segment of seg_blocks * 512 frames: every stream a
+        plugin instance whose host refreshes its bands and its master gain in front of every block.  x, out as in process()."""
+        import torch
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, 2, frames]")
+        S, ch, frames = x.shape
+        if S != self.n_streams or ch != 2 or frames % BLOCK_SIZE:
+            raise ValueError(f"expected [{self.n_streams}, 2, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
+        if x.device.index != self.device:
+            raise ValueError("tensor is on a different device than the BatchProcessor")
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+            raise ValueError("out must match x")
+        if hip_stream is None:
+            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+        self.process_scheduled_streams_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, 2 * frames, frames, seg_blocks,
+                                           table_idx, gains, hip_stream)
+        return out
+
     def join(self, hip_stream: int | None = None) -> None:
         """Make `hip_stream` (default: torch's current stream) wait for a pending deferred call."""
         if hip_stream is None:

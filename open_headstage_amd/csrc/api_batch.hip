@@ -330,10 +330,13 @@ static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, siz
     bool eq_active = b->eq_enable && eq_any_enabled(b->eq);
     if (sched_tabs) {
         eq_active = false;
-        for (size_t k = 0; k < sc->n_segs && b->eq_enable && !eq_active; ++k) eq_active = eq_schedule_table_any_enabled(b->eq, sc->tab[k]);
+        const size_t rows = sc->tab_stride ? b->conv.S : 1;
+        for (size_t r = 0; r < rows && b->eq_enable && !eq_active; ++r)
+            for (size_t k = 0; k < sc->n_segs && !eq_active; ++k)
+                eq_active = eq_schedule_table_any_enabled(b->eq, sc->tab[r * sc->tab_stride + k]);
     }
     ConvGains cg;
-    if (sc && sc->d_gain) { cg.tab = sc->d_gain; cg.seg_blocks = (int)sc->seg_blocks; }
+    if (sc && sc->d_gain) { cg.tab = sc->d_gain; cg.seg_blocks = (int)sc->seg_blocks; cg.stream_stride = (int)sc->gain_stride; }
 
     const long long ss = (long long)stream_stride, cs = (long long)channel_stride;
     int rc;
@@ -416,7 +419,9 @@ static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, siz
             b->ev_inflight.push_back(ev_b);
         }
         // (the time chunks cut at block positions that need not be segment boundaries: every launch is told where it starts)
-        if (sched_tabs) rc = eq_launch_scheduled(b->eq, *sc, blk0, (size_t)nb_i, d_in + off, d_out + off, ss, cs, st, ev_a, ev_b);
+        if (sched_tabs && sc->streams)
+            rc = eq_launch_scheduled_streams(b->eq, *sc, blk0, (size_t)nb_i, d_in + off, d_out + off, ss, cs, st, ev_a, ev_b);
+        else if (sched_tabs) rc = eq_launch_scheduled(b->eq, *sc, blk0, (size_t)nb_i, d_in + off, d_out + off, ss, cs, st, ev_a, ev_b);
         else rc = eq_launch(b->eq, d_in + off, d_out + off, ss, cs, (long long)nb_i * BS, st, nullptr, ev_a, ev_b);
         if (rc) return rc;
         hipStream_t cst = st;
@@ -574,6 +579,125 @@ int ohs_batch_process_scheduled(ohs_batch *b, const float *d_in, float *d_out, s
     if (table_idx) adopt_table(table_idx[n_segs - 1]);
     if (gain) b->gain = gain[n_segs - 1];
     return OHS_OK;
+}
+
+int ohs_batch_process_scheduled_streams(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
+                                        size_t channel_stride, size_t seg_blocks, const unsigned *table_idx, size_t idx_stride,
+                                        const float *gain, size_t gain_stride, void *hip_stream)
+{
+    if (!b || !d_in || !d_out) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    if (seg_blocks == 0) return fail(OHS_ERR_INVALID_ARG, "seg_blocks is 0");
+    if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
+    if (table_idx && b->eq.per_stream)
+        return fail(OHS_ERR_INVALID_ARG, "table_idx on a handle with static per-stream EQ tables is not supported: the schedule "
+                                         "tables take their place (ohs_batch_share_eq_table), or pass table_idx = NULL");
+    if (table_idx && b->eq.sched_n == 0)
+        return fail(OHS_ERR_INVALID_ARG, "table_idx given, but no tables uploaded (ohs_batch_set_schedule_tables)");
+    seg_blocks = std::min(seg_blocks, std::max<size_t>(n_blocks, 1));
+    const size_t n_segs = (n_blocks + seg_blocks - 1) / seg_blocks, S = b->conv.S;
+    if ((table_idx && idx_stride != 0 && idx_stride < n_segs) || (gain && gain_stride != 0 && gain_stride < n_segs))
+        return fail(OHS_ERR_INVALID_ARG, "a row stride is 0 (one row for all streams) or >= the number of segments");
+    if (S * n_segs > (size_t)0x7fffffff) return fail(OHS_ERR_INVALID_ARG, "schedule too large");
+    if (!table_idx) idx_stride = 0;
+    if (!gain) gain_stride = 0;
+    BatchSchedule sc;
+    sc.seg_blocks = seg_blocks; sc.n_segs = n_segs; sc.streams = true;
+    if (table_idx) {        // one pass over the caller's rows: the range check, and what the EQ launches have to know about the segments
+        sc.tab = table_idx; sc.tab_stride = idx_stride;
+        if (!eq_schedule_streams_scan(b->eq, sc)) return fail(OHS_ERR_INVALID_ARG, "table_idx entry out of range");
+    }
+    if (b->failed || n_blocks == 0)     // (the plain call's answers)
+        return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
+    {
+        const size_t frames = n_blocks * BS;
+        if (channel_stride < frames || (S > 1 && stream_stride < 2 * frames && stream_stride < channel_stride + frames))
+            return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
+    }
+    // rows that are all the same are one row
+    auto rows_equal = [&](const void *base, size_t stride) {
+        const unsigned *p = static_cast<const unsigned *>(base);      // (gains compare as bits)
+        for (size_t s = 1; s < S; ++s)
+            if (std::memcmp(p + s * stride, p, n_segs * sizeof(unsigned)) != 0) return false;
+        return true;
+    };
+    if (idx_stride && rows_equal(table_idx, idx_stride)) idx_stride = 0;
+    if (gain_stride && rows_equal(gain, gain_stride)) gain_stride = 0;
+    // The schedule governs this call only: what the handle holds is put back behind it, whatever the call returns.
+    struct Restore {
+        ohs_batch *b;
+        std::vector<float> coeffs; std::vector<int> en; float gain;
+        explicit Restore(ohs_batch *b_) : b(b_), coeffs(b_->eq.coeffs), en(b_->eq.en.begin(), b_->eq.en.end()), gain(b_->gain) {}
+        ~Restore()
+        {
+            b->gain = gain;
+            if (!b->eq.per_stream)
+                for (size_t band = 0; band < b->eq.nb; ++band) eq_set_shared_band(b->eq, band, &coeffs[5 * band], en[band]);
+        }
+    } restore(b);
+    // one row of each for all streams: the launches of ohs_batch_process_scheduled (its bits); only the adoption differs
+    if (!idx_stride && !gain_stride && !b->eq.per_stream)
+        return ohs_batch_process_scheduled(b, d_in, d_out, n_blocks, stream_stride, channel_stride, seg_blocks, table_idx, gain, hip_stream);
+    // a constant row of its own kind is the plain call's table / gain
+    auto adopt_table = [&](unsigned t) {
+        for (size_t band = 0; band < b->eq.nb; ++band)
+            eq_set_shared_band(b->eq, band, &b->eq.sched_coeffs[((size_t)t * b->eq.nb + band) * 5], b->eq.sched_en[(size_t)t * b->eq.nb + band]);
+    };
+    if (table_idx && !idx_stride) {
+        bool vary = false;
+        for (size_t k = 1; k < n_segs; ++k) vary = vary || table_idx[k] != table_idx[0];
+        if (!vary) { adopt_table(table_idx[0]); table_idx = nullptr; }
+    }
+    if (gain && !gain_stride) {
+        bool vary = false;
+        for (size_t k = 1; k < n_segs; ++k) vary = vary || std::memcmp(&gain[k], &gain[0], sizeof(float)) != 0;
+        if (!vary) { b->gain = gain[0]; gain = nullptr; }
+    }
+    if (!table_idx && !gain)
+        return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
+
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    // the schedule's staging slot (as ohs_batch_process_scheduled's), here with a row per stream: streams x n_segs entries per array
+    ohs_batch::SchedSlot &slot = b->sched_slot[b->sched_next];
+    b->sched_next = (b->sched_next + 1) % ohs_batch::kSchedSlots;
+    if (slot.in_use) HIP_TRY(hipEventSynchronize(slot.done));
+    slot.in_use = false;
+    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    // (the slot holds 2 * cap entries: here the index rows, packed n_segs apart whatever the caller's stride, and right behind them
+    // the gain rows -- ONE copy to the device)
+    const size_t n_tab = table_idx ? (idx_stride ? S : 1) * n_segs : 0, n_gain = gain ? (gain_stride ? S : 1) * n_segs : 0;
+    if (2 * slot.cap < n_tab + n_gain) {
+        if (slot.h) hipHostFree(slot.h);
+        if (slot.d) {
+            DeviceWideSection dws;
+            hipFree(slot.d);
+        }
+        slot.h = nullptr; slot.d = nullptr; slot.cap = 0;
+        const size_t cap = std::max<size_t>(1024, (n_tab + n_gain) / 2 + (n_tab + n_gain) / 4 + 1);
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&slot.h), 2 * cap * sizeof(unsigned), hipHostMallocDefault));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&slot.d), 2 * cap * sizeof(unsigned)));
+        slot.cap = cap;
+    }
+    auto pack = [&](const void *src, size_t stride, unsigned *h) {
+        const size_t rows = stride ? S : 1;
+        for (size_t s = 0; s < rows; ++s) std::memcpy(h + s * n_segs, static_cast<const unsigned *>(src) + s * stride, n_segs * sizeof(unsigned));
+    };
+    sc.tab = nullptr; sc.tab_stride = 0;
+    if (table_idx) {
+        pack(table_idx, idx_stride, slot.h);
+        sc.tab = slot.h; sc.d_tab = slot.d; sc.tab_stride = idx_stride ? n_segs : 0;
+    }
+    if (gain) {
+        pack(gain, gain_stride, slot.h + n_tab);
+        sc.gain = reinterpret_cast<const float *>(slot.h + n_tab);
+        sc.d_gain = reinterpret_cast<const float *>(slot.d + n_tab);
+        sc.gain_stride = gain_stride ? n_segs : 0;
+    }
+    HIP_TRY(hipMemcpyAsync(slot.d, slot.h, (n_tab + n_gain) * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    const int rc = batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false, &sc);
+    if (hipEventRecord(slot.done, st) == hipSuccess) slot.in_use = true;
+    else hipStreamSynchronize(st);
+    return rc;
 }
 
 int ohs_batch_process_deferred(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,

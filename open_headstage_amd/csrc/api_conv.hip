@@ -16,7 +16,8 @@ struct ConvCall {
     float *out; long long out_ss, out_cs;
     int n_blocks; float gain;
     // a gain per segment instead (ConvGains; device memory): frames of block t leave with tab[(off + t) / seg]
-    const float *gain_tab = nullptr; int gain_seg = 1, gain_off = 0;
+    // (gain_stream: stream s reads its row at gain_tab + s * gain_stream; 0 = one row for all)
+    const float *gain_tab = nullptr; int gain_seg = 1, gain_off = 0, gain_stream = 0;
 };
 
 // right before the handle is deleted: the buffers only
@@ -834,7 +835,7 @@ static int conv_run_p1(ConvState &c, DeviceCtx *ctx, const ConvCall &k, const Co
     a.merged_out = c.lazy_ok ? c.d_merged_alt : nullptr;
     a.last_in = c.lazy_ok ? c.d_last_in : nullptr;
     a.tw = ctx->d_tw; a.gain = k.gain; a.fp_mode = c.fp_mode;
-    a.gain_tab = k.gain_tab; a.gain_seg = k.gain_seg; a.gain_off = k.gain_off;     // (k_conv_p1_gains looks the gain up itself)
+    a.gain_tab = k.gain_tab; a.gain_seg = k.gain_seg; a.gain_off = k.gain_off; a.gain_stream = k.gain_stream;     // (k_conv_p1_gains looks the gain up itself)
     a.xcd_lo = plan.xcd_lo; a.xcd_n = plan.xcd_n;
     {   // boundary tails by the chunks' own waves where a stream's chunks share a workgroup (else: the pre-pass)
         const bool allowed = conv_p1_waves_per_cu() == 16 && (K == 2 || K == 4 || K == 8 || K == 16);
@@ -1031,7 +1032,7 @@ int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, 
     const ConvPlan plan = conv_choose_plan(c, ctx, k, allow_fast);
     int ranges = 0, rc;
     if (plan.kernel == OHS_CONV_KERNEL_BLOCK512_P1) {
-        if (seg_gains && !c.pt_active) { k.gain_tab = gains->tab; k.gain_seg = gains->seg_blocks; k.gain_off = gains->blk_off; }
+        if (seg_gains && !c.pt_active) { k.gain_tab = gains->tab; k.gain_seg = gains->seg_blocks; k.gain_off = gains->blk_off; k.gain_stream = gains->stream_stride; }
         rc = conv_run_p1(c, ctx, k, plan, st, ev_start, ev_stop, ranges);
     } else if (plan.kernel == OHS_CONV_KERNEL_HOP1536_P1) {
         rc = conv_run_os(c, ctx, k, plan.K, st, ev_start, ev_stop, ranges);
@@ -1067,7 +1068,7 @@ int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, 
     }
     if (seg_gains && !k.gain_tab) {
         hipError_t e = launch_scale_segments(out, out_ss, out_cs, n_blocks, (int)c.S, gains->tab, gains->seg_blocks, gains->blk_off, st,
-                                             c.fp_mode);
+                                             c.fp_mode, gains->stream_stride);
         if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("segment gains: ") + hipGetErrorString(e));
     }
     return OHS_OK;

@@ -1,6 +1,7 @@
 // api_eq.hip -- the EQ table / state of a handle (EqState), ohs_eq_* (StereoParametricEQ, parametric_eq.rs:125-209)
 // and ohs_biquad_* (BiquadFilter as a type of its own, parametric_eq.rs:46-123).
 #include "api_internal.h"
+#include <map>
 
 using namespace ohs;
 using namespace ohs_api;
@@ -58,7 +59,10 @@ void eq_free(EqState &e)
     if (e.d_stabs) hipFree(e.d_stabs);
     if (e.d_stamps) hipFree(e.d_stamps);
     if (e.d_sched_lanes) hipFree(e.d_sched_lanes);
+    if (e.d_sched_stabs) hipFree(e.d_sched_stabs);
+    if (e.d_sched_gather) hipFree(e.d_sched_gather);
     e.d_state = nullptr; e.d_stabs = nullptr; e.stabs_passes = 0; e.d_stamps = nullptr; e.d_sched_lanes = nullptr; e.sched_n = 0;
+    e.d_sched_stabs = nullptr; e.d_sched_gather = nullptr; e.sched_passes = 0;
 }
 
 bool eq_any_enabled(const EqState &e)
@@ -270,8 +274,11 @@ int eq_set_schedule_tables(EqState &e, size_t n_tables, const float *coeffs, con
     DeviceWideSection dws;
     HIP_TRY(hipDeviceSynchronize());
     if (e.d_sched_lanes) hipFree(e.d_sched_lanes);
+    if (e.d_sched_stabs) hipFree(e.d_sched_stabs);
+    if (e.d_sched_gather) hipFree(e.d_sched_gather);
     e.d_sched_lanes = nullptr; e.sched_n = 0;
-    e.sched_coeffs.clear(); e.sched_en.clear();
+    e.d_sched_stabs = nullptr; e.d_sched_gather = nullptr; e.sched_passes = 0;
+    e.sched_coeffs.clear(); e.sched_en.clear(); e.sched_on.clear(); e.sched_class.clear();
     if (n_tables == 0) return OHS_OK;
     e.sched_coeffs.assign(coeffs, coeffs + n_tables * e.nb * 5);
     e.sched_en.assign(enabled, enabled + n_tables * e.nb);
@@ -293,6 +300,47 @@ int eq_set_schedule_tables(EqState &e, size_t n_tables, const float *coeffs, con
     }
     HIP_TRY(hipMalloc(&e.d_sched_lanes, lanes.size() * sizeof(float)));
     HIP_TRY(hipMemcpy(e.d_sched_lanes, lanes.data(), lanes.size() * sizeof(float), hipMemcpyHostToDevice));
+    // for the per-stream scheduled call: band counts, flag classes, and every table as EqStreamTables of 12 bands per pass
+    // (eq_upload_stream_tables' compaction, per table instead of per stream)
+    e.sched_on.assign(n_tables, 0);
+    e.sched_class.assign(n_tables, 0);
+    {
+        std::map<std::vector<unsigned char>, unsigned> classes;
+        size_t mx = 0;
+        for (size_t t = 0; t < n_tables; ++t) {
+            const std::vector<unsigned char> fl(e.sched_en.begin() + (long)(t * e.nb), e.sched_en.begin() + (long)((t + 1) * e.nb));
+            e.sched_class[t] = classes.emplace(fl, (unsigned)classes.size()).first->second;
+            size_t on = 0;
+            for (unsigned char v : fl) on += v;
+            e.sched_on[t] = (unsigned char)on;         // (nb <= OHS_MAX_EQ_BANDS = 64)
+            mx = std::max(mx, on);
+        }
+        const size_t passes = std::max<size_t>(1, (mx + 11) / 12), S = e.chains / 2;
+        std::vector<EqStreamTable> tabs(passes * n_tables);
+        std::memset(tabs.data(), 0, tabs.size() * sizeof(EqStreamTable));
+        for (size_t t = 0; t < n_tables; ++t) {
+            size_t count = 0;
+            for (size_t b = 0; b < e.nb; ++b) {
+                if (!e.sched_en[t * e.nb + b]) continue;
+                EqStreamTable &T = tabs[(count / 12) * n_tables + t];
+                const int k = (int)(count % 12);
+                const float *c = &e.sched_coeffs[(t * e.nb + b) * 5];
+                T.b0[k] = c[0]; T.b1[k] = c[1]; T.b2[k] = c[2]; T.a1[k] = c[3]; T.a2[k] = c[4];
+                T.slot[k] = (int)b;
+                T.nb = k + 1;
+                ++count;
+            }
+            for (size_t pk = 0; pk < passes; ++pk) {        // unused entries repeat the pass's last band's slot (never stored)
+                EqStreamTable &T = tabs[pk * n_tables + t];
+                for (int j = T.nb; j < 12; ++j) T.slot[j] = T.nb ? T.slot[T.nb - 1] : 0;
+            }
+        }
+        HIP_TRY(hipMalloc(&e.d_sched_stabs, tabs.size() * sizeof(EqStreamTable)));
+        HIP_TRY(hipMemcpy(e.d_sched_stabs, tabs.data(), tabs.size() * sizeof(EqStreamTable), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&e.d_sched_gather, passes * S * sizeof(EqStreamTable)));
+        HIP_TRY(hipMemset(e.d_sched_gather, 0, passes * S * sizeof(EqStreamTable)));
+        e.sched_passes = passes;
+    }
     e.sched_n = n_tables;
     (void)st;
     return OHS_OK;
@@ -397,6 +445,127 @@ int eq_launch_scheduled(EqState &e, const BatchSchedule &sc, size_t blk0, size_t
                                      in + roff, out + roff, ss, cs, rn, st, nullptr, single ? ev_start : nullptr,
                                      single ? ev_stop : nullptr);
             if (rc) return rc;
+        }
+    }
+    if (!single && ev_stop) HIP_TRY(hipEventRecord(ev_stop, st));
+    return OHS_OK;
+}
+
+// ---- a row of table indices per stream (ohs_batch_process_scheduled_streams) -------------------------------------------------
+bool eq_schedule_streams_scan(const EqState &e, BatchSchedule &sc)
+{
+    const size_t S = sc.tab_stride ? e.chains / 2 : 1;
+    sc.seg_bits.assign(sc.n_segs, 0);
+    sc.seg_max_on.assign(sc.n_segs, 0);
+    for (size_t s = 0; s < S; ++s) {
+        const unsigned *row = sc.tab + s * sc.tab_stride;
+        unsigned prev = 0;
+        for (size_t k = 0; k < sc.n_segs; ++k) {
+            const unsigned t = row[k];
+            if (t >= e.sched_n) return false;
+            const unsigned char on = e.sched_on[t];
+            unsigned char bits = (on == 0 || on > 12) ? BatchSchedule::kSegNoRing : 0;
+            if (k > 0 && prev != t) {
+                bits |= BatchSchedule::kSegIdxChange;
+                if (e.sched_class[prev] != e.sched_class[t]) bits |= BatchSchedule::kSegFlagsChange;
+            }
+            prev = t;
+            sc.seg_bits[k] |= bits;
+            sc.seg_max_on[k] = std::max(sc.seg_max_on[k], on);
+        }
+    }
+    return true;
+}
+
+// Blocks [blk0, blk0 + n_blocks) of a per-stream scheduled call.  The frames are cut where ANY stream's enabled flags change (the
+// lanes' roles change: state travels through the state slots).  A piece in which every table met has 1 .. 12 enabled bands and for
+// whose frames launch_eq_pass would take the wave ring is ONE launch of k_eq_ring_sched_streams: every wave follows its stream's
+// row.  Every other piece is cut further where any stream's INDEX changes, and each of those spans is one launch sequence for all
+// streams under their own tables -- the per-stream form of eq_launch, its tables gathered on the device from the schedule tables
+// (launch_eq_gather_tables; the exact-specials / conveyor forms: one sequence per stream, as there).  The number of launches
+// does not grow with the number of streams.
+int eq_launch_scheduled_streams(EqState &e, const BatchSchedule &sc, size_t blk0, size_t n_blocks, const float *in, float *out,
+                                long long ss, long long cs, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop)
+{
+    const size_t S = e.chains / 2, blk1 = blk0 + n_blocks;
+    const size_t seg_first = blk0 / sc.seg_blocks, seg_last = (blk1 - 1) / sc.seg_blocks;
+    auto seg_begin = [&](size_t k) { return std::max(blk0, k * sc.seg_blocks); };
+    int xcd_lo = e.xcd_lo, xcd_n = e.xcd_n;
+    if (tuning().eq_xcd_n > 0) { xcd_lo = tuning().eq_xcd_lo; xcd_n = tuning().eq_xcd_n; }
+    const bool ring_forms = !e.exact_specials && !tuning().eq_conveyor;
+    // pieces [k0, k1] of segments without a change of flags
+    struct Piece { size_t k0, k1; bool no_ring, idx_change; };
+    std::vector<Piece> pieces;
+    for (size_t k = seg_first; k <= seg_last; ++k) {
+        const unsigned char bits = sc.seg_bits[k];
+        if (k == seg_first || (bits & BatchSchedule::kSegFlagsChange)) pieces.push_back({k, k, false, false});
+        else if (bits & BatchSchedule::kSegIdxChange) pieces.back().idx_change = true;
+        pieces.back().k1 = k;
+        if (bits & BatchSchedule::kSegNoRing) pieces.back().no_ring = true;
+    }
+    auto piece_takes_kernel = [&](const Piece &p) {
+        const long long n = (long long)((p.k1 == seg_last ? blk1 : (p.k1 + 1) * sc.seg_blocks) - seg_begin(p.k0)) * BS;
+        return !p.no_ring && sc.seg_blocks * BS < ((size_t)1 << 30) && eq_pass_takes_wave_ring(ss, cs, n, (int)e.chains, 1, e.exact_specials);
+    };
+    // the events ride in the dispatch when the chunk is exactly one launch of the scheduled kernel; else around
+    const bool single = pieces.size() == 1 && piece_takes_kernel(pieces[0]);
+    if (!single && ev_start) HIP_TRY(hipEventRecord(ev_start, st));
+    for (const Piece &p : pieces) {
+        const size_t pb0 = seg_begin(p.k0), pb1 = p.k1 == seg_last ? blk1 : (p.k1 + 1) * sc.seg_blocks;
+        if (piece_takes_kernel(p)) {
+            const long long off = (long long)(pb0 - blk0) * BS, n = (long long)(pb1 - pb0) * BS;
+            EqRingSched sch;
+            sch.lane_tabs = e.d_sched_lanes; sch.seg_tab = sc.d_tab; sch.n_segs = (int)sc.n_segs;
+            sch.seg_len = (int)(sc.seg_blocks * BS);
+            sch.seg0 = (int)p.k0; sch.off0 = (int)((pb0 - p.k0 * sc.seg_blocks) * BS);
+            hipError_t err = launch_eq_ring_sched_streams(in + off, out + off, ss, cs, n, (int)e.chains, e.d_sched_stabs, e.d_state, sch,
+                                                          (long long)sc.tab_stride, st, e.fp_mode, xcd_lo, xcd_n,
+                                                          single ? ev_start : nullptr, single ? ev_stop : nullptr);
+            if (err != hipSuccess) return fail(OHS_ERR_HIP, std::string("eq launch (per-stream schedule): ") + hipGetErrorString(err));
+            e.last_form = OHS_EQ_FORM_WAVE_RING;
+            e.last_scheduled = p.idx_change;
+            continue;
+        }
+        // spans [j0, j1] of segments without a change of any stream's index
+        for (size_t j0 = p.k0; j0 <= p.k1;) {
+            size_t j1 = j0;
+            const unsigned char mx = sc.seg_max_on[j0];        // (no index changes inside the span: every segment's is this)
+            while (j1 + 1 <= p.k1 && !(sc.seg_bits[j1 + 1] & BatchSchedule::kSegIdxChange)) ++j1;
+            const size_t sb0 = seg_begin(j0), sb1 = j1 == seg_last ? blk1 : (j1 + 1) * sc.seg_blocks;
+            const long long off = (long long)(sb0 - blk0) * BS, n = (long long)(sb1 - sb0) * BS;
+            const float *sin = in + off;
+            float *sout = out + off;
+            if (mx == 0) {      // identity for every stream: the frames still have to arrive in `out`
+                if (sout != sin)
+                    for (size_t s = 0; s < S; ++s)
+                        HIP_TRY(hipMemcpy2DAsync(sout + (long long)s * ss, (size_t)cs * sizeof(float), sin + (long long)s * ss,
+                                                 (size_t)cs * sizeof(float), (size_t)n * sizeof(float), 2, hipMemcpyDeviceToDevice, st));
+            } else if (ring_forms && eq_ring_addressable(ss, cs, n)) {
+                const size_t passes = ((size_t)mx + 11) / 12;
+                hipError_t err = launch_eq_gather_tables(e.d_sched_gather, e.d_sched_stabs, sc.d_tab + j0, (long long)sc.tab_stride, (int)S,
+                                                         (int)e.sched_n, (int)passes, st);
+                if (err != hipSuccess) return fail(OHS_ERR_HIP, std::string("eq schedule tables (gather): ") + hipGetErrorString(err));
+                for (size_t pk = 0; pk < passes; ++pk) {
+                    err = launch_eq_ring_streams(pk ? sout : sin, sout, ss, cs, n, (int)e.chains, e.d_sched_gather + pk * S, e.d_state, st,
+                                                 e.fp_mode, xcd_lo, xcd_n, nullptr, nullptr, &e.last_form);
+                    e.last_scheduled = false;
+                    if (err != hipSuccess) return fail(OHS_ERR_HIP, std::string("eq launch (per-stream schedule, span): ") + hipGetErrorString(err));
+                }
+            } else {
+                for (size_t s = 0; s < S; ++s) {
+                    const unsigned t = sc.tab[s * sc.tab_stride + j0];
+                    bool d1 = false;
+                    const float *si = sin + (long long)s * ss;
+                    float *so = sout + (long long)s * ss;
+                    int rc = eq_launch_table(e, &e.sched_coeffs[(size_t)t * e.nb * 5], &e.sched_en[(size_t)t * e.nb], nullptr, 2,
+                                             e.d_state + s * 2 * (size_t)kEqStateSlots * 2, si, so, ss, cs, n, st, &d1, nullptr, nullptr);
+                    if (rc) return rc;
+                    if (!d1 && so != si)
+                        HIP_TRY(hipMemcpy2DAsync(so, (size_t)cs * sizeof(float), si, (size_t)cs * sizeof(float), (size_t)n * sizeof(float),
+                                                 2, hipMemcpyDeviceToDevice, st));
+                }
+            }
+            j0 = j1 + 1;
         }
     }
     if (!single && ev_stop) HIP_TRY(hipEventRecord(ev_stop, st));

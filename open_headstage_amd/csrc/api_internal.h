@@ -244,9 +244,11 @@ int conv_os_chunks(const DeviceCtx *ctx, size_t S, long long n_blocks, bool in_p
 long long conv_p1_chunks(const DeviceCtx *ctx, size_t S, long long n_blocks, long long target_override, int xcd_n = 8);
 // a gain per segment of seg_blocks blocks (device memory): block t of the launch, block blk_off + t of the call, leaves with
 // tab[(blk_off + t) / seg_blocks].  NULL (or tab == NULL): the scalar `gain`.
+// stream_stride: stream s reads its row at tab + s * stream_stride (0: one row for all streams).
 struct ConvGains {
     const float *tab = nullptr;
     int seg_blocks = 1, blk_off = 0;
+    int stream_stride = 0;
 };
 int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
                 float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st,
@@ -305,6 +307,15 @@ struct EqState {
     std::vector<float> sched_coeffs;
     std::vector<unsigned char> sched_en;
     float *d_sched_lanes = nullptr;
+    // for the per-stream scheduled call: every schedule table as EqStreamTables, compacted by its own flags, 12 bands per pass --
+    // d_sched_stabs[pass * sched_n + table] (pass 0 is what k_eq_ring_sched_streams reads); sched_on = enabled bands per table,
+    // sched_class = a number per distinct set of enabled flags (two tables have equal flags iff equal class);
+    // d_sched_gather [sched_passes][streams]: the per-stream tables of the span a fallback launch serves, filled in stream order
+    // right in front of that launch (launch_eq_gather_tables)
+    ohs::EqStreamTable *d_sched_stabs = nullptr, *d_sched_gather = nullptr;
+    size_t sched_passes = 0;
+    std::vector<unsigned char> sched_on;
+    std::vector<unsigned> sched_class;
 };
 
 // One scheduled batch call, as the launches see it: segment k = blocks [k seg_blocks, (k + 1) seg_blocks) of the call.  tab / gain
@@ -315,6 +326,14 @@ struct BatchSchedule {
     const float *gain = nullptr;
     const unsigned *d_tab = nullptr;
     const float *d_gain = nullptr;
+    // ohs_batch_process_scheduled_streams: a row per stream -- stream s reads tab / d_tab at s * tab_stride and gain / d_gain at
+    // s * gain_stride (0: one row for all streams; else >= n_segs).  seg_bits[k], over ALL streams: kSegIdxChange -- some stream's
+    // index differs from segment k - 1's; kSegFlagsChange -- some stream's enabled flags do; kSegNoRing -- some stream's table has
+    // no or more than 12 enabled bands.  seg_max_on[k]: the largest number of enabled bands of any stream's table in segment k.
+    bool streams = false;
+    size_t tab_stride = 0, gain_stride = 0;
+    static constexpr unsigned char kSegIdxChange = 1, kSegFlagsChange = 2, kSegNoRing = 4;
+    std::vector<unsigned char> seg_bits, seg_max_on;
 };
 
 
@@ -333,6 +352,11 @@ bool eq_schedule_table_any_enabled(const EqState &e, size_t table);
 // the cascade over blocks [blk0, blk0 + n_blocks) of a scheduled call (shared table only; sc.tab != NULL); in / out point at blk0
 int eq_launch_scheduled(EqState &e, const BatchSchedule &sc, size_t blk0, size_t n_blocks, const float *in, float *out,
                         long long ss, long long cs, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);
+// the same with a row of table indices per stream (sc.streams, sc.tab != NULL).  First, one pass over the rows (sc.tab, tab_stride,
+// n_segs set) that fills sc.seg_bits / seg_max_on; false: an index is out of range (nothing else is to be trusted then)
+bool eq_schedule_streams_scan(const EqState &e, BatchSchedule &sc);
+int eq_launch_scheduled_streams(EqState &e, const BatchSchedule &sc, size_t blk0, size_t n_blocks, const float *in, float *out,
+                                long long ss, long long cs, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop);
 
 // ---- growable planar device FIFO [2][cap] (api_engine.hip) -----------------------------
 struct DevFifo {
@@ -441,6 +465,8 @@ struct ohs_batch {
     // ohs_batch_process_scheduled: the call's schedule travels through one of kSchedSlots staging slots -- pinned host memory
     // (the caller's arrays are free on return, the copy to the device is asynchronous) and its device copy, [cap] table indices
     // then [cap] gains; `done` is recorded behind the call that used the slot and waited for before the slot is filled again
+    // (ohs_batch_process_scheduled_streams: a row per stream, packed n_segs apart -- up to streams x n_segs entries per array; it
+    // uses the slot's 2 * cap entries as one array, the gain rows right behind the index rows, and copies them in one go)
     static constexpr int kSchedSlots = 4;
     struct SchedSlot {
         unsigned *h = nullptr, *d = nullptr;

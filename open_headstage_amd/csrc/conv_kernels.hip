@@ -1219,7 +1219,7 @@ __global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1(const ConvP1Args A)
 #undef OHS_P1_BLOCK_GAIN
 #define OHS_P1_GAIN seg_gain
 #define OHS_P1_BLOCK_GAIN(t) \
-    const float seg_gain = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(A.gain_tab[(A.gain_off + (t)) / A.gain_seg])));
+    const float seg_gain = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(A.gain_tab[(long long)s * A.gain_stream + (A.gain_off + (t)) / A.gain_seg])));
 __global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1_gains(const ConvP1Args A)
 #include "conv_p1_body.inc"
 #undef OHS_P1_GAIN
@@ -1606,22 +1606,23 @@ hipError_t launch_zero_tail_component(float2 *tails, long long n_streams, int wh
 
 // one workgroup per (block, chain): 512 frames times the gain of the block's segment
 __global__ __launch_bounds__(256) void k_scale_segments(float *out, long long stream_stride, long long ch_stride, int n_blocks,
-                                                        const float *__restrict__ gain_tab, int gain_seg, int gain_off, int fp_mode)
+                                                        const float *__restrict__ gain_tab, int gain_seg, int gain_off, int fp_mode,
+                                                        int gain_stream)
 {
     ohs_set_fp_mode(fp_mode);
     const int t = (int)(blockIdx.x % (unsigned)n_blocks), chain = (int)(blockIdx.x / (unsigned)n_blocks);
-    const float g = gain_tab[(gain_off + t) / gain_seg];
+    const float g = gain_tab[(long long)(chain >> 1) * gain_stream + (gain_off + t) / gain_seg];
     float *p = out + (long long)(chain >> 1) * stream_stride + (long long)(chain & 1) * ch_stride + (long long)t * kBlock;
     p[threadIdx.x] *= g;
     p[threadIdx.x + 256] *= g;
 }
 hipError_t launch_scale_segments(float *out, long long stream_stride, long long ch_stride, int n_blocks, int n_streams,
-                                 const float *gain_tab, int gain_seg, int gain_off, hipStream_t st, int fp_mode)
+                                 const float *gain_tab, int gain_seg, int gain_off, hipStream_t st, int fp_mode, int gain_stream)
 {
     if (n_blocks <= 0 || n_streams <= 0) return hipSuccess;
-    if (!out || !gain_tab || gain_seg < 1 || gain_off < 0 || 2ll * n_streams * n_blocks > 0x7fffffffll) return hipErrorInvalidValue;
+    if (!out || !gain_tab || gain_seg < 1 || gain_off < 0 || gain_stream < 0 || 2ll * n_streams * n_blocks > 0x7fffffffll) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_scale_segments, dim3((unsigned)(2ll * n_streams * n_blocks)), dim3(256), 0, st, out, stream_stride,
-                       ch_stride, n_blocks, gain_tab, gain_seg, gain_off, fp_mode);
+                       ch_stride, n_blocks, gain_tab, gain_seg, gain_off, fp_mode, gain_stream);
     return hipGetLastError();
 }
 

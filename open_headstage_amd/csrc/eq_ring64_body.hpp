@@ -183,24 +183,36 @@ __device__ __forceinline__ void eq_ring64_groups(const RingLane &c, Ring64Regs &
 // PER_STREAM: the chain's stream owns its bands (parametric_eq.rs:125-129) -- constants, state slots and the NUMBER of enabled
 // bands come from stabs[chain / 2] (kernels.h: EqStreamTable) instead of the launch's one table.
 // SCHED: the launch's table changes at segment boundaries (kernels.h: EqRingSched; the rule in the header comment).
+// Both (k_eq_ring_sched_streams, ohs_batch_process_scheduled_streams): the chain's stream follows its OWN row of segment indices,
+// sch->seg_tab + (chain >> 1) * idx_stride, and stabs holds one EqStreamTable per SCHEDULE TABLE: lane roles, band count and
+// state slots are those of the table the row names for the launch's first sample (all tables the stream meets inside the launch
+// have that table's enabled flags).  One chain per wave, so the row walk stays wave-uniform and every wave pays for its own
+// boundaries only.
 template <bool PER_STREAM, bool SCHED = false>
 __device__ __forceinline__ void eq_ring64_wave_t(const float *in, float *out, long long stream_stride, long long ch_stride,
                                                  long long n, int n_chains, int nb_shared, const EqPassTable &tab,
                                                  const EqStreamTable *__restrict__ stabs, float *__restrict__ state, long long chain,
-                                                 const EqRingSched *sch = nullptr)
+                                                 const EqRingSched *sch = nullptr, long long idx_stride = 0)
 {
     constexpr int G = kR64Group;
     if (chain >= n_chains) return;
     const int lane = threadIdx.x & 63;
     const int n32 = (int)n;
     int nb = nb_shared;
-    if constexpr (PER_STREAM) nb = stabs[chain >> 1].nb;
+    [[maybe_unused]] const unsigned *seg_row = nullptr;     // SCHED: the row of segment indices this wave follows
+    if constexpr (SCHED) seg_row = sch->seg_tab;
+    [[maybe_unused]] long long stab_i = chain >> 1;         // PER_STREAM: the stream's table, or (SCHED) its first schedule table
+    if constexpr (PER_STREAM && SCHED) {
+        seg_row += (chain >> 1) * idx_stride;
+        stab_i = (unsigned)__builtin_amdgcn_readfirstlane((int)seg_row[sch->seg0]);
+    }
+    if constexpr (PER_STREAM) nb = stabs[stab_i].nb;
     const bool pre = lane < nb, band = lane >= 1 && lane <= nb;
     const int jb = band ? lane - 1 : 0, jp = pre ? lane : 0;
     RingLane c;
     int slot;
     if constexpr (PER_STREAM) {
-        const EqStreamTable *T = stabs + (chain >> 1);
+        const EqStreamTable *T = stabs + stab_i;
         c.pb0 = pre ? T->b0[jp] : 1.0f;
         c.pb1 = pre ? T->b1[jp] : 0.0f;
         c.b2 = band ? T->b2[jb] : 0.0f;
@@ -288,11 +300,11 @@ __device__ __forceinline__ void eq_ring64_wave_t(const float *in, float *out, lo
         };
         // the launch starts off0 samples into segment seg0; segment seg0 + j starts at sample j * seg_len - off0
         const int n_segs = sch->n_segs, seg_len = sch->seg_len;
-        unsigned cur = (unsigned)__builtin_amdgcn_readfirstlane((int)sch->seg_tab[sch->seg0]);
+        unsigned cur = (unsigned)__builtin_amdgcn_readfirstlane((int)seg_row[sch->seg0]);
         int B = seg_len - sch->off0;
 #pragma unroll 1
         for (int seg = sch->seg0 + 1; seg < n_segs && B < n32; ++seg, B += seg_len) {
-            const unsigned t = (unsigned)__builtin_amdgcn_readfirstlane((int)sch->seg_tab[seg]);
+            const unsigned t = (unsigned)__builtin_amdgcn_readfirstlane((int)seg_row[seg]);
             if (t == cur) continue;             // (consecutive segments with one table are one run)
             cur = t;
             const int gb = B / G;               // the group of steps B + 1 .. B + 13

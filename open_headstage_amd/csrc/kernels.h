@@ -45,6 +45,8 @@ struct EqStreamTable {
 // lane of, {b2, a1, a2} of the one it is post lane of, (1, 0, 0, 0, 0) where it is neither -- i.e. every table compacted by its
 // own enabled mask; all tables a launch meets have the SAME mask (the host ends a launch where the mask changes).
 // seg_tab: device [n_segs], the table index of every segment of the call.  The launch starts off0 samples into segment seg0.
+// (k_eq_ring_sched_streams: seg_tab holds a row of n_segs indices per stream, idx_stride apart, and "the same mask" holds per
+// stream -- streams may sit on different masks and different numbers of bands.)
 struct EqRingSched {
     const float *lane_tabs;
     const unsigned *seg_tab;
@@ -74,6 +76,19 @@ hipError_t launch_eq_ring_sched(const float *in, float *out, long long stream_st
                                 int n_chains, const EqPassTable &tab, int n_bands, float *state, const EqRingSched &sch,
                                 hipStream_t st, int fp_mode, int xcd_lo, int xcd_n, hipEvent_t ev_start, hipEvent_t ev_stop,
                                 unsigned long long *stamps);
+// The same with a schedule per stream (k_eq_ring_sched_streams, ohs_batch_process_scheduled_streams): the wave of chain c walks
+// the index row sch.seg_tab + (c >> 1) * idx_stride (idx_stride 0: one row for all; else >= sch.n_segs).  d_tabs: device
+// [n_tables], one EqStreamTable per schedule table, compacted by the table's own flags -- the band count, state slots and
+// constants of the launch's first sample come from the table the stream's row names for segment seg0.  Within the launch every
+// table a stream meets has the enabled flags of that stream's first one, 1 .. 12 of them (the host ends the launch elsewhere).
+hipError_t launch_eq_ring_sched_streams(const float *in, float *out, long long stream_stride, long long ch_stride, long long n,
+                                        int n_chains, const EqStreamTable *d_tabs, float *state, const EqRingSched &sch,
+                                        long long idx_stride, hipStream_t st, int fp_mode, int xcd_lo, int xcd_n,
+                                        hipEvent_t ev_start, hipEvent_t ev_stop);
+// dst[pass * n_streams + s] = tabs[pass * n_tables + idx[s * idx_stride]] for pass < passes: the per-stream tables of ONE segment
+// of a per-stream schedule, in the layout launch_eq_ring_streams reads (the fallback forms of the per-stream scheduled call)
+hipError_t launch_eq_gather_tables(EqStreamTable *dst, const EqStreamTable *tabs, const unsigned *idx, long long idx_stride,
+                                   int n_streams, int n_tables, int passes, hipStream_t st);
 // (stamps, optional, device memory [4]: wave 0 of a RING launch writes {real-time counter at start, at end, shader-clock
 // counter at start, at end}: s_memrealtime runs at 100 MHz, s_memtime at the shader clock)
 // (ev_start / ev_stop: recorded at the start / completion of THIS launch.  The ring kernel's dispatch carries them
@@ -215,6 +230,7 @@ struct ConvP1Args {
     // segment) by k_conv_p1_gains; nullptr: `gain`, by k_conv_p1
     const float *gain_tab = nullptr;
     int gain_seg = 1, gain_off = 0;
+    int gain_stream = 0;        // stream s reads its row at gain_tab + s * gain_stream (0: one row for all streams)
 };
 // (ev_start / ev_stop, optional: recorded at the start / completion of the launches; carried by the dispatch itself when
 // the call is a single kernel -- see launch_eq_pass)
@@ -431,10 +447,11 @@ hipError_t launch_zero_tail_component(float2 *tails, long long n_streams, int wh
 hipError_t launch_debug_fft(const float2 *in, float2 *out, int inverse, int batch, const float2 *tw,
                             hipStream_t st);
 
-// the families without a gain table of their own: out (s, ch, i) *= gain_tab[(gain_off + i / 512) / gain_seg] for the n_blocks * 512
-// frames of every chain, behind a launch that ran with gain 1
+// the families without a gain table of their own: out (s, ch, i) *= gain_tab[s * gain_stream + (gain_off + i / 512) / gain_seg] for
+// the n_blocks * 512 frames of every chain, behind a launch that ran with gain 1 (gain_stream 0: one row for all streams)
 hipError_t launch_scale_segments(float *out, long long stream_stride, long long ch_stride, int n_blocks, int n_streams,
-                                 const float *gain_tab, int gain_seg, int gain_off, hipStream_t st, int fp_mode = 0);
+                                 const float *gain_tab, int gain_seg, int gain_off, hipStream_t st, int fp_mode = 0,
+                                 int gain_stream = 0);
 // dst[i] = src[i] * gain  (n floats)
 hipError_t launch_scale_copy(const float *src, float *dst, long long n, float gain, hipStream_t st, int fp_mode = 0);
 hipError_t launch_scale_copy_done(const float *src, float *dst, long long n, float gain, unsigned *counter, unsigned *done,

@@ -12,12 +12,19 @@ Device time per step by HIP events around `--steps` back-to-back steps on a stre
 variant.  Prints one JSON line per round and a summary (median, min, max per variant, the ratios of the medians).
 
     python tools/bench_scheduled.py [--rounds 5] [--steps 5] [--out profiles/NAME.jsonl]
+
+--per-stream prices ohs_batch_process_scheduled_streams instead: every stream its own pseudo-random index row over the pool of
+tables (one set of flags) and its own gain row, a new table and gain in every segment of every stream.  The yardstick is
+`scheduled` (ohs_batch_process_scheduled, one row for all) on the same handle and buffers, alternating with the new call round
+by round; `stage` is the larger staging copy alone (streams x segments x 8 bytes, pinned host memory to the device), the margin
+the new call is allowed on top of the yardstick's own spread.
 """
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -39,6 +46,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--loop-steps", type=int, default=2)
     ap.add_argument("--out", type=str, default="")
+    ap.add_argument("--per-stream", action="store_true", help="ohs_batch_process_scheduled_streams against ohs_batch_process_scheduled")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     S, nb, sb = a.streams, a.blocks, a.seg_blocks
@@ -80,17 +88,50 @@ def main():
             b0, b1 = k * f, min((k + 1) * f, nb * 512)
             bp.process_ptr(x.data_ptr() + 4 * b0, y.data_ptr() + 4 * b0, (b1 - b0) // 512, 2 * nb * 512, nb * 512, hs)
 
+    # --per-stream: a row per stream; stream s starts elsewhere in the pool and walks it with its own odd step
+    rng = np.random.default_rng(8)
+    idx_s = np.zeros((S, n_segs), np.uint32)
+    idx_s[:, 0] = rng.integers(0, a.tables, S)
+    for k in range(1, n_segs):          # (a new table in every segment of every stream)
+        idx_s[:, k] = (idx_s[:, k - 1] + rng.integers(1, max(a.tables, 2), S)) % a.tables
+    assert a.tables < 2 or np.all(idx_s[:, 1:] != idx_s[:, :-1])
+    gains_s = (gains[None, :] * (1.0 + 0.001 * np.arange(S)[:, None])).astype(np.float32)
+    assert np.all(gains_s[:, 1:] != gains_s[:, :-1])
+    pinned = torch.empty(2 * S * n_segs, dtype=torch.int32).pin_memory()
+    staged = torch.empty(2 * S * n_segs, dtype=torch.int32, device=dev)
+
+    def streams():
+        bp.process_scheduled_streams(x, sb, idx_s, gains_s, out=y, hip_stream=hs)
+
+    def stage():
+        staged.copy_(pinned, non_blocking=True)
+
     variants = [("plain", plain, a.steps), ("scheduled", scheduled, a.steps)]
-    if a.loop_steps > 0:
+    if a.per_stream:
+        variants += [("streams", streams, a.steps), ("stage", stage, a.steps)]
+    elif a.loop_steps > 0:
         variants.append(("loop", loop, a.loop_steps))
     with torch.cuda.stream(stream):
-        for _, fn, _ in variants:       # warm-up: every shape the timed windows use
-            fn()
-            fn()
+        for _, fn, _ in variants:       # warm-up: every shape the timed windows use, every staging slot of the scheduled calls grown
+            for _ in range(5):
+                fn()
         stream.synchronize()
         forms = {}
         plain(); stream.synchronize(); forms["plain"] = list(bp.last_eq_form()) + list(bp.last_conv_plan())
         scheduled(); stream.synchronize(); forms["scheduled"] = list(bp.last_eq_form()) + list(bp.last_conv_plan())
+        if a.per_stream:
+            streams(); stream.synchronize(); forms["streams"] = list(bp.last_eq_form()) + list(bp.last_conv_plan())
+        prep = {}
+        if a.per_stream:        # host time of ONE call on an idle stream (no staging slot to wait for): the device idles that long
+            for name, fn in (("scheduled", scheduled), ("streams", streams)):
+                v = []
+                for _ in range(5):
+                    stream.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    v.append((time.perf_counter() - t0) * 1e3)
+                prep[name] = round(statistics.median(v), 4)
+            stream.synchronize()
         ms = {name: [] for name, _, _ in variants}
         lines = []
         for r in range(a.rounds):
@@ -98,13 +139,17 @@ def main():
             for name, fn, steps in variants:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
+                t0 = time.perf_counter()
                 for _ in range(steps):
                     fn()
+                t_host = (time.perf_counter() - t0) * 1e3 / steps
                 e1.record(stream)
                 stream.synchronize()
                 t = e0.elapsed_time(e1) / steps
                 ms[name].append(t)
                 rec[name + "_ms_per_step"] = round(t, 4)
+                if a.per_stream:        # (host time until the call returns: the device idles for the first call's share of it)
+                    rec[name + "_host_ms_per_call"] = round(t_host, 4)
             lines.append(rec)
             print(json.dumps(rec), flush=True)
     frames = S * nb * 512
@@ -119,6 +164,12 @@ def main():
     if "loop" in ms:
         summ["loop_over_scheduled"] = round(summ["loop"]["median_ms"] / summ["scheduled"]["median_ms"], 3)
         summ["loop_us_per_call"] = round(summ["loop"]["median_ms"] * 1e3 / n_segs, 2)
+    if prep:
+        summ["host_ms_per_call_on_an_idle_stream"] = prep
+    if "streams" in ms:
+        summ["streams_over_scheduled"] = round(summ["streams"]["median_ms"] / summ["scheduled"]["median_ms"], 4)
+        summ["margin_ms"] = round(summ["scheduled"]["max_ms"] - summ["scheduled"]["min_ms"] + summ["stage"]["median_ms"], 4)
+        summ["streams_minus_scheduled_ms"] = round(summ["streams"]["median_ms"] - summ["scheduled"]["median_ms"], 4)
     summ["scheduled_extra_us_per_boundary"] = round((summ["scheduled"]["median_ms"] - summ["plain"]["median_ms"]) * 1e3 / max(n_segs - 1, 1), 4)
     print(json.dumps(summ), flush=True)
     if a.out:

@@ -9,6 +9,11 @@ enqueue time does not unless it is the bound), and host wall time per call besid
 --eq: the reference's cadence through the existing setters -- ten bands on, and in front of EVERY call a changed table (ten
 ohs_batch_set_eq_band_coeffs) and a changed gain (ohs_batch_set_gain), as a host that refreshes per block does.  The per-segment
 call loop ohs_batch_process_scheduled replaces; `--streams 256 --taps 512 --sizes 2 --eq` is the headline's shape.
+
+--stream-eq: the same cadence with every stream on a table of its own -- streams x ten ohs_batch_set_stream_eq_band_coeffs and
+one ohs_batch_set_gain in front of EVERY call: the per-host-block loop ohs_batch_process_scheduled_streams replaces (one gain
+per call is all this loop can do: the handle has no gain per stream).  The setters are host work and the next launch uploads
+the tables synchronously, so the figure to read is wall_us_per_call.
 """
 import argparse
 import json
@@ -31,7 +36,10 @@ def main():
     ap.add_argument("--plan", type=int, default=0)
     ap.add_argument("--sizes", type=str, default="1,2,3,4,8,32,256")
     ap.add_argument("--eq", action="store_true", help="ten bands on; a changed table and gain in front of every call")
+    ap.add_argument("--stream-eq", action="store_true", help="as --eq, with streams x ten per-stream setters in front of every call")
+    ap.add_argument("--max-calls", type=int, default=400)
     a = ap.parse_args()
+    a.eq = a.eq or a.stream_eq
     dev = torch.device("cuda:0")
     S = a.streams
     bp = ohs.BatchProcessor(S, num_bands=10)
@@ -53,8 +61,13 @@ def main():
     def call(xs, ys):
         if a.eq:
             turn[0] += 1
-            for i, c in enumerate(tables[turn[0] % 6]):
-                bp.set_band_coeffs(i, c, True)
+            if a.stream_eq:
+                for s in range(S):
+                    for i, c in enumerate(tables[(turn[0] + s) % 6]):
+                        bp.set_stream_band_coeffs(s, i, c, True)
+            else:
+                for i, c in enumerate(tables[turn[0] % 6]):
+                    bp.set_band_coeffs(i, c, True)
             bp.set_gain(0.5 + 0.01 * (turn[0] % 32))
         bp.process(xs, out=ys)
     frames_total = 256 * 512
@@ -67,7 +80,7 @@ def main():
     steady = None
     for nb in [int(v) for v in a.sizes.split(",")]:
         n = nb * 512
-        calls = max(8, min(400, 4096 // nb))
+        calls = max(8, min(a.max_calls, 4096 // nb))
         xs = x[:, :, :n].contiguous()
         ys = torch.empty_like(xs)
         for _ in range(3):
@@ -83,7 +96,7 @@ def main():
         torch.cuda.synchronize()
         t_wall = time.perf_counter() - t0
         dev_us = e0.elapsed_time(e1) * 1e3 / calls
-        rec = {"streams": S, "taps": a.taps, "plan": a.plan, "eq": bool(a.eq), "blocks_per_call": nb, "calls": calls,
+        rec = {"streams": S, "taps": a.taps, "plan": a.plan, "eq": bool(a.eq), "stream_eq": bool(a.stream_eq), "blocks_per_call": nb, "calls": calls,
                "msamples_per_s": round(S * n / dev_us, 1),
                "device_us_per_call": round(dev_us, 2), "host_enqueue_us_per_call": round(t_host * 1e6 / calls, 2),
                "wall_us_per_call": round(t_wall * 1e6 / calls, 2),

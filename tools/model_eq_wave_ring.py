@@ -28,7 +28,9 @@ front of M.  Lane 0 has no b2, so everything happens in steps B + 1 .. B + 13: f
 or 32) these lie in ONE 48-step group, group B // 48.
 
 check() compares the model's bits with the oracle's StereoParametricEQ, refreshed with set_band_coeffs in front of every
-segment.  Run: python tools/model_eq_wave_ring.py
+segment.  check_streams() does so for several chains with different band counts that follow different index rows (the
+per-stream schedule of k_eq_ring_sched_streams: one chain per wave, every wave walks its own row, consecutive equal indices
+are one run).  Run: python tools/model_eq_wave_ring.py
 """
 import numpy as np
 
@@ -163,6 +165,49 @@ def check(nb, boundaries, n, n_tables=4, seed=0):
     return np.array_equal(got.view(np.uint32), ref.view(np.uint32))
 
 
+def row_schedule(row, seg_len, n, seg0=0, off0=0):
+    """A stream's row of table indices (one per segment of seg_len samples) -> the schedule [(B, table)] of ONE launch of n
+    samples that starts off0 samples into segment seg0.  Consecutive equal indices of the row are one run: the wave pays for
+    the boundaries of its own row only (k_eq_ring_sched_streams)."""
+    sched = [(0, int(row[seg0]))]
+    B, seg = seg_len - off0, seg0 + 1
+    while seg < len(row) and B < n:
+        if int(row[seg]) != sched[-1][1]:
+            sched.append((B, int(row[seg])))
+        seg += 1
+        B += seg_len
+    return sched
+
+
+def ring_eq_streams(xs, pools, rows, seg_len, states=None, seg0=0, off0=0):
+    """One launch of the per-stream scheduled wave ring: chain c (one wave) filters xs[c] with the tables of pools[c] -- every
+    chain its own number of bands -- along its own index row rows[c].  states: per chain [nb_c][2] or None.  -> (ys, states)"""
+    ys, out_states = [], []
+    for c, x in enumerate(xs):
+        y, st = ring_eq(x, pools[c], row_schedule(rows[c], seg_len, len(x), seg0, off0), None if states is None else states[c])
+        ys.append(y)
+        out_states.append(st)
+    return ys, out_states
+
+
+def check_streams(band_counts, rows1, rows2, seg_len=512, n_tables=4, seed=0):
+    """model == oracle, bit for bit, for chains with different band counts on different index rows over two consecutive launches
+    (rows1, rows2: [chains][segments of the launch]); the oracle EQ of every chain is refreshed in front of EVERY segment"""
+    rng = np.random.default_rng(seed)
+    n1, n2 = len(rows1[0]) * seg_len, len(rows2[0]) * seg_len
+    pools = [random_tables(rng, n_tables, nb) for nb in band_counts]
+    xs = [rng.standard_normal(n1 + n2).astype(F) for _ in band_counts]
+    y1, st = ring_eq_streams([x[:n1] for x in xs], pools, rows1, seg_len)
+    y2, _ = ring_eq_streams([x[n1:] for x in xs], pools, rows2, seg_len, st)
+    ok = True
+    for c, x in enumerate(xs):
+        every = [(k * seg_len, int(t)) for k, t in enumerate(list(rows1[c]) + list(rows2[c]))]
+        ref = oracle_eq(x, pools[c], every)
+        got = np.concatenate([y1[c], y2[c]])
+        ok = ok and np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+    return ok
+
+
 if __name__ == "__main__":
     import os, sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -170,3 +215,7 @@ if __name__ == "__main__":
         ok = check(nb, [512, 1024, 1536, 2560], 3072)
         print(f"{nb:2d} bands, boundaries at 512 1024 1536 2560 (mod 48: 32 16 0 16): {'bit-exact' if ok else 'MISMATCH'}")
         assert ok
+    ok = check_streams([10, 7, 12], [[0, 1, 1, 2, 2, 2], [3, 3, 0, 0, 1, 2], [1, 2, 3, 0, 1, 2]],
+                       [[2, 2, 3, 3, 0, 0], [0, 1, 1, 1, 1, 3], [3, 2, 1, 0, 3, 2]])
+    print(f"three chains (10, 7, 12 bands) on their own index rows, two launches: {'bit-exact' if ok else 'MISMATCH'}")
+    assert ok
