@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""k_eq_ring's two forms (Tuning::eq_form: 1 = four chains per wave, 2 = one chain per wave) on the headline job at several stream
+"""k_eq_ring's forms (Tuning::eq_form: 1 = four chains per wave, 2 = one chain per wave with a band per pair of lanes, 3 = one
+chain per wave with a band per quad of lanes; AB_EQ_FORMS=1,3 chooses, default 1,2) on the headline job at several stream
 counts: ms per step of the whole batch call (EQ || convolution over six time chunks), experiments library.  Where does one
 chain per wave stop paying -- it needs a SIMD per chain, and the convolution underneath needs issue slots too."""
 import json
@@ -14,13 +15,14 @@ import open_headstage_amd as ohs  # noqa: E402
 from open_headstage_amd import _ffi, synth  # noqa: E402
 
 L = _ffi.experiments_lib()
+FORMS = tuple(int(f) for f in os.environ.get("AB_EQ_FORMS", "1,2").split(","))
 frames = 480256
 dev = torch.device("cuda:0")
 for S in [int(a) for a in sys.argv[1:]] or [128, 256, 320, 384, 448, 512]:
     x = synth.white_noise_torch(0, S, frames, dev)
     y = torch.empty_like(x)
     row = {"streams": S}
-    for form in (1, 2, 1, 2):
+    for form in FORMS + FORMS:
         _ffi.set_tuning("eq_form", form)
         bp = ohs.BatchProcessor(S, num_bands=10, library=L)
         for p, h in enumerate(synth.hrir_set(512)):

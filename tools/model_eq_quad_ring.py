@@ -1,0 +1,438 @@
+#!/usr/bin/env python3
+"""Lane-level CPU model of the quad form of the wave-ring EQ: one band per aligned quad of lanes, FOUR VOP2+DPP instructions
+per sample instead of the six of csrc/eq_ring64_body.hpp (modelled in tools/model_eq_wave_ring.py).
+
+64 lanes, one chain.  Band k (of nb <= 12 enabled bands, cascade order) owns quad k = lanes 4k .. 4k+3 = (a, b, c, d); quads
+nb .. 11 pass samples on; quads 12 .. 15 are the conveyor that the I/O port serves.  Per lane: Z0 / Z1 (alternating by step
+parity), Zp, G, P and the constants C1, C2; per quad of a band C1 = (1, 1, a2, a1), C2 = (b2, b1, b0, 1), of a pass-on or
+conveyor quad C1 = (1, 1, 0, 0), C2 = (0, 0, 1, 1).  A step (Zc = Z[step & 1], Zo = the other one), every result float32:
+
+    alpha   Zc = Zp(wave_ror:1) + G             a: x = y of the quad in front + 0   b: m2 + 0   c: t = m1 + s2   d: y = m0 + s1
+    delta   Zp = Zo(quad_perm 0,0,0,3) * C2     a: m2 = b2 x   b: m1 = b1 x   c: m0 = b0 x   d: 1.0 y  (the next quad's a takes it)
+    <slot>  one issue slot that the DPP hazard leaves free: the port's instructions go here (else a no-op)
+    beta    P  = Zc(quad_perm 0,0,3,3) * C1     a, b: 1.0 x   c: p2 = a2 y   d: p1 = a1 y
+    gamma   G  = Zc(quad_perm 0,0,1,2) - P      a, b: x - x = 0   c: s2' = m2 - p2   d: s1' = t - p1
+
+This is the oracle's order (out = s1 + b0 x; s1 = s2 + b1 x - a1 out; s2 = b2 x - a2 out), s1 in G of lane d, s2 in G of
+lane c.  A quad has a latency of four steps and four samples in flight; in a pass-on quad a sample goes a -> c -> d.
+
+Timeline (steps count from 1): sample i is in Zc of lane 0 at step i + 1, in lane a of quad q at step i + 1 + 4q, in its lane
+d (filtered, if the quad is a band) at step i + 3 + 4q.  The ring is 64 steps round.
+
+The port.  Samples of even and of odd index never share a register: behind alpha of step m, Zc holds in lanes a and d of
+the conveyor quads the eight outputs m - 49, m - 51 .. m - 63, and behind delta of step m + 1 those eight sit in lanes c
+and d of Zp, where alpha of step m + 2 .. picks them up.  So a group is 16 steps and has two half ports:
+    step 16g + 8    store B: lanes a, d of Zc               step 16g + 9   inject B: lanes c, d of Zp <- lanes a, b of x
+    step 16g + 15   store A (of group g + 1)                step 16g + 16  inject A (of group g + 1): <- lanes c, d of x
+    step 16g + 10   load x <- the 16 inputs of group g + K  step 16g + 14  wait for the x of group g + 1
+(the inject is a v_cndmask with a quad_perm on x; DPP's bank_mask selects quads of a row, not lanes of a quad)
+An inject at step n puts sample n + 60 - 4q into lane d and n + 62 - 4q into lane c of conveyor quad q (q = 12 .. 15); the x
+register of group g holds, in quad q, (a, b, c, d) = samples 16g + (71, 69, 62, 60) - 4q.  Outputs leave 64 samples behind
+the inputs that replace them, and an input is requested K groups before it is injected (K registers in rotation).
+All port instructions sit in the free slots of different steps; the inject writes Zp two instructions (beta, gamma) ahead of
+the alpha that reads it through DPP.
+
+Head and tail.  The ring starts at zero one group early (step -15; nothing of it depends on a sample before the first: an
+input that does not exist is a zero).  Band k's state of the launch before goes into G of its lanes c, d behind step
+4k + 2, one step before its first sample's sums; it is taken out behind step n + 4k + 2, in which the band has filtered
+sample n - 1.  The ring runs on zeros until the last output has been stored.
+
+hazards() walks the steady-state loop and gives, per DPP read, the distance in issue slots to the register's last VALU
+writer; check_hazards() fails below 2 (gfx9 / CDNA: two wait states between a VALU write and a DPP read of a VGPR).
+
+Run: python tools/model_eq_quad_ring.py
+"""
+import numpy as np
+
+F = np.float32
+LANES = 64
+G = 16                       # steps (= samples) per group
+Q0 = 12                      # first conveyor quad
+K_DEFAULT = 8                # groups between an input's request and its injection = x registers
+TINY = np.finfo(F).tiny
+
+_lane = np.arange(LANES)
+
+
+def _perm(p):
+    return (_lane & ~3) + np.asarray(p)[_lane & 3]
+
+
+QP_DELTA, QP_BETA, QP_GAMMA = _perm([0, 0, 0, 3]), _perm([0, 0, 3, 3]), _perm([0, 0, 1, 2])
+QP_INJECT = {"A": _perm([0, 1, 2, 3]), "B": _perm([0, 1, 0, 1])}
+ROLE = _lane & 3             # 0 .. 3 = a .. d
+QUAD = _lane >> 2
+CONV = QUAD >= Q0
+INJECT_LANES = CONV & (ROLE >= 2)
+STORE_LANES = CONV & ((ROLE == 0) | (ROLE == 3))
+X_SAMPLE = np.array([71, 69, 62, 60])[ROLE] - 4 * QUAD      # sample index of an x register's lane, from 16 g
+STORE_SAMPLE = np.array([-1, 0, 0, -3])[ROLE] - 4 * QUAD    # sample index a store at step m finds in Zc, from m
+
+
+def lane_constants(table):
+    """table: float32 [nb][5] = {b0, b1, b2, a1, a2} of the enabled bands -> (C1, C2), each [64]"""
+    table = np.asarray(table, F).reshape(-1, 5)
+    nb = table.shape[0]
+    assert 1 <= nb <= 12
+    c1 = np.tile(np.array([1, 1, 0, 0], F), 16)
+    c2 = np.tile(np.array([0, 0, 1, 1], F), 16)
+    for k in range(nb):
+        b0, b1, b2, a1, a2 = table[k]
+        c1[4 * k:4 * k + 4] = (1, 1, a2, a1)
+        c2[4 * k:4 * k + 4] = (b2, b1, b0, 1)
+    return c1, c2
+
+
+def group_program(g, K=K_DEFAULT):
+    """The instructions of group g (steps 16g + 1 .. 16g + 16) in issue order: (op, step, ...)"""
+    prog = []
+    for s in range(1, G + 1):
+        step = G * g + s
+        zc, zo = f"Z{step & 1}", f"Z{(step - 1) & 1}"
+        prog += [("alpha", step, zc), ("delta", step, zo)]
+        if s == 8:
+            prog.append(("store", step, zc))
+        elif s == 9:
+            prog.append(("inject", step, "B", f"x{g % K}"))
+        elif s == 10:
+            prog.append(("load", step, f"x{g % K}", g + K))
+        elif s == 14:
+            prog += [("wait", step, f"x{(g + 1) % K}"), ("nop4", step)]
+        elif s == 15:
+            prog.append(("store", step, zc))
+        elif s == 16:
+            prog.append(("inject", step, "A", f"x{(g + 1) % K}"))
+        else:
+            prog.append(("nop", step))
+        prog += [("beta", step, zc), ("gamma", step, zc), ("state", step)]
+    return prog
+
+
+def wait_count(K=K_DEFAULT):
+    """vmcnt of a group's wait: the memory instructions issued behind the load it waits for (they retire in issue order)"""
+    prog = [i for g in range(0, K + 1) for i in group_program(g, K)]
+    at = max(j for j, i in enumerate(prog) if i[0] == "wait")
+    reg = prog[at][2]
+    ld = max(j for j, i in enumerate(prog[:at]) if i[0] == "load" and i[2] == reg)
+    return sum(1 for i in prog[ld + 1:at] if i[0] in ("load", "store"))
+
+
+def hazards(K=K_DEFAULT, extra=()):
+    """(reader, step, register, distance) for every DPP read of the steady-state loop: distance = issue slots between the
+    register's last VALU write and the read.  `extra`: instructions (op, dpp-read register, written register) put behind the
+    last step of every K groups (the loop's own: offset advances, counter)."""
+    prog = []
+    for g in range(2 * K, 4 * K):
+        prog += [i for i in group_program(g, K) if i[0] != "state"]
+        if (g + 1) % K == 0:
+            prog += list(extra)
+    last_write, out = {}, []
+    for pos, ins in enumerate(prog):
+        op = ins[0]
+        dpp_read = write = None
+        if op == "alpha": dpp_read, write = "Zp", ins[2]
+        elif op == "delta": dpp_read, write = ins[2], "Zp"
+        elif op == "beta": dpp_read, write = ins[2], "P"
+        elif op == "gamma": dpp_read, write = ins[2], "G"
+        elif op == "inject": dpp_read, write = ins[3], "Zp"        # (x is written by a load: the wait covers it)
+        elif op == "valu": dpp_read, write = ins[1], ins[2]
+        if dpp_read is not None and dpp_read in last_write and pos >= len(prog) // 2:     # (the second pass: all writers seen)
+            out.append((op, ins[1], dpp_read, pos - last_write[dpp_read] - 1))
+        if write is not None:
+            last_write[write] = pos
+    return out
+
+
+def check_hazards(K=K_DEFAULT, verbose=False):
+    worst = {}
+    for op, step, reg, d in hazards(K):
+        key = (op, reg[:1] if reg.startswith("Z") and reg != "Zp" else reg)
+        worst[key] = min(worst.get(key, 99), d)
+    for (op, reg), d in sorted(worst.items()):
+        if verbose:
+            print(f"  {op:6s} reads {reg:3s} through DPP: {d} issue slots behind its last VALU write")
+        assert d >= 2, (op, reg, d)
+    return worst
+
+
+def _flush(v):
+    return np.where(np.abs(v) < TINY, np.copysign(F(0), v), v).astype(F)
+
+
+class Ring:
+    """the registers of one wave and the interpreter of group_program's instructions"""
+
+    def __init__(self, x, table, state=None, K=K_DEFAULT, mode=0):
+        self.x = np.asarray(x, F)
+        self.n = self.x.size
+        tab = np.asarray(table, F).reshape(-1, 5)
+        self.nb = tab.shape[0]
+        self.C1, self.C2 = lane_constants(tab)
+        self.K, self.mode = K, mode
+        self.r = {k: np.zeros(LANES, F) for k in ["Z0", "Z1", "Zp", "G", "P"]}
+        for g in range(-1, K - 1):
+            self.r[f"x{g % K}"] = self.load(g)
+        self.y = np.zeros(self.n, F)
+        self.stored = np.zeros(self.n, np.int32)
+        self.s_init = np.zeros((self.nb, 2), F) if state is None else np.asarray(state, F).reshape(self.nb, 2).copy()
+        self.s_save = self.s_init.copy()
+
+    def load(self, g):
+        i = G * g + X_SAMPLE
+        ok = CONV & (i >= 0) & (i < self.n)
+        v = np.zeros(LANES, F)
+        v[ok] = self.x[i[ok]]
+        return v
+
+    def op(self, f, a, b):
+        # MODE.FP_DENORM (kernels.h, ohs_set_fp_mode): mode 1 flushes results, mode 2 operands as well
+        if self.mode == 2:
+            a, b = _flush(a), _flush(b)
+        with np.errstate(invalid="ignore"):
+            v = f(a, b).astype(F)
+        return _flush(v) if self.mode else v
+
+    def run(self, prog):
+        r = self.r
+        for ins in prog:
+            o, step = ins[0], ins[1]
+            if o == "alpha":
+                r[ins[2]] = self.op(np.add, np.roll(r["Zp"], 1), r["G"])
+            elif o == "delta":
+                r["Zp"] = self.op(np.multiply, r[ins[2]][QP_DELTA], self.C2)
+            elif o == "beta":
+                r["P"] = self.op(np.multiply, r[ins[2]][QP_BETA], self.C1)
+            elif o == "gamma":
+                r["G"] = self.op(np.subtract, r[ins[2]][QP_GAMMA], r["P"])
+            elif o == "store":
+                i = step + STORE_SAMPLE
+                ok = STORE_LANES & (i >= 0) & (i < self.n)
+                self.y[i[ok]] = r[ins[2]][ok]
+                self.stored[i[ok]] += 1
+            elif o == "inject":
+                r["Zp"] = np.where(INJECT_LANES, r[ins[3]][QP_INJECT[ins[2]]], r["Zp"]).astype(F)
+            elif o == "load":
+                r[ins[2]] = self.load(ins[3])
+            elif o == "state":
+                for k in range(self.nb):
+                    if step == 4 * k + 2:
+                        r["G"][4 * k + 3], r["G"][4 * k + 2] = self.s_init[k]
+                    if step == self.n + 4 * k + 2:
+                        self.s_save[k] = (r["G"][4 * k + 3], r["G"][4 * k + 2])
+
+
+def n_groups(n):
+    """groups -1 .. n_groups(n) - 1 run: the last output, sample n - 1, is stored by step n + 62 at the latest"""
+    return (n + 62 + G - 1) // G
+
+
+def ring_eq(x, table, state=None, K=K_DEFAULT, mode=0):
+    """One launch over x (float32 [n]) -> (y, new state [nb][2] = (s1, s2))"""
+    ring = Ring(x, table, state, K, mode)
+    for g in range(-1, n_groups(ring.n)):
+        ring.run(group_program(g, K))
+    assert np.all(ring.stored == 1), "every output is stored exactly once"
+    return ring.y, ring.s_save
+
+
+def oracle_eq(x, table, sizes, mode=0, fs=48000.0):
+    """the oracle's StereoParametricEQ over x, one process_block per entry of sizes"""
+    from oracle import ohs_oracle as orc
+    tab = np.asarray(table, F).reshape(-1, 5)
+    eq = orc.StereoParametricEQ(tab.shape[0], fs)
+    for j in range(tab.shape[0]):
+        eq.set_band_coeffs(j, tab[j], True)
+    out, o = [], 0
+    for n in sizes:
+        l = np.asarray(x[o:o + n], F).copy(); r = l.copy()
+        if mode:
+            with orc.flush_denormals(mode):
+                eq.process_block(l, r)
+        else:
+            eq.process_block(l, r)
+        out.append(l)
+        o += n
+    return np.concatenate(out)
+
+
+def random_table(rng, nb, fs=48000.0):
+    import open_headstage_amd as ohs
+    t = np.zeros((nb, 5), F)
+    for j in range(nb):
+        t[j] = ohs.biquad_coefficients(int(rng.integers(0, 3)), fs, float(rng.uniform(40.0, 16000.0)),
+                                       float(rng.uniform(0.4, 4.0)), float(rng.uniform(-9.0, 9.0)))
+    return t
+
+
+def model_launches(x, table, sizes, K=K_DEFAULT, mode=0):
+    out, st, o = [], None, 0
+    for n in sizes:
+        y, st = ring_eq(x[o:o + n], table, st, K, mode)
+        out.append(y)
+        o += n
+    return np.concatenate(out)
+
+
+def check(nb, sizes, seed=0, K=K_DEFAULT, mode=0, x=None):
+    """model == oracle over consecutive launches of the given sizes (the state handed over by the model's own array): bit for
+    bit in mode 0; in the flushing modes equal as numbers, differing bits only where both are zero (include/ohs_hip.h)"""
+    rng = np.random.default_rng(seed + 100 * nb)
+    tab = random_table(rng, nb)
+    if x is None:
+        x = rng.standard_normal(sum(sizes)).astype(F)
+    got = model_launches(x, tab, sizes, K, mode)
+    ref = oracle_eq(x, tab, sizes, mode)
+    if mode == 0:
+        return np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+    d = got.view(np.uint32) != ref.view(np.uint32)
+    return np.array_equal(got, ref) and bool(np.all(got[d] == 0.0) and np.all(ref[d] == 0.0))
+
+
+def check_zero_corners(nb=10, n=3000, seed=5):
+    """zeros and -0.0 in the input: equal as numbers everywhere, bit-exact wherever the oracle's output is not a zero, and a
+    zero of the model that differs is +0.0 for the oracle's -0.0 (never the reverse)"""
+    rng = np.random.default_rng(seed)
+    tab = random_table(rng, nb)
+    x = rng.standard_normal(n).astype(F)
+    x[200:300] = -0.0
+    x[700:900] = 0.0
+    x[1500:] = -0.0
+    got, ref = model_launches(x, tab, [n]), oracle_eq(x, tab, [n])
+    d = got.view(np.uint32) != ref.view(np.uint32)
+    return np.array_equal(got, ref) and bool(np.all(ref[d] == 0.0) and np.all(np.signbit(ref[d])) and not np.any(np.signbit(got[d])))
+
+
+def check_nonfinite_reach(nb=10, n=6000, k=3001, seed=6):
+    """a non-finite input sample k: bit-exact up to sample k - 64, non-finite from k on (include/ohs_hip.h: up to 64 early)"""
+    rng = np.random.default_rng(seed)
+    tab = random_table(rng, nb)
+    ok = True
+    for bad in (np.nan, np.inf):
+        for kk in range(k, k + 16):
+            x = rng.standard_normal(n).astype(F)
+            x[kk] = bad
+            got, ref = model_launches(x, tab, [n]), oracle_eq(x, tab, [n])
+            ok = ok and np.array_equal(got[:kk - 64].view(np.uint32), ref[:kk - 64].view(np.uint32)) and not np.any(np.isfinite(got[kk:]))
+    return ok
+
+
+# ---- the launch as csrc/eq_quad_ring_body.hpp runs it: the C++ form around an interpreter of the generated asm TEXT ----------
+
+def run_asm(lines, v, x, y, stored, n, iters):
+    """`iters` iterations of the generated loop (tools/gen_eq_quad_ring_asm.py: loop_asm) on the register file v (v[k]: 64
+    lanes; uint32 for the offsets v0, v1, v9, v10, float32 elsewhere).  Buffer accesses are range-checked against 4 n as the
+    hardware checks a raw buffer: VGPR offset + instruction offset >= num_records is dropped / reads 0.  VCC = every lane
+    but c, d of the conveyor quads."""
+    import re
+    vcc = ~INJECT_LANES
+    ops = {"v_add_f32_dpp": np.add, "v_mul_f32_dpp": np.multiply, "v_sub_f32_dpp": np.subtract}
+
+    def dpp(src, ctrl):
+        if ctrl == "wave_ror:1":
+            return np.roll(src, 1)
+        return src[_perm([int(c) for c in re.match(r"quad_perm:\[(\d),(\d),(\d),(\d)\]", ctrl).groups()])]
+
+    for _ in range(iters):
+        for l in lines:
+            t = l.replace(",", " ").split()
+            op = t[0]
+            if op in ops:
+                d, a, b = (int(r[1:]) for r in t[1:4])
+                ctrl = "wave_ror:1" if "wave_ror:1" in l else re.search(r"quad_perm:\[[\d,]+\]", l).group(0)
+                v[d] = ops[op](dpp(v[a], ctrl), v[b]).astype(F)
+            elif op == "v_cndmask_b32_dpp":
+                d, a, b = (int(r[1:]) for r in t[1:4])
+                v[d] = np.where(vcc, v[b], dpp(v[a], re.search(r"quad_perm:\[[\d,]+\]", l).group(0))).astype(F)
+            elif op in ("buffer_store_dword", "buffer_load_dword"):
+                d, a = int(t[1][1:]), int(t[2][1:])
+                off = v[a].astype(np.uint64) + int(re.search(r"offset:(\d+)", l).group(1))
+                ok = off < 4 * n
+                i = (off[ok] // 4).astype(np.int64)
+                if op == "buffer_store_dword":
+                    y[i] = v[d][ok]
+                    stored[i] += 1
+                else:
+                    w = np.zeros(LANES, F)
+                    w[ok] = x[i]
+                    v[d] = w
+            elif op == "v_add_u32_e64":
+                d, a, b = (int(r[1:]) for r in t[1:4])
+                v[d] = (v[a] + v[b]).astype(np.uint32)
+            else:
+                assert op in ("v_nop_e64", "s_waitcnt", "s_nop", "s_add_u32"), l
+
+
+def ring_eq_as_launched(x, table, state=None, lines=None, K=K_DEFAULT):
+    """One launch with the structure of eq_quad_ring_wave: groups -1 .. g0 - 1 in the C++ form (inputs requested two groups
+    ahead: xcur, xnext), whole iterations of K groups through run_asm on the generated text with the kernel's offsets, the
+    C++ form to the end.  -> (y, new state)"""
+    ring = Ring(x, table, state, K)
+    n = ring.n
+    xcur, xnext = ring.load(-1), ring.load(0)
+    g_hi = (n + 1) // G
+    iters = (g_hi - 5) // K if g_hi - 5 >= K else 0
+    g0 = g_hi - iters * K if iters else -1
+    xa = [ring.load(g0 + k) if iters else None for k in range(K)]      # (x0, x1 come from the head: checked below)
+
+    def group_cpp(g):
+        nonlocal xcur, xnext
+        xnext2 = ring.load(g + 2)
+        ring.r["xcur"], ring.r["xnext"] = xcur, xnext
+        prog = []
+        for ins in group_program(g, K):
+            if ins[0] == "inject":
+                prog.append(("inject", ins[1], ins[2], "xcur" if ins[2] == "B" else "xnext"))
+            elif ins[0] != "load":
+                prog.append(ins)
+        ring.run(prog)
+        xcur, xnext = xnext, xnext2
+
+    g_total = n_groups(n)
+    g = -1
+    while g < (g0 if iters else g_total):
+        group_cpp(g)
+        g += 1
+    if iters:
+        assert np.array_equal(xcur, xa[0]) and np.array_equal(xnext, xa[1])
+        r = ring.r
+        st_off = np.where(STORE_LANES, (G * (g0 - 1) + 8 + STORE_SAMPLE) * 4, 0xFFFFF000).astype(np.uint32)
+        ld_off = np.where(CONV, (G * g0 + X_SAMPLE) * 4, 0xFFFFF000).astype(np.uint32)
+        assert np.all(st_off[STORE_LANES] < 2 ** 31)            # (g0 >= 5: no store offset of the run is negative)
+        v = {0: st_off, 1: ld_off, 2: r["Z0"], 3: r["Z1"], 4: r["Zp"], 5: r["G"], 6: r["P"], 7: ring.C1, 8: ring.C2,
+             9: np.where(CONV, 4 * G * K, 0).astype(np.uint32), 10: np.where(STORE_LANES, 4 * G * K, 0).astype(np.uint32),
+             11: xcur, 12: xnext}
+        for k in range(2, K):
+            v[11 + k] = xa[k]
+        run_asm(lines, v, ring.x, ring.y, ring.stored, n, iters)
+        r["Z0"], r["Z1"], r["Zp"], r["G"], r["P"] = v[2], v[3], v[4], v[5], v[6]
+        xcur, xnext = v[11], v[12]
+        g = g_hi
+        while g < g_total:
+            group_cpp(g)
+            g += 1
+    assert np.all(ring.stored == 1), "every output is stored exactly once"
+    return ring.y, ring.s_save
+
+
+if __name__ == "__main__":
+    import os, sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    print(f"DPP read distances of the steady-state loop (K = {K_DEFAULT}, wait: vmcnt({wait_count()})):")
+    check_hazards(verbose=True)
+    for nb in range(1, 13):
+        ok = check(nb, [700, 1, 333, 64, 1000])
+        print(f"{nb:2d} bands, launches of 700 1 333 64 1000 samples: {'bit-exact' if ok else 'MISMATCH'}")
+        assert ok
+    for n in list(range(1, 40)) + [47, 48, 49, 63, 64, 65, 127, 128, 129, 130, 143, 144, 145]:
+        assert check(10, [n, n, 7, n]), n
+    print("10 bands, every launch length 1 .. 39 and around the group and ring edges: bit-exact")
+    for mode in (1, 2):
+        x = np.random.default_rng(9).standard_normal(30000).astype(F)
+        x[1500:] = 0.0
+        ok = check(10, [1000, 9000, 20000], mode=mode, x=x)
+        print(f"denormal mode {mode}, the state decaying behind the signal's end: {'equal' if ok else 'MISMATCH'}")
+        assert ok
+    assert check_zero_corners()
+    print("zeros and -0.0 in the input: equal as numbers, only -0.0 -> +0.0")
+    assert check_nonfinite_reach()
+    print("a non-finite input sample: bit-exact up to 64 samples before it, non-finite from it on")
