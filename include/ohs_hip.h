@@ -454,6 +454,57 @@ enum {
     OHS_EQ_FORM_CONVEYOR = 3    /* conveyor form (more than 12 bands per pass, exact-specials mode, far strides) */
 };
 int  ohs_batch_last_eq_form(const ohs_batch *b, int *form, int *scheduled);
+/* ---- a schedule of HRIR sets inside one call ----
+ * A binaural renderer moves its four impulse responses while audio runs: speaker angles move, a head turns, a source travels.
+ * ohs_batch_set_ir between short calls allocates and waits per change, has one set for ALL streams and one semantics (the old
+ * response's tail is cut off).  Here the handle holds a TABLE of sets, and in one processing call every stream names a set per
+ * segment.
+ *
+ * ohs_batch_set_schedule_irs: n_sets sets of four responses [Lsl, Lsr, Rsl, Rsr], irs[n_sets][4][len], 1 <= len <= 512 (one
+ * partition; shorter responses are zero-padded by the caller, or by a smaller len for all).  Host array, copied before return.
+ * Replaces any earlier table; n_sets == 0 frees it.  Not on the audio path: it allocates and waits for the device.
+ * (ohs_sofa_speaker_irs builds the four responses of a set for any speaker angles, without a device.)
+ *
+ * ohs_batch_process_ir_scheduled: ohs_batch_process in which stream s convolves segment k -- frames [k * seg_blocks * 512,
+ * (k + 1) * seg_blocks * 512) of the call, the last one may be short; n_segments = ceil(n_blocks / seg_blocks) -- with set
+ * ir_idx[s * idx_stride + k] (32-bit entries < n_sets).  idx_stride == 0: one row of n_segments entries for all streams, else
+ * >= n_segments.  Host array, reusable on return.  Asynchronous on `hip_stream`; d_in may equal d_out.
+ *   Per block: block t of stream s is convolved with the set of its segment, all four paths; its frames leave as
+ *     (w_t + overlap) * gain, the arithmetic of the plain call's kernel.
+ *   OHS_IR_SWITCH_RING_OUT: the overlap block t - 1 left is added, whatever set produced it -- the old response's tail rings out
+ *     under the new one: a block-wise time-varying FIR, what a renderer wants.  The start of the call is no boundary: the state the
+ *     previous call left rings out into the first block.
+ *   OHS_IR_SWITCH_CUT: where a stream's index changes between consecutive segments, that stream's incoming overlap is zero; the
+ *     start of the call counts as a boundary too.  This is the reference's set_ir (convolution.rs:135-138): the result is that of
+ *     ohs_batch_set_ir for all four paths in front of every run of equal indices and ohs_batch_process per run (bit for bit under
+ *     plan 1).  Consecutive equal indices are no boundary in either mode.
+ *   After the call, one row for all streams (idx_stride == 0): the handle's four responses ARE the last segment's set, as
+ *     ohs_batch_process_scheduled leaves its last table: a following ohs_batch_process continues with them.
+ *   After the call, a row per stream: the handle's responses are what they were before the call (there is no per-stream response
+ *     on the handle to adopt into).
+ *   State at rest, both cases: every stream's overlaps are what ITS last block left -- the merged overlap the next call adds, and
+ *     the per-path overlaps under that stream's own last set, so that a later ohs_batch_set_ir of one path drops exactly that
+ *     path's tail of every stream and the other three ring out.
+ *   The EQ and the gain are the handle's own (shared or static per-stream tables, as in ohs_batch_process); this schedule does not
+ *     combine with the EQ and gain schedules in one call.  EQ state, overlaps and last input carry over in both directions: plain,
+ *     EQ-scheduled and IR-scheduled calls may be mixed freely.
+ *   The call is always served by the block-512 family, whatever ohs_batch_set_conv_plan says (the hop-1536 plan's windows
+ *     straddle segment boundaries): ohs_batch_last_conv_plan reports OHS_CONV_KERNEL_BLOCK512_P1 and
+ *     ohs_batch_last_conv_ir_scheduled 1.  One convolution launch per time chunk of the call, as for the plain call, whatever the
+ *     number of segments or streams.  A call whose one row names one set throughout IS the plain call on that set (its launches,
+ *     its bits; ohs_batch_last_conv_ir_scheduled 0).
+ * OHS_ERR_INVALID_ARG, before anything is queued (the handle stays usable): NULL handle, buffers or ir_idx; seg_blocks == 0; an
+ * index >= n_sets in any row; no set table uploaded; a non-zero idx_stride below n_segments; an unknown switch_mode; strides
+ * smaller than the processed region; a handle whose own responses are longer than one partition, or which has tails of such a
+ * response pending; at upload, len == 0 or len > 512.  A HIP failure marks the handle failed until ohs_batch_reset, as in every
+ * processing call. */
+int  ohs_batch_set_schedule_irs(ohs_batch *b, size_t n_sets, const float *irs, size_t len);
+enum { OHS_IR_SWITCH_RING_OUT = 0, OHS_IR_SWITCH_CUT = 1 };
+int  ohs_batch_process_ir_scheduled(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
+                                    size_t channel_stride, size_t seg_blocks, const unsigned *ir_idx, size_t idx_stride,
+                                    int switch_mode, void *hip_stream);
+/* whether the handle's most recent convolution launch looked the set up per block inside the kernel (k_conv_p1_irs) */
+int  ohs_batch_last_conv_ir_scheduled(const ohs_batch *b, int *scheduled);
 /* The same as ohs_batch_process, but `hip_stream` is NOT made to wait for the last time chunk's convolution (it runs on an
  * internal stream underneath the EQ): d_out is complete on `hip_stream` only after ohs_batch_join (a
  * stream-side wait, asynchronous) or ohs_batch_sync.  Back-to-back deferred calls with the same buffers

@@ -132,6 +132,10 @@ PROTOTYPES = {
     "ohs_batch_process_scheduled_streams": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                     C.POINTER(C.c_uint32), C.c_size_t, fp, C.c_size_t, vp]),
     "ohs_batch_last_eq_form": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ohs_batch_set_schedule_irs": (C.c_int, [vp, C.c_size_t, fp, C.c_size_t]),
+    "ohs_batch_process_ir_scheduled": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                 C.POINTER(C.c_uint32), C.c_size_t, C.c_int, vp]),
+    "ohs_batch_last_conv_ir_scheduled": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "ohs_batch_join": (C.c_int, [vp, vp]),
     "ohs_batch_sync": (C.c_int, [vp, vp]),
     "ohs_batch_process_host": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),

@@ -228,6 +228,88 @@ class BatchProcessor:
                                            table_idx, gains, hip_stream)
         return out
 
+    # -- a schedule of HRIR sets -------------------------------------------------------
+    IR_SWITCH = {"ring_out": 0, "cut": 1}
+
+    def set_schedule_irs(self, irs) -> None:
+        """The sets of four impulse responses [Lsl, Lsr, Rsl, Rsr] an IR-scheduled call chooses from: irs [n_sets][4][len],
+        len <= 512; replaces any earlier table, an empty array frees it (ohs_batch_set_schedule_irs)."""
+        a = np.ascontiguousarray(irs, dtype=np.float32)
+        if a.size == 0:
+            self._check(self._lib.ohs_batch_set_schedule_irs(self._h, 0, None, 0))
+            return
+        if a.ndim != 3 or a.shape[1] != 4:
+            raise ValueError(f"expected irs [n_sets][4][len], got {a.shape}")
+        self._check(self._lib.ohs_batch_set_schedule_irs(self._h, a.shape[0], a.ctypes.data_as(fp), a.shape[2]))
+
+    def set_schedule_speakers(self, sofa, angles, radius_m: float = 1.0, fs: float = 0.0) -> np.ndarray:
+        """A set per row of angles [n_sets][4] = (az_l, el_l, az_r, el_r) (the plugin's degrees, as set_speakers): the four
+        responses ohs_sofa_speaker_irs builds for them, zero-padded to the longest; sets of more than 512 taps are refused.
+        -> the uploaded array [n_sets][4][len]"""
+        ang = np.asarray(angles, dtype=np.float64)
+        if ang.ndim != 2 or ang.shape[1] != 4 or ang.shape[0] == 0:
+            raise ValueError(f"expected angles [n_sets][4], got {ang.shape}")
+        from .sofa import speaker_irs_plugin_angles
+        sets = [speaker_irs_plugin_angles(sofa, float(r[0]), float(r[1]), float(r[2]), float(r[3]), radius_m, fs) for r in ang]
+        longest = max(len(h) for st in sets for h in st)
+        if longest > BLOCK_SIZE:
+            raise ValueError(f"a response of {longest} taps: a schedule holds one-partition responses (<= {BLOCK_SIZE} taps)")
+        out = np.zeros((len(sets), 4, max(longest, 1)), dtype=np.float32)
+        for i, st in enumerate(sets):
+            for p, h in enumerate(st):
+                out[i, p, :len(h)] = h
+        self.set_schedule_irs(out)
+        return out
+
+    def last_conv_ir_scheduled(self) -> bool:
+        """whether the most recent convolution launch looked the HRIR set up per block inside the kernel
+        (ohs_batch_last_conv_ir_scheduled)"""
+        v = C.c_int()
+        self._check(self._lib.ohs_batch_last_conv_ir_scheduled(self._h, C.byref(v)))
+        return bool(v.value)
+
+    def process_ir_scheduled_ptr(self, d_in: int, d_out: int, n_blocks: int, stream_stride: int, channel_stride: int,
+                                 seg_blocks: int, ir_idx, mode="ring_out", hip_stream: int = 0) -> None:
+        """ohs_batch_process_ir_scheduled: stream s convolves segment k = blocks [k seg_blocks, (k + 1) seg_blocks) of the call
+        with set ir_idx[s][k] (set_schedule_irs); a 1-D ir_idx is one row for all streams.  mode: "ring_out" (the old response's
+        tail rings out under the new one) or "cut" (the reference's set_ir: it is cut off), or the C constants 0 / 1."""
+        n_segs = -(-int(n_blocks) // int(seg_blocks)) if seg_blocks else 0
+        if ir_idx is None:
+            raise ValueError("ir_idx is required")
+        a = np.ascontiguousarray(ir_idx, dtype=np.uint32)
+        if a.ndim == 1:
+            if a.size < n_segs:
+                raise ValueError(f"ir_idx needs {n_segs} entries")
+            stride = 0
+        elif a.ndim == 2 and a.shape[0] == self.n_streams and a.shape[1] >= n_segs:
+            stride = int(a.shape[1])
+        else:
+            raise ValueError(f"ir_idx: expected [{self.n_streams}][>= {n_segs}] or [>= {n_segs}], got {a.shape}")
+        m = self.IR_SWITCH[mode] if isinstance(mode, str) else int(mode)
+        self._check(self._lib.ohs_batch_process_ir_scheduled(
+            self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(stream_stride), int(channel_stride), int(seg_blocks),
+            a.ctypes.data_as(C.POINTER(C.c_uint32)), stride, m, C.c_void_p(hip_stream) if hip_stream else None))
+
+    def process_ir_scheduled(self, x, seg_blocks: int, ir_idx, mode="ring_out", out=None, hip_stream: int | None = None):
+        """process() with a schedule of HRIR sets per stream and segment of seg_blocks * 512 frames.  x, out as in process()."""
+        import torch
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, 2, frames]")
+        S, ch, frames = x.shape
+        if S != self.n_streams or ch != 2 or frames % BLOCK_SIZE:
+            raise ValueError(f"expected [{self.n_streams}, 2, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
+        if x.device.index != self.device:
+            raise ValueError("tensor is on a different device than the BatchProcessor")
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+            raise ValueError("out must match x")
+        if hip_stream is None:
+            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+        self.process_ir_scheduled_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, 2 * frames, frames, seg_blocks,
+                                      ir_idx, mode, hip_stream)
+        return out
+
     def join(self, hip_stream: int | None = None) -> None:
         """Make `hip_stream` (default: torch's current stream) wait for a pending deferred call."""
         if hip_stream is None:

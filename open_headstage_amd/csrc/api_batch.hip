@@ -223,7 +223,7 @@ int ohs_batch_reset(ohs_batch *b)
     ConvState &c = b->conv;
     HIP_TRY(hipMemsetAsync(c.d_hist, 0, c.S * (size_t)c.cap * NF * sizeof(float2), b->st));
     HIP_TRY(hipMemsetAsync(c.d_tails, 0, c.S * 2 * 8 * 64 * sizeof(float2), b->st));
-    c.tails_lazy = false;       // (the zeroed per-path overlaps are the state)
+    c.tails_lazy = false; c.tails_both = false;     // (the zeroed per-path overlaps are the state)
     c.lb_lazy = false; c.lb_valid = 0;
     c.pt_active = false;        // (pending tails belong to the frames in front of the reset)
     if (c.d_xhist) {            // (the block-2048 plan's state: zeros are what every path may see of the past)
@@ -243,19 +243,20 @@ int ohs_batch_reset(ohs_batch *b)
 
 static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
                               size_t stream_stride, size_t channel_stride, void *hip_stream, bool deferred,
-                              const BatchSchedule *sc);
+                              const BatchSchedule *sc, const ConvIrs *irs);
 
 // sc (optional): the schedule of ohs_batch_process_scheduled, its device copies already queued on hip_stream
+// irs (optional): the rows of ohs_batch_process_ir_scheduled, likewise
 static int batch_process_impl(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
                               size_t stream_stride, size_t channel_stride, void *hip_stream, bool deferred,
-                              const BatchSchedule *sc = nullptr)
+                              const BatchSchedule *sc = nullptr, const ConvIrs *irs = nullptr)
 {
     if (!b || !d_in || !d_out) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
     if (b->failed)
         return fail(OHS_ERR_HIP, "this batch failed in the middle of an earlier call (" + b->fail_msg +
                                      "): its per-stream state is half-advanced; ohs_batch_reset starts it afresh");
     const size_t spans_before = b->spans.size();
-    const int rc = batch_process_body(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, deferred, sc);
+    const int rc = batch_process_body(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, deferred, sc, irs);
     if (rc == OHS_OK || rc == OHS_ERR_INVALID_ARG) return rc;      // (argument errors are found before anything is queued)
     // A HIP call failed with part of the work queued.  Keep the message, then leave nothing dangling:
     const std::string why = g_err;
@@ -286,7 +287,7 @@ static int batch_process_impl(ohs_batch *b, const float *d_in, float *d_out, siz
 
 static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
                               size_t stream_stride, size_t channel_stride, void *hip_stream, bool deferred,
-                              const BatchSchedule *sc)
+                              const BatchSchedule *sc, const ConvIrs *irs)
 {
     if (n_blocks == 0) return OHS_OK;
     if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
@@ -337,6 +338,8 @@ static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, siz
     }
     ConvGains cg;
     if (sc && sc->d_gain) { cg.tab = sc->d_gain; cg.seg_blocks = (int)sc->seg_blocks; cg.stream_stride = (int)sc->gain_stride; }
+    ConvIrs ci;         // (every convolution launch is told where its first block lies in the call, as for the gains)
+    if (irs) ci = *irs;
 
     const long long ss = (long long)stream_stride, cs = (long long)channel_stride;
     int rc;
@@ -359,7 +362,7 @@ static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, siz
             return fail(OHS_ERR_HIP, "injected failure (ohs_debug_inject_batch_failure)");
 #endif
         rc = span_begin(st, 1); if (rc) return rc;
-        rc = conv_launch(b->conv, b->ctx, d_in, ss, cs, d_out, ss, cs, (int)n_blocks, b->gain, st, true, nullptr, nullptr, &cg);
+        rc = conv_launch(b->conv, b->ctx, d_in, ss, cs, d_out, ss, cs, (int)n_blocks, b->gain, st, true, nullptr, nullptr, &cg, &ci);
         if (rc) return rc;
         return span_end(st);
     }
@@ -449,8 +452,8 @@ static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, siz
                 b->spans.push_back(sp);
                 cv_a = sp.a; cv_b = sp.b;
             }
-            cg.blk_off = (int)blk0;
-            rc = conv_launch(b->conv, b->ctx, d_out + off, ss, cs, d_out + off, ss, cs, nb_i, b->gain, cst, true, cv_a, cv_b, &cg);
+            cg.blk_off = (int)blk0; ci.blk_off = (int)blk0;
+            rc = conv_launch(b->conv, b->ctx, d_out + off, ss, cs, d_out + off, ss, cs, nb_i, b->gain, cst, true, cv_a, cv_b, &cg, &ci);
             if (rc) return rc;
         }
         if (nch > 1 && deferred) {
@@ -698,6 +701,116 @@ int ohs_batch_process_scheduled_streams(ohs_batch *b, const float *d_in, float *
     if (hipEventRecord(slot.done, st) == hipSuccess) slot.in_use = true;
     else hipStreamSynchronize(st);
     return rc;
+}
+
+// ---- a schedule of HRIR sets inside one call -------------------------------------------------------------------
+int ohs_batch_set_schedule_irs(ohs_batch *b, size_t n_sets, const float *irs, size_t len)
+{
+    if (!b) return fail(OHS_ERR_INVALID_ARG, "batch is NULL");
+    if (n_sets > 0 && !irs) return fail(OHS_ERR_INVALID_ARG, "irs is NULL");
+    if (n_sets > 0 && (len == 0 || len > (size_t)BS)) return fail(OHS_ERR_INVALID_ARG, "len must be 1 .. 512 (one partition)");
+    if (n_sets > ((size_t)1 << 16)) return fail(OHS_ERR_INVALID_ARG, "n_sets too large");
+    HIP_TRY(hipSetDevice(b->device));
+    DeviceWideSection dws;
+    HIP_TRY(hipDeviceSynchronize());
+    return conv_set_schedule_irs(b->conv, b->ctx, n_sets, irs, len, b->st);
+}
+
+int ohs_batch_last_conv_ir_scheduled(const ohs_batch *b, int *scheduled)
+{
+    if (!b || !scheduled) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    *scheduled = b->conv.last_ir_scheduled ? 1 : 0;
+    return OHS_OK;
+}
+
+int ohs_batch_process_ir_scheduled(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
+                                   size_t channel_stride, size_t seg_blocks, const unsigned *ir_idx, size_t idx_stride,
+                                   int switch_mode, void *hip_stream)
+{
+    if (!b || !d_in || !d_out || !ir_idx) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    if (seg_blocks == 0) return fail(OHS_ERR_INVALID_ARG, "seg_blocks is 0");
+    if (switch_mode != OHS_IR_SWITCH_RING_OUT && switch_mode != OHS_IR_SWITCH_CUT)
+        return fail(OHS_ERR_INVALID_ARG, "switch_mode must be OHS_IR_SWITCH_RING_OUT or OHS_IR_SWITCH_CUT");
+    if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
+    ConvState &c = b->conv;
+    if (c.irs_n == 0) return fail(OHS_ERR_INVALID_ARG, "no sets uploaded (ohs_batch_set_schedule_irs)");
+    if (conv_max_p(c) != 1)
+        return fail(OHS_ERR_INVALID_ARG, "the handle holds a response longer than one partition (512 taps): not supported in a schedule");
+    if (c.pt_active) return fail(OHS_ERR_INVALID_ARG, "the handle has pending tails of a longer response: not supported in a schedule");
+    if (!c.lazy_ok) return fail(OHS_ERR_INVALID_ARG, "the handle does not keep the lazy state the scheduled kernel leaves");
+    seg_blocks = std::min(seg_blocks, std::max<size_t>(n_blocks, 1));
+    const size_t n_segs = (n_blocks + seg_blocks - 1) / seg_blocks, S = c.S;
+    if (idx_stride != 0 && idx_stride < n_segs)
+        return fail(OHS_ERR_INVALID_ARG, "idx_stride is 0 (one row for all streams) or >= the number of segments");
+    if (S * n_segs > (size_t)0x7fffffff) return fail(OHS_ERR_INVALID_ARG, "schedule too large");
+    // one pass over the rows: the range check, whether anything varies along a row, whether the rows differ
+    const size_t rows = idx_stride ? S : 1;
+    bool vary = false, rows_differ = false;
+    for (size_t r = 0; r < rows; ++r) {
+        const unsigned *row = ir_idx + r * idx_stride;
+        for (size_t k = 0; k < n_segs; ++k) {
+            if (row[k] >= c.irs_n) return fail(OHS_ERR_INVALID_ARG, "ir_idx entry out of range");
+            vary = vary || row[k] != row[0];
+            rows_differ = rows_differ || row[k] != ir_idx[k];
+        }
+    }
+    if (b->failed || n_blocks == 0)     // (the plain call's answers)
+        return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
+    {
+        const size_t frames = n_blocks * BS;
+        if (channel_stride < frames || (S > 1 && stream_stride < 2 * frames && stream_stride < channel_stride + frames))
+            return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const bool cut = switch_mode == OHS_IR_SWITCH_CUT, shared = idx_stride == 0;
+    if (shared && !vary) {
+        // One set throughout, for all streams: the plain kernel on that set's table -- the plain call's launches and bits.  The overlaps
+        // at rest belong to the responses that go: under RING_OUT they are computed now (and ring out), under CUT the call's start is a
+        // boundary and they are zero, as after four set_ir.
+        if (cut) {
+            HIP_TRY(hipMemsetAsync(c.d_tails, 0, S * 2 * 8 * 64 * sizeof(float2), st));
+            c.tails_lazy = false; c.tails_both = false;
+        } else {
+            const int rcm = conv_materialise_keep_lazy(c, b->ctx, st);
+            if (rcm) return rcm;
+        }
+        const int rca = conv_adopt_schedule_set(c, ir_idx[0], st);
+        if (rca) return rca;
+        return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
+    }
+    // the rows' staging slot (ohs_batch_process_scheduled's): rows packed n_segs apart; equal rows travel as one
+    const size_t n_tab = (rows_differ ? S : 1) * n_segs;
+    ohs_batch::SchedSlot &slot = b->sched_slot[b->sched_next];
+    b->sched_next = (b->sched_next + 1) % ohs_batch::kSchedSlots;
+    if (slot.in_use) HIP_TRY(hipEventSynchronize(slot.done));
+    slot.in_use = false;
+    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    if (2 * slot.cap < n_tab) {
+        if (slot.h) hipHostFree(slot.h);
+        if (slot.d) {
+            DeviceWideSection dws;
+            hipFree(slot.d);
+        }
+        slot.h = nullptr; slot.d = nullptr; slot.cap = 0;
+        const size_t cap = std::max<size_t>(1024, n_tab / 2 + n_tab / 4 + 1);
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&slot.h), 2 * cap * sizeof(unsigned), hipHostMallocDefault));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&slot.d), 2 * cap * sizeof(unsigned)));
+        slot.cap = cap;
+    }
+    for (size_t r = 0; r < (rows_differ ? S : 1); ++r) std::memcpy(slot.h + r * n_segs, ir_idx + r * idx_stride, n_segs * sizeof(unsigned));
+    HIP_TRY(hipMemcpyAsync(slot.d, slot.h, n_tab * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    ConvIrs ci;
+    ci.tab = slot.d; ci.seg_blocks = (int)seg_blocks; ci.stream_stride = rows_differ ? (int)n_segs : 0; ci.call_blocks = (int)n_blocks;
+    ci.cut = cut;
+    ci.per_stream_state = !shared;      // (a shared row is adopted below: the handle's spectra rebuild the overlaps when asked)
+    const int rc = batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false, nullptr, &ci);
+    if (hipEventRecord(slot.done, st) == hipSuccess) slot.in_use = true;
+    else hipStreamSynchronize(st);
+    if (rc) return rc;
+    // one row for all streams: the handle's responses ARE the last segment's now (what ohs_batch_process_scheduled does with its table)
+    if (shared) return conv_adopt_schedule_set(c, ir_idx[n_segs - 1], st);
+    return OHS_OK;
 }
 
 int ohs_batch_process_deferred(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,

@@ -18,6 +18,7 @@ struct ConvCall {
     // a gain per segment instead (ConvGains; device memory): frames of block t leave with tab[(off + t) / seg]
     // (gain_stream: stream s reads its row at gain_tab + s * gain_stream; 0 = one row for all)
     const float *gain_tab = nullptr; int gain_seg = 1, gain_off = 0, gain_stream = 0;
+    const ConvIrs *irs = nullptr;       // a set of responses per segment and stream (k_conv_p1_irs)
 };
 
 // right before the handle is deleted: the buffers only
@@ -28,7 +29,7 @@ void conv_free(ConvState &c)
     for (void *d : std::initializer_list<void *>{c.d_hist, c.d_pre, c.d_tails, c.d_tails_alt, c.d_cd, c.d_chunk_tails, c.d_cdm, c.d_W,
                                                  c.d_W1, c.d_merged, c.d_merged_alt, c.d_last_in, c.d_irt, c.d_cd_os, c.d_irl,
                                                  c.d_xhist, c.d_xhist_alt, c.d_lb_ring, c.d_lb_cd, c.d_lb_ab, c.d_lb_cd_alt,
-                                                 c.d_xb_cd, c.d_xb_ab, c.d_ptail, c.d_ptail_alt})
+                                                 c.d_xb_cd, c.d_xb_ab, c.d_ptail, c.d_ptail_alt, c.d_irs_cd, c.d_irs_H, c.d_irs_t})
         if (d) hipFree(d);
 }
 
@@ -118,7 +119,17 @@ int conv_materialise_state(ConvState &c, DeviceCtx *ctx, hipStream_t st)
         if (rc) return rc;
     }
     if (!c.tails_lazy) return OHS_OK;
-    ConvP1Args a;
+    if (!c.tails_both) {        // (else d_tails is current already)
+        const int rc = conv_materialise_keep_lazy(c, ctx, st);
+        if (rc) return rc;
+    }
+    c.tails_lazy = false; c.tails_both = false;
+    return OHS_OK;
+}
+
+// arguments of the state kernels on the lazy state: block 0 of d_last_in -> d_tails
+static void conv_state_args(const ConvState &c, const DeviceCtx *ctx, ConvP1Args &a)
+{
     std::memset(&a, 0, sizeof(a));
     a.in = c.d_last_in; a.in_stream_stride = 2 * (long long)BS; a.in_ch_stride = (long long)BS;
     a.n_blocks = 1; a.n_streams = (int)c.S;
@@ -126,9 +137,16 @@ int conv_materialise_state(ConvState &c, DeviceCtx *ctx, hipStream_t st)
     a.tails_out = c.d_tails;
     a.tw = ctx->d_tw; a.fp_mode = c.fp_mode;
     a.xcd_lo = 0; a.xcd_n = 8;
+}
+
+int conv_materialise_keep_lazy(ConvState &c, DeviceCtx *ctx, hipStream_t st)
+{
+    if (!c.tails_lazy || c.tails_both) return OHS_OK;
+    ConvP1Args a;
+    conv_state_args(c, ctx, a);
     hipError_t e = launch_conv_p1_state(a, st);
     if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_state launch: ") + hipGetErrorString(e));
-    c.tails_lazy = false;
+    c.tails_both = true;
     return OHS_OK;
 }
 
@@ -632,6 +650,68 @@ int conv_set_ir(ConvState &c, DeviceCtx *ctx, int path, const float *ir, size_t 
     return OHS_OK;
 }
 
+// The set table of the IR-scheduled call.  Per set: the four spectra by k_ir_spectrum (all sets' paths in one launch: the padded
+// responses lie 512 apart, one "partition" each), (C, D) by k_build_cd -- the kernels set_ir and the plain call use, so that a
+// block convolved with set i has the bits of a plain call on a handle that loaded set i --, then the block loop's layout once.
+int conv_set_schedule_irs(ConvState &c, DeviceCtx *ctx, size_t n_sets, const float *irs, size_t len, hipStream_t st)
+{
+    DeviceWideSection dws;      // (frees below)
+    for (void *d : std::initializer_list<void *>{c.d_irs_cd, c.d_irs_H, c.d_irs_t})
+        if (d) hipFree(d);
+    c.d_irs_cd = nullptr; c.d_irs_H = nullptr; c.d_irs_t = nullptr; c.irs_n = 0;
+    if (n_sets == 0) return OHS_OK;
+    std::vector<float> padded(n_sets * 4 * (size_t)BS, 0.0f);
+    for (size_t r = 0; r < n_sets * 4; ++r) std::memcpy(&padded[r * BS], irs + r * len, len * sizeof(float));
+    float2 *d_cd = nullptr;     // [n_sets][2][1024] scratch
+    auto body = [&]() -> int {
+        HIP_TRY(hipMalloc(&c.d_irs_t, padded.size() * sizeof(float)));
+        HIP_TRY(hipMalloc(&c.d_irs_H, n_sets * 4 * (size_t)NF * sizeof(float2)));
+        HIP_TRY(hipMalloc(&c.d_irs_cd, n_sets * (size_t)NF * sizeof(float4)));
+        HIP_TRY(hipMalloc(&d_cd, n_sets * 2 * (size_t)NF * sizeof(float2)));
+        HIP_TRY(hipMemcpyAsync(c.d_irs_t, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(launch_ir_spectrum(c.d_irs_t, (int)padded.size(), (int)(n_sets * 4), c.d_irs_H, ctx->d_tw, st));
+        for (size_t i = 0; i < n_sets; ++i) {
+            const float2 *h = c.d_irs_H + i * 4 * (size_t)NF;
+            HIP_TRY(launch_build_cd(h, h + NF, h + 2 * NF, h + 3 * NF, d_cd + i * 2 * (size_t)NF, st));
+        }
+        HIP_TRY(launch_irs_tables(d_cd, (int)n_sets, c.d_irs_cd, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return OHS_OK;
+    };
+    int rc = body();
+    if (d_cd) hipFree(d_cd);
+    // (a shared-row call adopts a set's taps into the time-domain copies the large-transform plans build their tables from)
+    if (rc == OHS_OK && c.lazy_ok) rc = conv_lb_irl_reserve(c, lb_p2pad_for(1) * kLbBlock, st);
+    if (rc) {
+        for (void *d : std::initializer_list<void *>{c.d_irs_cd, c.d_irs_H, c.d_irs_t})
+            if (d) hipFree(d);
+        c.d_irs_cd = nullptr; c.d_irs_H = nullptr; c.d_irs_t = nullptr;
+        return rc;
+    }
+    c.irs_n = n_sets;
+    return OHS_OK;
+}
+
+// What four set_ir calls would load, without their resets: spectra, time-domain copies, every derived table invalid.
+int conv_adopt_schedule_set(ConvState &c, size_t set, hipStream_t st)
+{
+    if (set >= c.irs_n || conv_max_p(c) != 1) return fail(OHS_ERR_INVALID_ARG, "no such set, or a response longer than one partition");
+    c.pre_cnt = ~0ull;
+    for (int p = 0; p < 4; ++p) {
+        const size_t row = set * 4 + (size_t)p;
+        HIP_TRY(hipMemcpyAsync(c.d_H[p], c.d_irs_H + row * NF, NF * sizeof(float2), hipMemcpyDeviceToDevice, st));
+        if (c.d_irt) HIP_TRY(hipMemcpyAsync(c.d_irt + p * BS, c.d_irs_t + row * BS, BS * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (c.d_irl && c.irl_len >= BS) {
+            HIP_TRY(hipMemsetAsync(c.d_irl + (size_t)p * c.irl_len, 0, (size_t)c.irl_len * sizeof(float), st));
+            HIP_TRY(hipMemcpyAsync(c.d_irl + (size_t)p * c.irl_len, c.d_irs_t + row * BS, BS * sizeof(float), hipMemcpyDeviceToDevice, st));
+        }
+        c.spk_set[p] = false;
+    }
+    c.cd_valid = false; c.cd_os_valid = false; c.cdm_valid = false;
+    c.lb_cd_valid = false; c.lb_tables_gen++;
+    return OHS_OK;
+}
+
 // Chunks per stream of the P = 1 kernel: at least ONE round of resident waves (CUs x 16), and a wave count S * K that
 // FILLS its last round -- all waves of a launch take the same time, so 2.13 rounds cost 3 (1024 and 2048 streams with
 // K = ceil(2 R / S) ran at 71 % for that reason).  K is the smallest value from ceil(R / S) upwards whose last round is
@@ -742,7 +822,8 @@ static ConvPlan conv_choose_plan(const ConvState &c, const DeviceCtx *ctx, const
                            ((k.in_ss | k.in_cs | k.out_ss | k.out_cs) & 1) == 0 &&
                            ((reinterpret_cast<uintptr_t>(k.in) | reinterpret_cast<uintptr_t>(k.out)) & 7) == 0 &&
                            (unsigned long long)k.n_blocks * BS + 1536ull < (1ull << 31);
-        if (os_ok && (c.conv_plan == 2 || (c.conv_plan == 0 && conv_plan_auto_is_os(c.S, k.n_blocks, k.in == k.out)))) {
+        // (a schedule of impulse responses is always the block-512 family's: the hop-1536 windows straddle segment boundaries)
+        if (!k.irs && os_ok && (c.conv_plan == 2 || (c.conv_plan == 0 && conv_plan_auto_is_os(c.S, k.n_blocks, k.in == k.out)))) {
             plan.kernel = OHS_CONV_KERNEL_HOP1536_P1;
             plan.K = conv_os_chunks(ctx, c.S, k.n_blocks, k.in == k.out);
             return plan;
@@ -751,6 +832,11 @@ static ConvPlan conv_choose_plan(const ConvState &c, const DeviceCtx *ctx, const
         plan.xcd_lo = c.xcd_lo; plan.xcd_n = c.xcd_n;
         if (tn.p1_xcd_n > 0) { plan.xcd_lo = tn.p1_xcd_lo; plan.xcd_n = tn.p1_xcd_n; }
         plan.K = (int)conv_p1_chunks(ctx, c.S, k.n_blocks, tn.p1_target_waves, plan.xcd_n);
+        if (k.irs) {    // k_conv_p1_irs has no pre-pass: 1 chunk, or 2 / 4 / 8 / 16 that compute their own boundary tails
+            int K = 16;
+            while (K > plan.K) K >>= 1;
+            plan.K = K;
+        }
         return plan;
     }
     if (allow_fast && c.d_xhist && Pmax >= lb_min_p()) {
@@ -813,8 +899,9 @@ static int conv_p1_build_cd(ConvState &c, hipStream_t st)
 static int conv_run_p1(ConvState &c, DeviceCtx *ctx, const ConvCall &k, const ConvPlan &plan, hipStream_t st,
                        hipEvent_t ev_start, hipEvent_t ev_stop, int &ranges)
 {
-    int rc = conv_p1_build_cd(c, st);
+    int rc = k.irs ? OHS_OK : conv_p1_build_cd(c, st);
     if (rc) return rc;
+    if (k.irs && (!c.lazy_ok || !c.d_irs_cd)) return fail(OHS_ERR_HIP, "IR-scheduled launch without the lazy state or the set table");
     const Tuning &tn = tuning();
     const int K = plan.K;
     if ((size_t)K > c.chunk_tails_cap) {
@@ -839,7 +926,7 @@ static int conv_run_p1(ConvState &c, DeviceCtx *ctx, const ConvCall &k, const Co
     a.xcd_lo = plan.xcd_lo; a.xcd_n = plan.xcd_n;
     {   // boundary tails by the chunks' own waves where a stream's chunks share a workgroup (else: the pre-pass)
         const bool allowed = conv_p1_waves_per_cu() == 16 && (K == 2 || K == 4 || K == 8 || K == 16);
-        a.own_tails = (allowed && tn.p1_own_tails) ? 1 : 0;
+        a.own_tails = (allowed && (tn.p1_own_tails || k.irs)) ? 1 : 0;
     }
     a.stagger = tn.p1_stagger;
     a.prio_mode = tn.p1_prio;
@@ -852,7 +939,15 @@ static int conv_run_p1(ConvState &c, DeviceCtx *ctx, const ConvCall &k, const Co
     const int wmax = std::max(std::max(kw[0], kw[1]), std::max(kw[2], kw[3]));
     const bool weighted = (long long)k.n_blocks * wmin >= 2ll * K * wmax;
     for (int g = 0; g < 4; ++g) a.weights[g] = weighted ? kw[g] : 1;
-    hipError_t e = launch_conv_p1(a, st, ev_start, ev_stop);
+    hipError_t e;
+    if (k.irs) {
+        ConvIrArgs i;
+        i.cd = c.d_irs_cd; i.H = c.d_irs_H; i.tab = k.irs->tab;
+        i.seg = k.irs->seg_blocks; i.off = k.irs->blk_off; i.stream = k.irs->stream_stride; i.cut = k.irs->cut ? 1 : 0;
+        e = launch_conv_p1_irs(a, i, st, ev_start, ev_stop);
+    } else {
+        e = launch_conv_p1(a, st, ev_start, ev_stop);
+    }
     if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1 launch: ") + hipGetErrorString(e));
     if (c.lazy_ok) {
         std::swap(c.d_merged, c.d_merged_alt);
@@ -1016,7 +1111,7 @@ static int conv_run_tp(ConvState &c, DeviceCtx *ctx, const ConvCall &k, const Co
 
 int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
                 float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st,
-                bool allow_fast, hipEvent_t ev_start, hipEvent_t ev_stop, const ConvGains *gains)
+                bool allow_fast, hipEvent_t ev_start, hipEvent_t ev_stop, const ConvGains *gains, const ConvIrs *irs)
 {
     // (ev_start / ev_stop: recorded at the start / completion of the call's launches)
     if (n_blocks <= 0) {                    // nothing to do (the pre-pass would index block -1)
@@ -1029,6 +1124,11 @@ int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, 
     // gain in -- there (a + b) * g instead of a * g + b * g).  The plan is chosen exactly as for the plain call.
     const bool seg_gains = gains != nullptr && gains->tab != nullptr;
     ConvCall k{in, in_ss, in_cs, out, out_ss, out_cs, n_blocks, seg_gains ? 1.0f : gain};
+    if (irs && irs->tab) {
+        if (conv_max_p(c) != 1 || !allow_fast || c.pt_active || seg_gains)
+            return fail(OHS_ERR_INVALID_ARG, "a schedule of impulse responses needs one-partition responses, no pending tails and no gain schedule");
+        k.irs = irs;
+    }
     const ConvPlan plan = conv_choose_plan(c, ctx, k, allow_fast);
     int ranges = 0, rc;
     if (plan.kernel == OHS_CONV_KERNEL_BLOCK512_P1) {
@@ -1056,6 +1156,20 @@ int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, 
     for (int p = 0; p < 4; ++p) c.since[p] += n_blocks;
     c.last_kernel = plan.kernel; c.last_ranges = ranges;
     c.kernel_calls[plan.kernel]++;
+    c.last_ir_scheduled = k.irs != nullptr;
+    c.tails_both = false;       // (d_tails belongs to the state in front of this launch)
+    if (k.irs && k.irs->per_stream_state && k.irs->blk_off + n_blocks == k.irs->call_blocks) {
+        // the call's last block has left the lazy state; the per-path overlaps under every stream's own last set, now, while the rows
+        // are at hand (conv_materialise_state would take the handle's spectra)
+        ConvP1Args a;
+        conv_state_args(c, ctx, a);
+        ConvIrArgs i;
+        i.cd = c.d_irs_cd; i.H = c.d_irs_H; i.tab = k.irs->tab;
+        i.seg = k.irs->seg_blocks; i.off = k.irs->call_blocks - 1; i.stream = k.irs->stream_stride; i.cut = 0;
+        hipError_t e = launch_conv_p1_state_irs(a, i, st);
+        if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_state_irs launch: ") + hipGetErrorString(e));
+        c.tails_both = true;
+    }
     if (c.pt_active) {
         // what the frames in front of a per-path set_ir still owe these frames (conv_lb_tail_route)
         const long long n = (long long)n_blocks * BS;

@@ -195,6 +195,17 @@ struct ConvState {
     // what served the last convolution launch (ohs_batch_last_conv_plan): OHS_CONV_KERNEL_*, and its ranges per stream
     int last_kernel = 0, last_ranges = 0;
     unsigned long long kernel_calls[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // conv_launch calls served per family (ohs_batch_conv_plan_counts)
+    // The set table of the IR-scheduled call (ohs_batch_set_schedule_irs): irs_n sets of four one-partition responses, as the (C, D)
+    // tables k_conv_p1_irs reads, as the four path spectra per set (the state kernel; what a shared-row call adopts into d_H) and in
+    // the time domain, zero-padded to 512 (what it adopts into d_irt / d_irl)
+    size_t irs_n = 0;
+    float4 *d_irs_cd = nullptr;     // [irs_n][1024]
+    float2 *d_irs_H = nullptr;      // [irs_n][4][1024]
+    float *d_irs_t = nullptr;       // [irs_n][4][512]
+    // tails_lazy && tails_both: d_tails holds the per-path overlaps too (computed behind an IR-scheduled call with a row per stream,
+    // where d_H could not rebuild them); the next launch clears it
+    bool tails_both = false;
+    bool last_ir_scheduled = false; // the last conv_launch looked the set up per block (ohs_batch_last_conv_ir_scheduled)
     // ohs_*_set_speakers: what it last loaded into each path (a set_ir from anywhere else forgets it), so that a
     // change of the speaker angles re-loads only the paths whose impulse response really changed
     std::vector<float> spk_ir[4];
@@ -250,10 +261,26 @@ struct ConvGains {
     int seg_blocks = 1, blk_off = 0;
     int stream_stride = 0;
 };
+// a set of impulse responses per segment and stream (device rows of indices into the handle's set table): block t of the launch,
+// block blk_off + t of a call of call_blocks blocks, is convolved with set tab[s * stream_stride + (blk_off + t) / seg_blocks].
+// cut: OHS_IR_SWITCH_CUT.  per_stream_state: behind the call's last block the per-path overlaps are computed from every stream's
+// own last set (rows per stream: d_H cannot rebuild them later).  Needs every path at one partition, the lazy state, no pending tails
+// (the batch entry point checks); always served by the block-512 family.
+struct ConvIrs {
+    const unsigned *tab = nullptr;
+    int seg_blocks = 1, blk_off = 0, stream_stride = 0, call_blocks = 0;
+    bool cut = false, per_stream_state = false;
+};
 int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
                 float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st,
                 bool allow_fast = true, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
-                const ConvGains *gains = nullptr);
+                const ConvGains *gains = nullptr, const ConvIrs *irs = nullptr);
+// the set table (host array irs[n_sets][4][len], 1 <= len <= 512; n_sets == 0 frees it); the caller has drained the device
+int conv_set_schedule_irs(ConvState &c, DeviceCtx *ctx, size_t n_sets, const float *irs, size_t len, hipStream_t st);
+// the handle's four responses become set `set` of the table, overlaps and history untouched (asynchronous on st)
+int conv_adopt_schedule_set(ConvState &c, size_t set, hipStream_t st);
+// the per-path overlaps from the lazy state with the CURRENT spectra, the lazy state kept valid beside them (tails_both)
+int conv_materialise_keep_lazy(ConvState &c, DeviceCtx *ctx, hipStream_t st);
 
 // ---- speaker angles -> four set_ir (the wiring the reference leaves open; speakers.cpp) ---------
 template <class SetIr>

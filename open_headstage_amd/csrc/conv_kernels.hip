@@ -1126,6 +1126,37 @@ __device__ __forceinline__ void p1_spectral_product_paired(const float2 (&z)[16]
     }
 }
 
+// The same product with (C, D) of the block's own set read from the device table of k_conv_p1_irs (cdp = the set's [16][64]
+// float4 in the paired layout + lane: every load of the wave is one contiguous KiB, an L2 hit for a table of some tens of
+// sets).  Four loads at a time: the 16 registers they need fit under the transform's peak, all sixteen would not.
+// Operation for operation the arithmetic of p1_spectral_product_paired.
+#ifndef OHS_P1_IRS_GROUP
+#define OHS_P1_IRS_GROUP 4
+#endif
+#ifndef OHS_P1_IRS_FENCE
+#define OHS_P1_IRS_FENCE __builtin_amdgcn_sched_barrier(0);
+#endif
+__device__ __forceinline__ void p1_spectral_product_paired_global(const float2 (&z)[16], float2 (&w)[16], const float4 *cdp, int lane)
+{
+    constexpr int G = OHS_P1_IRS_GROUP;
+    const bool lane32 = lane == 32;
+#pragma unroll
+    for (int g = 0; g < 16 / G; ++g) {
+        float4 q[G];
+        OHS_P1_IRS_FENCE
+#pragma unroll
+        for (int j = 0; j < G; ++j) q[j] = cdp[(G * g + j) * 64];
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            const int i = G * g + j;
+            const float2 zz = z[i], m = paired_mirror(z, i >> 2, i & 3, lane32);
+            const float2 c = make_float2(q[j].x, q[j].y), d = make_float2(q[j].z, q[j].w);
+            w[i].x = fmaf(m.y, d.y, fmaf(m.x, d.x, fmaf(-zz.y, c.y, zz.x * c.x)));
+            w[i].y = fmaf(-m.y, d.x, fmaf(m.x, d.y, fmaf(zz.y, c.x, zz.x * c.y)));
+        }
+    }
+}
+
 // First block of chunk ck of stream s.  Chunk (s, ck) is the work of wave (s * chunks + ck) % 16 of its workgroup,
 // and a wave's speed depends on that index: issue arbitration among the four waves of a SIMD is oldest first, so
 // waves 0..3 of a workgroup (the oldest of their SIMDs) run 2.3x as fast as waves 12..15 while all sixteen are
@@ -1210,7 +1241,22 @@ __device__ __forceinline__ long long p1_xcd_block(const ConvP1Args &A)
     return (long long)bid;
 }
 
-// k_conv_p1 and k_conv_p1_gains share one body (conv_p1_body.inc); they differ in where a block's gain comes from
+// k_conv_p1, k_conv_p1_gains and k_conv_p1_irs share one body (conv_p1_body.inc); they differ in where a block's gain and its
+// (C, D) table come from
+#define OHS_P1_TABLE_LDS(cd) \
+    {   /* C and D interleaved position by position: cd4[i] = (C[i], D[i]) -- i in the layout the block loop computes in */ \
+        float4 *dst = reinterpret_cast<float4 *>(cd); \
+        for (int i = threadIdx.x; i < kFft; i += 64 * kP1Waves) { \
+            const int src = paired_to_natural(i & 63, i >> 6); \
+            const float2 c = A.CD[src], d = A.CD[kFft + src]; \
+            dst[i] = make_float4(c.x, c.y, d.x, d.y); \
+        } \
+    }
+#define OHS_P1_TABLE(cd) OHS_P1_TABLE_LDS(cd)
+#define OHS_P1_LOOP_INIT
+#define OHS_P1_BLOCK_BEGIN(t)
+#define OHS_P1_BLOCK_END
+#define OHS_P1_PRODUCT(v, w) p1_spectral_product_paired(v, w, cd, lane);
 #define OHS_P1_GAIN A.gain
 #define OHS_P1_BLOCK_GAIN(t)
 __global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1(const ConvP1Args A)
@@ -1224,6 +1270,45 @@ __global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1_gains(const ConvP1Arg
 #include "conv_p1_body.inc"
 #undef OHS_P1_GAIN
 #undef OHS_P1_BLOCK_GAIN
+#undef OHS_P1_TABLE
+#undef OHS_P1_LOOP_INIT
+#undef OHS_P1_BLOCK_BEGIN
+#undef OHS_P1_BLOCK_END
+#undef OHS_P1_PRODUCT
+
+// k_conv_p1_irs (ohs_batch_process_ir_scheduled; kernels.h: ConvIrArgs): every wave follows its own stream's row of set indices.
+// Block t of the launch is block I.off + t of the call, in segment ir_k = (I.off + t) / I.seg at position ir_r -- two scalar counters,
+// so that no block pays a division; the index is one scalar load per block (the dry block in front of a chunk reads the set of ITS
+// block).  CUT: the overlap entering the first block of a run of equal indices is zero -- a wave-uniform select; the call's first block
+// starts a run (ir_prev = ~0 there), the first block of a later time chunk does not unless the row says so.  The LDS the plain kernel's
+// table occupies stays unused: the workgroup owns its CU either way.
+#define OHS_P1_TABLE(cd) (void)cd;
+#define OHS_P1_LOOP_INIT \
+    const unsigned *ir_row = I.tab + (size_t)s * (size_t)I.stream; \
+    int ir_k = __builtin_amdgcn_readfirstlane((I.off + t_first) / I.seg); \
+    int ir_r = __builtin_amdgcn_readfirstlane((I.off + t_first) - ir_k * I.seg); \
+    unsigned ir_prev = ir_k > 0 ? (unsigned)__builtin_amdgcn_readfirstlane((int)ir_row[ir_k - 1]) : 0xffffffffu;
+#define OHS_P1_BLOCK_BEGIN(t) \
+    const unsigned ir_idx = (unsigned)__builtin_amdgcn_readfirstlane((int)ir_row[ir_k]); \
+    if (I.cut && ir_r == 0 && ir_idx != ir_prev) { \
+        _Pragma("unroll") for (int a = 0; a < 8; ++a) tail[a] = make_float2(0.0f, 0.0f); \
+    } \
+    ir_prev = ir_idx; \
+    const float4 *cdp = I.cd + (size_t)ir_idx * kFft + lane;
+#define OHS_P1_BLOCK_END \
+    if (++ir_r == I.seg) { ir_r = 0; ++ir_k; }
+#define OHS_P1_PRODUCT(v, w) p1_spectral_product_paired_global(v, w, cdp, lane);
+#define OHS_P1_GAIN A.gain
+#define OHS_P1_BLOCK_GAIN(t)
+__global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1_irs(const ConvP1Args A, const ConvIrArgs I)
+#include "conv_p1_body.inc"
+#undef OHS_P1_GAIN
+#undef OHS_P1_BLOCK_GAIN
+#undef OHS_P1_TABLE
+#undef OHS_P1_LOOP_INIT
+#undef OHS_P1_BLOCK_BEGIN
+#undef OHS_P1_BLOCK_END
+#undef OHS_P1_PRODUCT
 
 // pre-pass, two small kernels that read INPUT frames only -- which is why they run before the main kernel stores over
 // them (in place) -- one transform pair per wave:
@@ -1237,18 +1322,10 @@ __global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1_gains(const ConvP1Arg
 // per-speaker spectra alive together: 128 VGPRs + 244 B of scratch per lane.  The output of every block now belongs to
 // the main kernel, and neither pre-pass kernel spills.
 constexpr int kP1StateWaves = 4;
-__global__ __launch_bounds__(64 * kP1StateWaves) void k_conv_p1_state(const ConvP1Args A)
+// one wave of k_conv_p1_state / k_conv_p1_state_irs: stream s, speaker spk, that speaker's two spectra ha, hb
+__device__ __forceinline__ void p1_state_wave(const ConvP1Args &A, int s, int spk, const float2 *ha, const float2 *hb,
+                                              float2 *lds, const float2 *tab, int lane)
 {
-    ohs_set_fp_mode(A.fp_mode);
-    extern __shared__ __attribute__((aligned(16))) float2 smem[];
-    float2 *tab = smem;
-    fill_twiddle_tables(tab, A.tw, threadIdx.x, 64 * kP1StateWaves);
-    __syncthreads();
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    float2 *lds = smem + kTabComplex + wave * kWaveLdsComplex;
-    const long long gw = (long long)blockIdx.x * kP1StateWaves + wave;
-    if (gw >= 2ll * A.n_streams) return;
-    const int s = (int)(gw >> 1), spk = (int)(gw & 1);
     const float *in_l = A.in + (size_t)s * A.in_stream_stride;
     const float *in_r = in_l + A.in_ch_stride;
     const unsigned base = (unsigned)(A.n_blocks - 1) * kBlock + lane;
@@ -1259,7 +1336,6 @@ __global__ __launch_bounds__(64 * kP1StateWaves) void k_conv_p1_state(const Conv
         v[a + 8] = make_float2(0.0f, 0.0f);
     }
     wave_fft_fwd_mirror(v, w, lds, tab, lane);
-    const float2 *ha = A.H[2 * spk], *hb = A.H[2 * spk + 1];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const float2 zm = w[r];
@@ -1276,6 +1352,40 @@ __global__ __launch_bounds__(64 * kP1StateWaves) void k_conv_p1_state(const Conv
     float2 *tails_out = A.tails_out + (size_t)s * (2 * 8 * 64) + (size_t)spk * (8 * 64);
 #pragma unroll
     for (int a = 0; a < 8; ++a) tails_out[a * 64 + lane] = make_float2(w[a + 8].x * scale, w[a + 8].y * scale);
+}
+
+__global__ __launch_bounds__(64 * kP1StateWaves) void k_conv_p1_state(const ConvP1Args A)
+{
+    ohs_set_fp_mode(A.fp_mode);
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    float2 *tab = smem;
+    fill_twiddle_tables(tab, A.tw, threadIdx.x, 64 * kP1StateWaves);
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    float2 *lds = smem + kTabComplex + wave * kWaveLdsComplex;
+    const long long gw = (long long)blockIdx.x * kP1StateWaves + wave;
+    if (gw >= 2ll * A.n_streams) return;
+    const int s = (int)(gw >> 1), spk = (int)(gw & 1);
+    p1_state_wave(A, s, spk, A.H[2 * spk], A.H[2 * spk + 1], lds, tab, lane);
+}
+
+// the same behind an IR-scheduled call with a row per stream: the spectra are those of the set the stream's LAST block used
+// (I.tab row entry I.off / I.seg: the host passes that block's index within the call as I.off), from the per-set table I.H
+__global__ __launch_bounds__(64 * kP1StateWaves) void k_conv_p1_state_irs(const ConvP1Args A, const ConvIrArgs I)
+{
+    ohs_set_fp_mode(A.fp_mode);
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    float2 *tab = smem;
+    fill_twiddle_tables(tab, A.tw, threadIdx.x, 64 * kP1StateWaves);
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    float2 *lds = smem + kTabComplex + wave * kWaveLdsComplex;
+    const long long gw = (long long)blockIdx.x * kP1StateWaves + wave;
+    if (gw >= 2ll * A.n_streams) return;
+    const int s = (int)(gw >> 1), spk = (int)(gw & 1);
+    const unsigned idx = (unsigned)__builtin_amdgcn_readfirstlane((int)I.tab[(size_t)s * (size_t)I.stream + (size_t)(I.off / I.seg)]);
+    const float2 *h = I.H + ((size_t)idx * 4 + 2 * spk) * kFft;
+    p1_state_wave(A, s, spk, h, h + kFft, lds, tab, lane);
 }
 
 __global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1_edges(const ConvP1Args A)
@@ -1376,6 +1486,57 @@ hipError_t launch_conv_p1(const ConvP1Args &a, hipStream_t st, hipEvent_t ev_sta
         if (e == hipSuccess && ev_stop) e = hipEventRecord(ev_stop, st);
         return e;
     }
+}
+
+// ---- the IR-scheduled sibling (ohs_batch_process_ir_scheduled) ------------------------------------------------------
+// (C, D) of every set in the block loop's own layout: dst[set][i] = (C[src], D[src]), src = paired_to_natural(i & 63, i >> 6),
+// from the sets' k_build_cd tables cd[set][2][1024] (1/N folded in there)
+__global__ void k_irs_tables(const float2 *__restrict__ cd, int n_sets, float4 *__restrict__ dst)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, set = blockIdx.y;
+    if (i >= kFft || set >= n_sets) return;
+    const float2 *t = cd + (size_t)set * 2 * kFft;
+    const int src = paired_to_natural(i & 63, i >> 6);
+    const float2 c = t[src], d = t[kFft + src];
+    dst[(size_t)set * kFft + i] = make_float4(c.x, c.y, d.x, d.y);
+}
+hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st)
+{
+    if (n_sets <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_irs_tables, dim3(kFft / 256, (unsigned)n_sets), dim3(256), 0, st, cd, n_sets, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv_p1_state_irs(const ConvP1Args &a, const ConvIrArgs &i, hipStream_t st)
+{
+    if (a.n_blocks <= 0 || a.n_streams <= 0 || !a.tails_out || !i.H || !i.tab || i.seg < 1) return hipErrorInvalidValue;
+    const size_t shmem_state = (kTabComplex + kP1StateWaves * kWaveLdsComplex) * sizeof(float2);
+    const long long waves = 2ll * a.n_streams;
+    hipLaunchKernelGGL(k_conv_p1_state_irs, dim3((unsigned)((waves + kP1StateWaves - 1) / kP1StateWaves)),
+                       dim3(64 * kP1StateWaves), shmem_state, st, a, i);
+    return hipGetLastError();
+}
+
+// One kernel, no pre-pass: the launch leaves the lazy state (merged_out + last_in) and its chunks compute their own boundary
+// tails (chunks 1, 2, 4, 8 or 16: own_tails) -- neither k_conv_p1_state nor k_conv_p1_edges would know a block's set.
+hipError_t launch_conv_p1_irs(const ConvP1Args &a, const ConvIrArgs &i, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop)
+{
+    if (a.n_blocks <= 0 || a.n_streams <= 0 || a.chunks < 1 || a.chunks > a.n_blocks) return hipErrorInvalidValue;
+    if ((unsigned long long)a.n_blocks * kBlock >= (1ull << 32)) return hipErrorInvalidValue;   // 32-bit frame offsets
+    if (a.xcd_n < 1 || a.xcd_n > 8 || a.xcd_lo < 0 || a.xcd_lo + a.xcd_n > 8) return hipErrorInvalidValue;
+    if (!a.merged_out || !a.last_in) return hipErrorInvalidValue;
+    if (!i.cd || !i.tab || i.seg < 1 || i.off < 0 || i.stream < 0) return hipErrorInvalidValue;
+    if (a.chunks == 1 ? a.own_tails != 0 : !(a.own_tails && kP1Waves == 16 && (a.chunks == 2 || a.chunks == 4 || a.chunks == 8 || a.chunks == 16)))
+        return hipErrorInvalidValue;
+    const size_t shmem_main = (kTabComplex + 2 * kFft + kP1Waves * kWaveLdsComplex) * sizeof(float2);
+    static std::atomic<unsigned long long> lds_ok{0};
+    hipError_t e = allow_large_lds(reinterpret_cast<const void *>(k_conv_p1_irs), shmem_main, lds_ok);
+    if (e != hipSuccess) return e;
+    const long long waves = (long long)a.n_streams * a.chunks;
+    const dim3 grid(xcd_grid((unsigned)((waves + kP1Waves - 1) / kP1Waves), a.xcd_n));
+    if (ev_start || ev_stop) hipExtLaunchKernelGGL(k_conv_p1_irs, grid, dim3(64 * kP1Waves), shmem_main, st, ev_start, ev_stop, 0, a, i);
+    else hipLaunchKernelGGL(k_conv_p1_irs, grid, dim3(64 * kP1Waves), shmem_main, st, a, i);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------

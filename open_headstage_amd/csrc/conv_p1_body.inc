@@ -2,6 +2,12 @@
 //   k_conv_p1        OHS_P1_GAIN = A.gain, OHS_P1_BLOCK_GAIN(t) empty: the kernel as it has always been
 //   k_conv_p1_gains  a gain per segment (ohs_batch_process_scheduled): OHS_P1_BLOCK_GAIN(t) reads the gain of block t's segment
 //                    from A.gain_tab -- wave-uniform, one scalar load per block -- into the variable OHS_P1_GAIN names
+//   k_conv_p1_irs    a set of impulse responses per segment and stream (ohs_batch_process_ir_scheduled): no (C, D) table in LDS;
+//                    OHS_P1_BLOCK_BEGIN(t) reads the set index of block t's segment -- wave-uniform, one scalar load per block --,
+//                    zeroes the incoming overlap at a run's first block in the CUT mode, and OHS_P1_PRODUCT takes (C, D) of that
+//                    set from the device table I.cd
+// The hooks the includer defines: OHS_P1_TABLE(cd) fills the LDS table, OHS_P1_LOOP_INIT runs once in front of the block loop,
+// OHS_P1_BLOCK_BEGIN(t) / OHS_P1_BLOCK_END at the loop's top and bottom, OHS_P1_PRODUCT(v, w) is the spectral product.
 // Textual inclusion, so that the plain kernel's code does not depend on the other one's existence.
 {
     const long long wg = p1_xcd_block(A);
@@ -12,14 +18,7 @@
     float2 *tab = smem;
     float2 *cd = smem + kTabComplex;                    // [2][16][64]
     fill_twiddle_tables(tab, A.tw, threadIdx.x, 64 * kP1Waves);
-    {   // C and D interleaved position by position: cd4[i] = (C[i], D[i]) -- i in the layout the block loop computes in
-        float4 *dst = reinterpret_cast<float4 *>(cd);
-        for (int i = threadIdx.x; i < kFft; i += 64 * kP1Waves) {
-            const int src = paired_to_natural(i & 63, i >> 6);
-            const float2 c = A.CD[src], d = A.CD[kFft + src];
-            dst[i] = make_float4(c.x, c.y, d.x, d.y);
-        }
-    }
+    OHS_P1_TABLE(cd)
     __syncthreads();
     // wave-uniform quantities are forced into SGPRs: stream, chunk, block range and the four audio base
     // pointers then cost no VGPRs and the address arithmetic runs on the scalar unit
@@ -97,8 +96,10 @@
     const int age_rank = wave >> 2;
     int prio_phase = age_rank;
     const PairedPlan plan = paired_plan(lane);
+    OHS_P1_LOOP_INIT
     for (int t = t_first; t < b1; ++t) {
         const bool dry = t < b0;            // the block in front of the range: its overlap is all that is wanted
+        OHS_P1_BLOCK_BEGIN(t)
         if (A.prio_mode == 1) {
             switch (prio_phase & 3) {       // (s_setprio takes an immediate)
             case 0: __builtin_amdgcn_s_setprio(0); break;
@@ -121,7 +122,7 @@
         }
         float2 w[16];
         wave_fft_fwd_paired(v, lds, tab, lane, plan);
-        p1_spectral_product_paired(v, w, cd, lane);
+        OHS_P1_PRODUCT(v, w)
         // the prefetch of block t + 1 needs no guard except behind the launch's last block, where it re-reads that
         // block (its own frames: in bounds; the values are never used)
         const int adv = (t + 1 < A.n_blocks) ? kBlock : 0;
@@ -140,6 +141,7 @@
 #pragma unroll
         for (int a = 0; a < 8; ++a) tail[a] = w[a + 8];
         ql += kBlock; qr += kBlock;
+        OHS_P1_BLOCK_END
     }
     if (A.merged_out && b1 == A.n_blocks) {         // lazy state: the merged overlap the launch leaves behind
         float2 *mo = A.merged_out + (size_t)s * (8 * 64);

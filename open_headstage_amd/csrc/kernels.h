@@ -238,6 +238,25 @@ hipError_t launch_conv_p1(const ConvP1Args &a, hipStream_t st, hipEvent_t ev_sta
 // k_conv_p1_state alone: the per-path overlaps block n_blocks - 1 of a.in leaves behind -> a.tails_out
 hipError_t launch_conv_p1_state(const ConvP1Args &a, hipStream_t st);
 int conv_p1_waves_per_cu();      // resident waves of k_conv_p1 per CU (one workgroup)
+// A set of four impulse responses per segment and stream (ohs_batch_process_ir_scheduled): k_conv_p1_irs, the block loop of
+// k_conv_p1 with the (C, D) table of every block looked up by the stream's row of set indices -- block t of the launch, block
+// off + t of the call, uses set tab[s * stream + (off + t) / seg].  A second kernel argument, so that ConvP1Args and with it
+// k_conv_p1 stay what they are.
+struct ConvIrArgs {
+    const float4 *cd;           // [set][1024] (C[i], D[i]), i in the block loop's paired layout, 1/N folded in (launch_irs_tables)
+    const float2 *H;            // [set][4][1024] the sets' four path spectra (k_conv_p1_state_irs)
+    const unsigned *tab;        // rows of set indices (device memory)
+    int seg, off;               // blocks per segment; the launch's first block within the call
+    int stream;                 // stream s reads its row at tab + s * stream (0: one row for all streams)
+    int cut;                    // 1: the overlap entering the first block of a run of equal indices (and of the call) is zero
+};
+// the main kernel alone (a.merged_out / a.last_in set: the lazy state; a.chunks 1, or 2 / 4 / 8 / 16 with a.own_tails)
+hipError_t launch_conv_p1_irs(const ConvP1Args &a, const ConvIrArgs &i, hipStream_t st, hipEvent_t ev_start = nullptr,
+                              hipEvent_t ev_stop = nullptr);
+// the per-path overlaps block a.n_blocks - 1 of a.in leaves behind under the set of call block i.off of every stream's row -> a.tails_out
+hipError_t launch_conv_p1_state_irs(const ConvP1Args &a, const ConvIrArgs &i, hipStream_t st);
+// cd[set][2][1024] (launch_build_cd per set) -> dst[set][1024] in the block loop's layout
+hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st);
 // CD[0][..] = (A - jB)/2, CD[1][..] = (A + jB)/2 from four single-partition spectra
 hipError_t launch_build_cd(const float2 *h0, const float2 *h1, const float2 *h2, const float2 *h3,
                            float2 *cd, hipStream_t st);
