@@ -503,8 +503,39 @@ enum { OHS_IR_SWITCH_RING_OUT = 0, OHS_IR_SWITCH_CUT = 1 };
 int  ohs_batch_process_ir_scheduled(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
                                     size_t channel_stride, size_t seg_blocks, const unsigned *ir_idx, size_t idx_stride,
                                     int switch_mode, void *hip_stream);
-/* whether the handle's most recent convolution launch looked the set up per block inside the kernel (k_conv_p1_irs) */
+/* whether the handle's most recent convolution launch looked the set up per block inside the kernel: 0 no, 1 k_conv_p1_irs,
+ * 2 the crossfading kernel k_conv_p1_irs_xf (ohs_batch_process_ir_crossfaded) */
 int  ohs_batch_last_conv_ir_scheduled(const ohs_batch *b, int *scheduled);
+/* ---- the same schedule with a crossfade at segment boundaries ----
+ * Both switch modes above change the direct part of the response between two consecutive samples: a step in the signal at every
+ * boundary.  ohs_batch_process_ir_crossfaded walks the same table of sets by the same rows (segments, ir_idx, idx_stride, the table
+ * of ohs_batch_set_schedule_irs, asynchrony and in-place use exactly as in ohs_batch_process_ir_scheduled) and fades from the old
+ * set to the new one over the first block of the new segment, 512 frames (10.7 ms at 48 kHz; the length is fixed).
+ *   Per stream and block: block t has the set of its segment, cur, and a set it fades from, old: cur where t is not the first
+ *     block of a segment; the set of segment k - 1 where t is the first block of segment k > 0; in the first block of the call
+ *     prev_idx[s] where prev_idx is given (one entry when idx_stride == 0, else one per stream; host array, reusable on return),
+ *     cur where prev_idx is NULL -- the call's start is then no boundary, as under OHS_IR_SWITCH_RING_OUT.
+ *   old == cur: the block is OHS_IR_SWITCH_RING_OUT's block, the same arithmetic, the same bits.
+ *   old != cur: with f[n] = n / 512 and g[n] = (512 - n) / 512, n = 0 .. 511 (exact in f32), x_old = x * g is convolved with all
+ *     four paths of old and x_new = x * f with all four of cur, each the full 1023-frame response.  The block's 512 frames are the
+ *     sum of both heads plus the incoming overlap, times the gain; the overlap it leaves is the sum of both tails.  Nothing is cut:
+ *     every tail rings out.  The call's output is RING_OUT(x_new, or x off the boundary blocks; the rows) + RING_OUT(x_old, or 0;
+ *     the rows moved one segment on).
+ *   State after the call: the rules of ohs_batch_process_ir_scheduled -- one row for all streams: the handle adopts the last
+ *     segment's set; a row per stream: the handle's responses are untouched; merged and per-path overlaps are kept for both.  Where
+ *     the call's LAST block fades (seg_blocks == 1, a last segment of one block, a one-block call with prev_idx), the per-path
+ *     overlaps are those of both halves of the fade, summed per path: a later ohs_batch_set_ir of one path drops exactly that
+ *     path's tail and the other three ring out.
+ *   A call without any boundary -- every row constant, prev_idx NULL or equal to the rows' first entries -- IS
+ *     ohs_batch_process_ir_scheduled(OHS_IR_SWITCH_RING_OUT) on the same rows: its launches, its bits,
+ *     ohs_batch_last_conv_ir_scheduled 0 or 1.  Any other call is served by the crossfading kernel, one launch per time chunk
+ *     whatever the number of segments or streams, always the block-512 family; ohs_batch_last_conv_ir_scheduled 2.
+ *   This schedule does not combine with the EQ and gain schedules in one call; responses stay within one partition.
+ * OHS_ERR_INVALID_ARG, before anything is queued (the handle stays usable): everything ohs_batch_process_ir_scheduled refuses
+ * (there is no switch mode here), and a prev_idx entry >= n_sets. */
+int  ohs_batch_process_ir_crossfaded(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
+                                     size_t channel_stride, size_t seg_blocks, const unsigned *ir_idx, size_t idx_stride,
+                                     const unsigned *prev_idx, void *hip_stream);
 /* The same as ohs_batch_process, but `hip_stream` is NOT made to wait for the last time chunk's convolution (it runs on an
  * internal stream underneath the EQ): d_out is complete on `hip_stream` only after ohs_batch_join (a
  * stream-side wait, asynchronous) or ohs_batch_sync.  Back-to-back deferred calls with the same buffers

@@ -136,6 +136,8 @@ PROTOTYPES = {
     "ohs_batch_process_ir_scheduled": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                  C.POINTER(C.c_uint32), C.c_size_t, C.c_int, vp]),
     "ohs_batch_last_conv_ir_scheduled": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "ohs_batch_process_ir_crossfaded": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                  C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), vp]),
     "ohs_batch_join": (C.c_int, [vp, vp]),
     "ohs_batch_sync": (C.c_int, [vp, vp]),
     "ohs_batch_process_host": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),

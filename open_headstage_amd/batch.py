@@ -310,6 +310,60 @@ class BatchProcessor:
                                       ir_idx, mode, hip_stream)
         return out
 
+    def last_conv_ir_crossfaded(self) -> bool:
+        """whether the crossfading kernel served the most recent convolution launch (ohs_batch_last_conv_ir_scheduled == 2)"""
+        v = C.c_int()
+        self._check(self._lib.ohs_batch_last_conv_ir_scheduled(self._h, C.byref(v)))
+        return v.value == 2
+
+    def process_ir_crossfaded_ptr(self, d_in: int, d_out: int, n_blocks: int, stream_stride: int, channel_stride: int,
+                                  seg_blocks: int, ir_idx, prev_idx=None, hip_stream: int = 0) -> None:
+        """ohs_batch_process_ir_crossfaded: process_ir_scheduled_ptr's rows, with a crossfade from the old set to the new one over
+        the first block of every segment whose set differs from the one in front of it.  prev_idx: the set in front of the call's
+        first block -- a scalar for a 1-D ir_idx, [n_streams] for rows per stream --, or None: the call's start is no boundary."""
+        n_segs = -(-int(n_blocks) // int(seg_blocks)) if seg_blocks else 0
+        if ir_idx is None:
+            raise ValueError("ir_idx is required")
+        a = np.ascontiguousarray(ir_idx, dtype=np.uint32)
+        if a.ndim == 1:
+            if a.size < n_segs:
+                raise ValueError(f"ir_idx needs {n_segs} entries")
+            stride = 0
+        elif a.ndim == 2 and a.shape[0] == self.n_streams and a.shape[1] >= n_segs:
+            stride = int(a.shape[1])
+        else:
+            raise ValueError(f"ir_idx: expected [{self.n_streams}][>= {n_segs}] or [>= {n_segs}], got {a.shape}")
+        pp = None
+        if prev_idx is not None:
+            pv = np.ascontiguousarray(prev_idx, dtype=np.uint32).reshape(-1)
+            if pv.size != (self.n_streams if stride else 1):
+                raise ValueError(f"prev_idx: expected {self.n_streams if stride else 1} entries, got {pv.size}")
+            pp = pv.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._check(self._lib.ohs_batch_process_ir_crossfaded(
+            self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(stream_stride), int(channel_stride), int(seg_blocks),
+            a.ctypes.data_as(C.POINTER(C.c_uint32)), stride, pp, C.c_void_p(hip_stream) if hip_stream else None))
+
+    def process_ir_crossfaded(self, x, seg_blocks: int, ir_idx, prev_idx=None, out=None, hip_stream: int | None = None):
+        """process() with a schedule of HRIR sets per stream and segment of seg_blocks * 512 frames, crossfaded over the first
+        block of every segment that changes the set.  x, out as in process()."""
+        import torch
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, 2, frames]")
+        S, ch, frames = x.shape
+        if S != self.n_streams or ch != 2 or frames % BLOCK_SIZE:
+            raise ValueError(f"expected [{self.n_streams}, 2, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
+        if x.device.index != self.device:
+            raise ValueError("tensor is on a different device than the BatchProcessor")
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+            raise ValueError("out must match x")
+        if hip_stream is None:
+            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+        self.process_ir_crossfaded_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, 2 * frames, frames, seg_blocks,
+                                       ir_idx, prev_idx, hip_stream)
+        return out
+
     def join(self, hip_stream: int | None = None) -> None:
         """Make `hip_stream` (default: torch's current stream) wait for a pending deferred call."""
         if hip_stream is None:

@@ -719,13 +719,15 @@ int ohs_batch_set_schedule_irs(ohs_batch *b, size_t n_sets, const float *irs, si
 int ohs_batch_last_conv_ir_scheduled(const ohs_batch *b, int *scheduled)
 {
     if (!b || !scheduled) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
-    *scheduled = b->conv.last_ir_scheduled ? 1 : 0;
+    *scheduled = b->conv.last_ir_crossfaded ? 2 : b->conv.last_ir_scheduled ? 1 : 0;
     return OHS_OK;
 }
 
-int ohs_batch_process_ir_scheduled(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
-                                   size_t channel_stride, size_t seg_blocks, const unsigned *ir_idx, size_t idx_stride,
-                                   int switch_mode, void *hip_stream)
+// ohs_batch_process_ir_scheduled (crossfade false) and ohs_batch_process_ir_crossfaded (crossfade true; switch_mode RING_OUT, prev_idx
+// optional) share the validation pass, the staging slot and the state rules
+static int batch_process_irs(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
+                             size_t channel_stride, size_t seg_blocks, const unsigned *ir_idx, size_t idx_stride,
+                             int switch_mode, bool crossfade, const unsigned *prev_idx, void *hip_stream)
 {
     if (!b || !d_in || !d_out || !ir_idx) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
     if (seg_blocks == 0) return fail(OHS_ERR_INVALID_ARG, "seg_blocks is 0");
@@ -754,6 +756,24 @@ int ohs_batch_process_ir_scheduled(ohs_batch *b, const float *d_in, float *d_out
             rows_differ = rows_differ || row[k] != ir_idx[k];
         }
     }
+    // the crossfaded call: where a fade begins -- at a change along a row, or at the call's start against prev_idx -- and whether
+    // the call's last block is such a block in any stream (its per-path overlaps are then the sum of both halves of the fade)
+    bool boundary = false, faded_end = false, prev_differ = false;
+    if (crossfade) {
+        const bool last_is_first = n_blocks > 0 && (n_blocks - 1) % seg_blocks == 0;
+        for (size_t r = 0; r < rows; ++r) {
+            const unsigned *row = ir_idx + r * idx_stride;
+            if (prev_idx) {
+                if (prev_idx[r] >= c.irs_n) return fail(OHS_ERR_INVALID_ARG, "prev_idx entry out of range");
+                prev_differ = prev_differ || prev_idx[r] != prev_idx[0];
+                boundary = boundary || prev_idx[r] != row[0];
+                faded_end = faded_end || (last_is_first && n_segs == 1 && prev_idx[r] != row[0]);
+            }
+            faded_end = faded_end || (last_is_first && n_segs > 1 && row[n_segs - 1] != row[n_segs - 2]);
+        }
+        boundary = boundary || vary;
+        crossfade = boundary;       // (a call without any boundary takes the RING_OUT paths below: their launches, their bits)
+    }
     if (b->failed || n_blocks == 0)     // (the plain call's answers)
         return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
     {
@@ -764,7 +784,7 @@ int ohs_batch_process_ir_scheduled(ohs_batch *b, const float *d_in, float *d_out
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const bool cut = switch_mode == OHS_IR_SWITCH_CUT, shared = idx_stride == 0;
-    if (shared && !vary) {
+    if (shared && !vary && !crossfade) {
         // One set throughout, for all streams: the plain kernel on that set's table -- the plain call's launches and bits.  The overlaps
         // at rest belong to the responses that go: under RING_OUT they are computed now (and ring out), under CUT the call's start is a
         // boundary and they are zero, as after four set_ir.
@@ -780,7 +800,9 @@ int ohs_batch_process_ir_scheduled(ohs_batch *b, const float *d_in, float *d_out
         return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
     }
     // the rows' staging slot (ohs_batch_process_scheduled's): rows packed n_segs apart; equal rows travel as one
-    const size_t n_tab = (rows_differ ? S : 1) * n_segs;
+    // (the crossfaded call's prev_idx travels behind the rows)
+    const size_t n_rows = (rows_differ ? S : 1) * n_segs, n_prev = (crossfade && prev_idx) ? (prev_differ ? S : 1) : 0;
+    const size_t n_tab = n_rows + n_prev;
     ohs_batch::SchedSlot &slot = b->sched_slot[b->sched_next];
     b->sched_next = (b->sched_next + 1) % ohs_batch::kSchedSlots;
     if (slot.in_use) HIP_TRY(hipEventSynchronize(slot.done));
@@ -799,11 +821,16 @@ int ohs_batch_process_ir_scheduled(ohs_batch *b, const float *d_in, float *d_out
         slot.cap = cap;
     }
     for (size_t r = 0; r < (rows_differ ? S : 1); ++r) std::memcpy(slot.h + r * n_segs, ir_idx + r * idx_stride, n_segs * sizeof(unsigned));
+    if (n_prev) std::memcpy(slot.h + n_rows, prev_idx, n_prev * sizeof(unsigned));
     HIP_TRY(hipMemcpyAsync(slot.d, slot.h, n_tab * sizeof(unsigned), hipMemcpyHostToDevice, st));
     ConvIrs ci;
     ci.tab = slot.d; ci.seg_blocks = (int)seg_blocks; ci.stream_stride = rows_differ ? (int)n_segs : 0; ci.call_blocks = (int)n_blocks;
     ci.cut = cut;
     ci.per_stream_state = !shared;      // (a shared row is adopted below: the handle's spectra rebuild the overlaps when asked)
+    if (crossfade) {
+        ci.xfade = true; ci.faded_end = faded_end;
+        if (n_prev) { ci.prev = slot.d + n_rows; ci.prev_stride = prev_differ ? 1 : 0; }
+    }
     const int rc = batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false, nullptr, &ci);
     if (hipEventRecord(slot.done, st) == hipSuccess) slot.in_use = true;
     else hipStreamSynchronize(st);
@@ -811,6 +838,22 @@ int ohs_batch_process_ir_scheduled(ohs_batch *b, const float *d_in, float *d_out
     // one row for all streams: the handle's responses ARE the last segment's now (what ohs_batch_process_scheduled does with its table)
     if (shared) return conv_adopt_schedule_set(c, ir_idx[n_segs - 1], st);
     return OHS_OK;
+}
+
+int ohs_batch_process_ir_scheduled(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
+                                   size_t channel_stride, size_t seg_blocks, const unsigned *ir_idx, size_t idx_stride,
+                                   int switch_mode, void *hip_stream)
+{
+    return batch_process_irs(b, d_in, d_out, n_blocks, stream_stride, channel_stride, seg_blocks, ir_idx, idx_stride, switch_mode,
+                             false, nullptr, hip_stream);
+}
+
+int ohs_batch_process_ir_crossfaded(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
+                                    size_t channel_stride, size_t seg_blocks, const unsigned *ir_idx, size_t idx_stride,
+                                    const unsigned *prev_idx, void *hip_stream)
+{
+    return batch_process_irs(b, d_in, d_out, n_blocks, stream_stride, channel_stride, seg_blocks, ir_idx, idx_stride,
+                             OHS_IR_SWITCH_RING_OUT, true, prev_idx, hip_stream);
 }
 
 int ohs_batch_process_deferred(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,

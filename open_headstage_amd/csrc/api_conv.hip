@@ -941,10 +941,11 @@ static int conv_run_p1(ConvState &c, DeviceCtx *ctx, const ConvCall &k, const Co
     for (int g = 0; g < 4; ++g) a.weights[g] = weighted ? kw[g] : 1;
     hipError_t e;
     if (k.irs) {
-        ConvIrArgs i;
+        ConvIrXfArgs i;
         i.cd = c.d_irs_cd; i.H = c.d_irs_H; i.tab = k.irs->tab;
         i.seg = k.irs->seg_blocks; i.off = k.irs->blk_off; i.stream = k.irs->stream_stride; i.cut = k.irs->cut ? 1 : 0;
-        e = launch_conv_p1_irs(a, i, st, ev_start, ev_stop);
+        i.prev = k.irs->prev; i.prev_stream = k.irs->prev_stride;
+        e = k.irs->xfade ? launch_conv_p1_irs_xf(a, i, st, ev_start, ev_stop) : launch_conv_p1_irs(a, i, st, ev_start, ev_stop);
     } else {
         e = launch_conv_p1(a, st, ev_start, ev_stop);
     }
@@ -1157,16 +1158,19 @@ int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, 
     c.last_kernel = plan.kernel; c.last_ranges = ranges;
     c.kernel_calls[plan.kernel]++;
     c.last_ir_scheduled = k.irs != nullptr;
+    c.last_ir_crossfaded = k.irs != nullptr && k.irs->xfade;
     c.tails_both = false;       // (d_tails belongs to the state in front of this launch)
-    if (k.irs && k.irs->per_stream_state && k.irs->blk_off + n_blocks == k.irs->call_blocks) {
+    if (k.irs && (k.irs->per_stream_state || k.irs->faded_end) && k.irs->blk_off + n_blocks == k.irs->call_blocks) {
         // the call's last block has left the lazy state; the per-path overlaps under every stream's own last set, now, while the rows
-        // are at hand (conv_materialise_state would take the handle's spectra)
+        // are at hand (conv_materialise_state would take the handle's spectra) -- and, where that block faded, as the sum of both
+        // halves of the fade (the last input through ONE set is not what it left)
         ConvP1Args a;
         conv_state_args(c, ctx, a);
-        ConvIrArgs i;
+        ConvIrXfArgs i;
         i.cd = c.d_irs_cd; i.H = c.d_irs_H; i.tab = k.irs->tab;
         i.seg = k.irs->seg_blocks; i.off = k.irs->call_blocks - 1; i.stream = k.irs->stream_stride; i.cut = 0;
-        hipError_t e = launch_conv_p1_state_irs(a, i, st);
+        i.prev = k.irs->prev; i.prev_stream = k.irs->prev_stride;
+        hipError_t e = k.irs->xfade ? launch_conv_p1_state_irs_xf(a, i, st) : launch_conv_p1_state_irs(a, i, st);
         if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_state_irs launch: ") + hipGetErrorString(e));
         c.tails_both = true;
     }

@@ -206,6 +206,7 @@ struct ConvState {
     // where d_H could not rebuild them); the next launch clears it
     bool tails_both = false;
     bool last_ir_scheduled = false; // the last conv_launch looked the set up per block (ohs_batch_last_conv_ir_scheduled)
+    bool last_ir_crossfaded = false;    // ... with the crossfading kernel k_conv_p1_irs_xf (the query then reports 2)
     // ohs_*_set_speakers: what it last loaded into each path (a set_ir from anywhere else forgets it), so that a
     // change of the speaker angles re-loads only the paths whose impulse response really changed
     std::vector<float> spk_ir[4];
@@ -266,10 +267,16 @@ struct ConvGains {
 // cut: OHS_IR_SWITCH_CUT.  per_stream_state: behind the call's last block the per-path overlaps are computed from every stream's
 // own last set (rows per stream: d_H cannot rebuild them later).  Needs every path at one partition, the lazy state, no pending tails
 // (the batch entry point checks); always served by the block-512 family.
+// xfade: ohs_batch_process_ir_crossfaded -- k_conv_p1_irs_xf serves the launches; prev (device memory, or nullptr): the set in front
+// of the call's first block, stream s reads prev[s * prev_stride].  faded_end: the call's last block fades in at least one stream,
+// so the per-path overlaps are computed behind it whatever the rows (neither d_H nor one set per stream could rebuild them).
 struct ConvIrs {
     const unsigned *tab = nullptr;
     int seg_blocks = 1, blk_off = 0, stream_stride = 0, call_blocks = 0;
     bool cut = false, per_stream_state = false;
+    bool xfade = false, faded_end = false;
+    const unsigned *prev = nullptr;
+    int prev_stride = 0;
 };
 int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
                 float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st,

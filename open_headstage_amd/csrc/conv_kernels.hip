@@ -1256,6 +1256,7 @@ __device__ __forceinline__ long long p1_xcd_block(const ConvP1Args &A)
 #define OHS_P1_LOOP_INIT
 #define OHS_P1_BLOCK_BEGIN(t)
 #define OHS_P1_BLOCK_END
+#define OHS_P1_PRE_PRODUCT(v, w)
 #define OHS_P1_PRODUCT(v, w) p1_spectral_product_paired(v, w, cd, lane);
 #define OHS_P1_GAIN A.gain
 #define OHS_P1_BLOCK_GAIN(t)
@@ -1274,6 +1275,7 @@ __global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1_gains(const ConvP1Arg
 #undef OHS_P1_LOOP_INIT
 #undef OHS_P1_BLOCK_BEGIN
 #undef OHS_P1_BLOCK_END
+#undef OHS_P1_PRE_PRODUCT
 #undef OHS_P1_PRODUCT
 
 // k_conv_p1_irs (ohs_batch_process_ir_scheduled; kernels.h: ConvIrArgs): every wave follows its own stream's row of set indices.
@@ -1297,6 +1299,7 @@ __global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1_gains(const ConvP1Arg
     const float4 *cdp = I.cd + (size_t)ir_idx * kFft + lane;
 #define OHS_P1_BLOCK_END \
     if (++ir_r == I.seg) { ir_r = 0; ++ir_k; }
+#define OHS_P1_PRE_PRODUCT(v, w)
 #define OHS_P1_PRODUCT(v, w) p1_spectral_product_paired_global(v, w, cdp, lane);
 #define OHS_P1_GAIN A.gain
 #define OHS_P1_BLOCK_GAIN(t)
@@ -1308,6 +1311,77 @@ __global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1_irs(const ConvP1Args 
 #undef OHS_P1_LOOP_INIT
 #undef OHS_P1_BLOCK_BEGIN
 #undef OHS_P1_BLOCK_END
+#undef OHS_P1_PRE_PRODUCT
+#undef OHS_P1_PRODUCT
+
+// k_conv_p1_irs_xf (ohs_batch_process_ir_crossfaded; kernels.h: ConvIrXfArgs): k_conv_p1_irs without the CUT rule and with a
+// crossfade over the first block of every segment whose set differs from the one in front of it (ir_prev: the previous segment's
+// index, the caller's prev_idx in front of the call's first block, ~0 = none: no boundary).  The test is wave-uniform -- both
+// indices are scalar --, so every other block runs the block of k_conv_p1_irs.  A fading block splits its input by the ramps
+// f[n] = n / 512 and g[n] = (512 - n) / 512 (exact in f32; frame n = 64 a + lane) and runs as TWO blocks on the same frames:
+// x g through the OLD set first -- forward, product, inverse; its head is folded into the incoming overlap, its tail waits in
+// xf_tail --, then x f through the new set as the block every block is; OHS_P1_BLOCK_END adds xf_tail to the tail that block
+// left.  The frames leave as (w_new + (overlap + w_old)) * gain; the overlap the block leaves is the sum of both tails.
+// Registers decide the form: one inverse transform for both halves (the second product accumulating onto the first in w) keeps
+// w (32) alive across the second forward transform and the input (16) across the first -- hipcc spilled 56 VGPRs at the 128 a
+// 16-wave workgroup allows; in this form the first pass carries the input and the second xf_tail, 16 registers either way:
+// 127 VGPRs, no scratch.  The price is one inverse transform per fading block.  The input registers xl / xr stay alive up to
+// the second forward transform: the prefetch of block t + 1 is issued behind the last inverse transform, as in every block.
+// The dry block in front of a chunk takes the same path.
+#define OHS_P1_TABLE(cd) (void)cd;
+#define OHS_P1_LOOP_INIT \
+    const unsigned *ir_row = I.tab + (size_t)s * (size_t)I.stream; \
+    int ir_k = __builtin_amdgcn_readfirstlane((I.off + t_first) / I.seg); \
+    int ir_r = __builtin_amdgcn_readfirstlane((I.off + t_first) - ir_k * I.seg); \
+    unsigned ir_prev = ir_k > 0 ? (unsigned)__builtin_amdgcn_readfirstlane((int)ir_row[ir_k - 1]) \
+                     : I.prev   ? (unsigned)__builtin_amdgcn_readfirstlane((int)I.prev[(size_t)s * (size_t)I.prev_stream]) \
+                                : 0xffffffffu;
+#define OHS_P1_BLOCK_BEGIN(t) \
+    const unsigned ir_idx = (unsigned)__builtin_amdgcn_readfirstlane((int)ir_row[ir_k]); \
+    const bool ir_fade = ir_r == 0 && ir_prev != 0xffffffffu && ir_prev != ir_idx; \
+    float2 xf_tail[8]; \
+    const float4 *cdp = I.cd + (size_t)ir_idx * kFft + lane;
+#define OHS_P1_BLOCK_END \
+    if (ir_fade) { \
+        _Pragma("unroll") for (int a = 0; a < 8; ++a) tail[a] = make_float2(tail[a].x + xf_tail[a].x, tail[a].y + xf_tail[a].y); \
+    } \
+    ir_prev = ir_idx; \
+    if (++ir_r == I.seg) { ir_r = 0; ++ir_k; }
+#define OHS_P1_PRE_PRODUCT(v, w) \
+    if (ir_fade) { \
+        const float4 *cdo = I.cd + (size_t)ir_prev * kFft + lane; \
+        float xf_n = (float)lane; \
+        asm volatile("" : "+v"(xf_n));      /* (the sixteen ramp values are not worth sixteen registers across the loop) */ \
+        _Pragma("unroll") for (int a = 0; a < 8; ++a) { \
+            const float g = ((float)(kBlock - 64 * a) - xf_n) * (1.0f / (float)kBlock); \
+            v[a] = make_float2(xl[a] * g, xr[a] * g); \
+        } \
+        wave_fft_fwd_paired(v, lds, tab, lane, plan); \
+        p1_spectral_product_paired_global(v, w, cdo, lane); \
+        wave_fft_inv_paired(w, lds, tab, lane, plan); \
+        _Pragma("unroll") for (int a = 0; a < 8; ++a) { \
+            tail[a] = make_float2(tail[a].x + w[a].x, tail[a].y + w[a].y); \
+            xf_tail[a] = w[a + 8]; \
+        } \
+        asm volatile("" : "+v"(xf_n)); \
+        _Pragma("unroll") for (int a = 0; a < 8; ++a) { \
+            const float f = ((float)(64 * a) + xf_n) * (1.0f / (float)kBlock); \
+            v[a] = make_float2(xl[a] * f, xr[a] * f); \
+            v[a + 8] = make_float2(0.0f, 0.0f); \
+        } \
+    }
+#define OHS_P1_PRODUCT(v, w) p1_spectral_product_paired_global(v, w, cdp, lane);
+#define OHS_P1_GAIN A.gain
+#define OHS_P1_BLOCK_GAIN(t)
+__global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1_irs_xf(const ConvP1Args A, const ConvIrXfArgs I)
+#include "conv_p1_body.inc"
+#undef OHS_P1_GAIN
+#undef OHS_P1_BLOCK_GAIN
+#undef OHS_P1_TABLE
+#undef OHS_P1_LOOP_INIT
+#undef OHS_P1_BLOCK_BEGIN
+#undef OHS_P1_BLOCK_END
+#undef OHS_P1_PRE_PRODUCT
 #undef OHS_P1_PRODUCT
 
 // pre-pass, two small kernels that read INPUT frames only -- which is why they run before the main kernel stores over
@@ -1386,6 +1460,76 @@ __global__ __launch_bounds__(64 * kP1StateWaves) void k_conv_p1_state_irs(const 
     const unsigned idx = (unsigned)__builtin_amdgcn_readfirstlane((int)I.tab[(size_t)s * (size_t)I.stream + (size_t)(I.off / I.seg)]);
     const float2 *h = I.H + ((size_t)idx * 4 + 2 * spk) * kFft;
     p1_state_wave(A, s, spk, h, h + kFft, lds, tab, lane);
+}
+
+// The same behind a crossfaded call (ohs_batch_process_ir_crossfaded).  Call block I.off is the stream's last; where it is the first
+// block of its segment and the set in front of it (the previous segment's, or I.prev in front of the call) differs, its per-path
+// overlaps are state(x g, old set) + state(x f, its own set) -- two forward transforms, the two per-speaker products summed, one
+// inverse.  Every other stream takes p1_state_wave, as in k_conv_p1_state_irs.
+__device__ __forceinline__ void p1_state_wave_xf(const ConvP1Args &A, int s, int spk, const float2 *ha_old, const float2 *ha,
+                                                 float2 *lds, const float2 *tab, int lane)
+{
+    const float *in_l = A.in + (size_t)s * A.in_stream_stride;
+    const float *in_r = in_l + A.in_ch_stride;
+    const unsigned base = (unsigned)(A.n_blocks - 1) * kBlock + lane;
+    float xl[8], xr[8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a) { xl[a] = in_l[base + 64 * a]; xr[a] = in_r[base + 64 * a]; }
+    float2 v[16], w[16], acc[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = make_float2(0.0f, 0.0f);
+#pragma unroll 1                // (one copy of the transform; unrolled, hipcc took 266 registers for the two)
+    for (int half = 0; half < 2; ++half) {
+        const float2 *pa = half == 0 ? ha_old : ha, *pb = pa + kFft;
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+            const int n = half == 0 ? kBlock - 64 * a - lane : 64 * a + lane;
+            const float r = (float)n * (1.0f / (float)kBlock);
+            v[a] = make_float2(xl[a] * r, xr[a] * r);
+            v[a + 8] = make_float2(0.0f, 0.0f);
+        }
+        wave_fft_fwd_mirror(v, w, lds, tab, lane);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float2 zm = w[r];
+            const float2 x = spk == 0 ? make_float2(0.5f * (v[r].x + zm.x), 0.5f * (v[r].y - zm.y))
+                                      : make_float2(0.5f * (v[r].y + zm.y), -0.5f * (v[r].x - zm.x));
+            float2 y = acc[r];
+            cmac(y, x, pa[r * 64 + lane]);
+            cmac_j(y, x, pb[r * 64 + lane]);
+            acc[r] = y;
+        }
+    }
+    wave_fft_inv(acc, lds, tab, lane);
+    const float scale = 1.0f / (float)kFft;
+    float2 *tails_out = A.tails_out + (size_t)s * (2 * 8 * 64) + (size_t)spk * (8 * 64);
+#pragma unroll
+    for (int a = 0; a < 8; ++a) tails_out[a * 64 + lane] = make_float2(acc[a + 8].x * scale, acc[a + 8].y * scale);
+}
+
+__global__ __launch_bounds__(64 * kP1StateWaves) void k_conv_p1_state_irs_xf(const ConvP1Args A, const ConvIrXfArgs I)
+{
+    ohs_set_fp_mode(A.fp_mode);
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    float2 *tab = smem;
+    fill_twiddle_tables(tab, A.tw, threadIdx.x, 64 * kP1StateWaves);
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    float2 *lds = smem + kTabComplex + wave * kWaveLdsComplex;
+    const long long gw = (long long)blockIdx.x * kP1StateWaves + wave;
+    if (gw >= 2ll * A.n_streams) return;
+    const int s = (int)(gw >> 1), spk = (int)(gw & 1);
+    const unsigned *row = I.tab + (size_t)s * (size_t)I.stream;
+    const int k = I.off / I.seg;
+    const unsigned idx = (unsigned)__builtin_amdgcn_readfirstlane((int)row[k]);
+    unsigned old = idx;
+    if (I.off - k * I.seg == 0) {
+        if (k > 0) old = (unsigned)__builtin_amdgcn_readfirstlane((int)row[k - 1]);
+        else if (I.prev) old = (unsigned)__builtin_amdgcn_readfirstlane((int)I.prev[(size_t)s * (size_t)I.prev_stream]);
+    }
+    const float2 *h = I.H + ((size_t)idx * 4 + 2 * spk) * kFft;
+    if (old == idx) p1_state_wave(A, s, spk, h, h + kFft, lds, tab, lane);
+    else p1_state_wave_xf(A, s, spk, I.H + ((size_t)old * 4 + 2 * spk) * kFft, h, lds, tab, lane);
 }
 
 __global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1_edges(const ConvP1Args A)
@@ -1536,6 +1680,38 @@ hipError_t launch_conv_p1_irs(const ConvP1Args &a, const ConvIrArgs &i, hipStrea
     const dim3 grid(xcd_grid((unsigned)((waves + kP1Waves - 1) / kP1Waves), a.xcd_n));
     if (ev_start || ev_stop) hipExtLaunchKernelGGL(k_conv_p1_irs, grid, dim3(64 * kP1Waves), shmem_main, st, ev_start, ev_stop, 0, a, i);
     else hipLaunchKernelGGL(k_conv_p1_irs, grid, dim3(64 * kP1Waves), shmem_main, st, a, i);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv_p1_state_irs_xf(const ConvP1Args &a, const ConvIrXfArgs &i, hipStream_t st)
+{
+    if (a.n_blocks <= 0 || a.n_streams <= 0 || !a.tails_out || !i.H || !i.tab || i.seg < 1 || i.off < 0 || i.stream < 0 || i.prev_stream < 0)
+        return hipErrorInvalidValue;
+    const size_t shmem_state = (kTabComplex + kP1StateWaves * kWaveLdsComplex) * sizeof(float2);
+    const long long waves = 2ll * a.n_streams;
+    hipLaunchKernelGGL(k_conv_p1_state_irs_xf, dim3((unsigned)((waves + kP1StateWaves - 1) / kP1StateWaves)),
+                       dim3(64 * kP1StateWaves), shmem_state, st, a, i);
+    return hipGetLastError();
+}
+
+// the crossfading kernel: launch_conv_p1_irs's shapes and conditions
+hipError_t launch_conv_p1_irs_xf(const ConvP1Args &a, const ConvIrXfArgs &i, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop)
+{
+    if (a.n_blocks <= 0 || a.n_streams <= 0 || a.chunks < 1 || a.chunks > a.n_blocks) return hipErrorInvalidValue;
+    if ((unsigned long long)a.n_blocks * kBlock >= (1ull << 32)) return hipErrorInvalidValue;   // 32-bit frame offsets
+    if (a.xcd_n < 1 || a.xcd_n > 8 || a.xcd_lo < 0 || a.xcd_lo + a.xcd_n > 8) return hipErrorInvalidValue;
+    if (!a.merged_out || !a.last_in) return hipErrorInvalidValue;
+    if (!i.cd || !i.tab || i.seg < 1 || i.off < 0 || i.stream < 0 || i.prev_stream < 0) return hipErrorInvalidValue;
+    if (a.chunks == 1 ? a.own_tails != 0 : !(a.own_tails && kP1Waves == 16 && (a.chunks == 2 || a.chunks == 4 || a.chunks == 8 || a.chunks == 16)))
+        return hipErrorInvalidValue;
+    const size_t shmem_main = (kTabComplex + 2 * kFft + kP1Waves * kWaveLdsComplex) * sizeof(float2);
+    static std::atomic<unsigned long long> lds_ok{0};
+    hipError_t e = allow_large_lds(reinterpret_cast<const void *>(k_conv_p1_irs_xf), shmem_main, lds_ok);
+    if (e != hipSuccess) return e;
+    const long long waves = (long long)a.n_streams * a.chunks;
+    const dim3 grid(xcd_grid((unsigned)((waves + kP1Waves - 1) / kP1Waves), a.xcd_n));
+    if (ev_start || ev_stop) hipExtLaunchKernelGGL(k_conv_p1_irs_xf, grid, dim3(64 * kP1Waves), shmem_main, st, ev_start, ev_stop, 0, a, i);
+    else hipLaunchKernelGGL(k_conv_p1_irs_xf, grid, dim3(64 * kP1Waves), shmem_main, st, a, i);
     return hipGetLastError();
 }
 

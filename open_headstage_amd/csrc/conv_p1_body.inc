@@ -6,8 +6,13 @@
 //                    OHS_P1_BLOCK_BEGIN(t) reads the set index of block t's segment -- wave-uniform, one scalar load per block --,
 //                    zeroes the incoming overlap at a run's first block in the CUT mode, and OHS_P1_PRODUCT takes (C, D) of that
 //                    set from the device table I.cd
+//   k_conv_p1_irs_xf the same with a crossfade (ohs_batch_process_ir_crossfaded): in the first block of a segment whose set differs
+//                    from the one in front of it, OHS_P1_PRE_PRODUCT runs x * (512 - n) / 512 through the OLD set as a block of
+//                    its own (head into tail[], tail kept for OHS_P1_BLOCK_END) and leaves x * n / 512 in v for the block
+//                    that follows.  Every other block is k_conv_p1_irs's
 // The hooks the includer defines: OHS_P1_TABLE(cd) fills the LDS table, OHS_P1_LOOP_INIT runs once in front of the block loop,
-// OHS_P1_BLOCK_BEGIN(t) / OHS_P1_BLOCK_END at the loop's top and bottom, OHS_P1_PRODUCT(v, w) is the spectral product.
+// OHS_P1_BLOCK_BEGIN(t) / OHS_P1_BLOCK_END at the loop's top and bottom, OHS_P1_PRE_PRODUCT(v, w) sits between the block's input
+// (v filled, xl / xr still alive) and its forward transform, OHS_P1_PRODUCT(v, w) is the spectral product.
 // Textual inclusion, so that the plain kernel's code does not depend on the other one's existence.
 {
     const long long wg = p1_xcd_block(A);
@@ -121,6 +126,7 @@
             v[a + 8] = make_float2(0.0f, 0.0f);
         }
         float2 w[16];
+        OHS_P1_PRE_PRODUCT(v, w)
         wave_fft_fwd_paired(v, lds, tab, lane, plan);
         OHS_P1_PRODUCT(v, w)
         // the prefetch of block t + 1 needs no guard except behind the launch's last block, where it re-reads that

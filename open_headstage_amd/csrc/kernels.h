@@ -255,6 +255,17 @@ hipError_t launch_conv_p1_irs(const ConvP1Args &a, const ConvIrArgs &i, hipStrea
                               hipEvent_t ev_stop = nullptr);
 // the per-path overlaps block a.n_blocks - 1 of a.in leaves behind under the set of call block i.off of every stream's row -> a.tails_out
 hipError_t launch_conv_p1_state_irs(const ConvP1Args &a, const ConvIrArgs &i, hipStream_t st);
+// The crossfading sibling (ohs_batch_process_ir_crossfaded): k_conv_p1_irs_xf fades from the previous segment's set to the block's
+// own over the first block of a segment where the two differ.  A struct of its own, so that ConvIrArgs and with it k_conv_p1_irs
+// stay what they are.  cut is ignored (0).
+struct ConvIrXfArgs : ConvIrArgs {
+    const unsigned *prev;       // the set in front of the call's first block per stream (device memory), or nullptr: no boundary there
+    int prev_stream;            // stream s reads prev[s * prev_stream] (0: one entry for all streams)
+};
+hipError_t launch_conv_p1_irs_xf(const ConvP1Args &a, const ConvIrXfArgs &i, hipStream_t st, hipEvent_t ev_start = nullptr,
+                                 hipEvent_t ev_stop = nullptr);
+// launch_conv_p1_state_irs for a call block i.off that may have faded: the per-path overlaps state(x g, old set) + state(x f, its set)
+hipError_t launch_conv_p1_state_irs_xf(const ConvP1Args &a, const ConvIrXfArgs &i, hipStream_t st);
 // cd[set][2][1024] (launch_build_cd per set) -> dst[set][1024] in the block loop's layout
 hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st);
 // CD[0][..] = (A - jB)/2, CD[1][..] = (A + jB)/2 from four single-partition spectra

@@ -6,6 +6,8 @@ round by round in one session:
   plain    one ohs_batch_process of the same frames (the handle's one set): what the schedule costs on top of
   shared   one ohs_batch_process_ir_scheduled, one row of set indices for all streams
   streams  the same with a row per stream (every stream its own pseudo-random walk through the table)
+  xf_shared, xf_streams   ohs_batch_process_ir_crossfaded on the same rows: the first block of every segment fades from the
+           previous segment's set (prev_idx: the row's last entry, so the call's first block fades too)
   loop     the per-segment call loop the new call replaces: four ohs_batch_set_ir and one 2-block ohs_batch_process per
            segment -- one set for all streams, the tail cut at every change (--loop-steps of them per round; 0 leaves it out)
 
@@ -78,6 +80,7 @@ def main():
         bp.update_band_coeffs(i, synth.FS, b)
     bp.set_eq_enabled(bool(a.eq))
     new_api = hasattr(bp, "process_ir_scheduled")
+    xf_api = hasattr(bp, "process_ir_crossfaded")
     if new_api:
         bp.set_schedule_irs(sets)
     x = synth.white_noise_torch(0, S, nb * 512, dev)
@@ -94,6 +97,12 @@ def main():
     def streams():
         bp.process_ir_scheduled(x, sb, idx_s, a.mode, out=y, hip_stream=hs)
 
+    def xf_shared():
+        bp.process_ir_crossfaded(x, sb, idx, int(idx[-1]), out=y, hip_stream=hs)
+
+    def xf_streams():
+        bp.process_ir_crossfaded(x, sb, idx_s, idx_s[:, -1], out=y, hip_stream=hs)
+
     def loop():
         f = sb * 512
         for k in range(n_segs):
@@ -105,6 +114,8 @@ def main():
     variants = [("plain", plain, a.steps)]
     if new_api:
         variants += [("shared", shared, a.steps), ("streams", streams, a.steps)]
+    if xf_api:
+        variants += [("xf_shared", xf_shared, a.steps), ("xf_streams", xf_streams, a.steps)]
     if a.loop_steps > 0:
         variants.append(("loop", loop, a.loop_steps))
     if a.only:
@@ -120,7 +131,8 @@ def main():
             if name == "loop":
                 continue
             fn(); stream.synchronize()
-            forms[name] = list(bp.last_conv_plan()) + ([bp.last_conv_ir_scheduled()] if new_api else [])
+            forms[name] = list(bp.last_conv_plan()) + ([bp.last_conv_ir_scheduled()] if new_api else []) + \
+                ([bp.last_conv_ir_crossfaded()] if xf_api else [])
         if any(v[0] == "loop" for v in variants):       # (the loop leaves another set loaded: plain runs on set 0 again)
             for p in range(4):
                 bp.set_ir(p, sets[0][p])
@@ -153,11 +165,14 @@ def main():
         summ[name] = {"median_ms": round(med, 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4),
                       "msamples_per_s": round(frames / med / 1e3, 1)}
     if "plain" in ms:
-        for name in ("shared", "streams"):
+        for name in ("shared", "streams", "xf_shared", "xf_streams"):
             if name in ms:
                 summ[name + "_over_plain"] = round(summ[name]["median_ms"] / summ["plain"]["median_ms"], 4)
+    for name, base in (("xf_shared", "shared"), ("xf_streams", "streams"), ("xf_shared", "streams")):
+        if name in ms and base in ms:
+            summ[name + "_over_" + base] = round(summ[name]["median_ms"] / summ[base]["median_ms"], 4)
     if "loop" in ms:
-        for name in ("shared", "streams"):
+        for name in ("shared", "streams", "xf_shared", "xf_streams"):
             if name in ms:
                 summ["loop_over_" + name] = round(summ["loop"]["median_ms"] / summ[name]["median_ms"], 2)
         summ["loop_us_per_segment"] = round(summ["loop"]["median_ms"] * 1e3 / n_segs, 2)
