@@ -18,16 +18,23 @@
 // alpha wrote.  The slot carries the port (a group = 16 steps: two stores, two injects, one load, one wait), so the steady
 // state is 81 issue slots per 16 samples -- 5.06 per sample against 6.02 + 4.75 / 48.  The loop is generated from the model's
 // own instruction list (tools/gen_eq_quad_ring_asm.py -> eq_quad_ring_asm.inc), which also checks every DPP read's distance.
+// A slot with nothing to carry holds a v_nop.  FILL_SLOTS (experiments build, Tuning::eq_quad_fill) is the loop with a fill
+// instruction there, v_and_b32_dpp on v19 (a register nothing else touches), which keeps the vector unit for the four
+// cycles a step instruction takes instead of leaving them to a convolution wave of the same SIMD: a tie -- the loop runs at
+// the lone prototype's 21.9 ticks per sample with or without the convolution underneath.
 //
 // A launch: groups -1 .. 4 at least in the C++ form of the same step (the ring starts at zero one group early; band k's
 // state goes into G of its lanes c, d behind step 4k + 2), then whole iterations of K groups in asm while every step
 // filters existing samples, then the C++ form again (band k's state leaves behind step n + 4k + 2, the ring runs on zeros
 // until the last output is stored).  The C++ form checks every load and store against n; the asm goes through buffer
-// resources over the chain's n samples (eq_ring64_body.hpp: out-of-range lanes neither store nor load).
+// resources over the chain's n samples (eq_ring64_body.hpp: out-of-range lanes neither store nor load).  A launch has 11 to
+// 18 groups in the C++ form and a batch step six launches, so that form is written to compile to the loop's own four
+// VOP2+DPP instructions per step (quad_dpp, group_cpp below).
 #pragma once
 #include "kernels.h"
 #include "eq_ring64_body.hpp"   // kWaveRor1, ring64_rsrc, ring2_ld / ring2_st, dpp_mov
 #include "eq_quad_ring_asm.inc"
+#include <type_traits>
 
 namespace ohs {
 
@@ -37,6 +44,17 @@ constexpr int kQp0003 = 0xC0, kQp0033 = 0xF0, kQp0012 = 0x90, kQp0101 = 0x44;
 
 struct QuadRegs { float Z0, Z1, Zp, G, P; };
 
+// A DPP read for the C++ form of the step.  Every control of the step (wave_ror:1, the quad_perms) gives every lane a source
+// lane, so bound_ctrl changes no value; with it the compiler folds the move into the VOP2 instruction that consumes it --
+// v_add_f32_dpp and so on, the loop's own four instructions -- where dpp_mov (eq_ring_body.hpp) leaves a v_mov_b32_dpp in
+// front of each.
+template <int CTRL>
+__device__ __forceinline__ float quad_dpp(float src)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(src), CTRL, 0xf, 0xf, true));
+}
+
+template <bool FILL_SLOTS = false>
 __device__ __forceinline__ void eq_quad_ring_wave(const float *in, float *out, long long stream_stride, long long ch_stride,
                                                   long long n, int n_chains, int nb, const EqPassTable &tab,
                                                   float *__restrict__ state, long long chain)
@@ -86,31 +104,51 @@ __device__ __forceinline__ void eq_quad_ring_wave(const float *in, float *out, l
 
     // one group in the C++ form; (xcur, xnext) = the inputs of groups (g, g + 1) on entry, of (g + 1, g + 2) on exit: a
     // request has a whole group's steps to arrive
-    auto group_cpp = [&](int g) {
+    // The port's steps are known when the code is written (8 and 15 store, 9 and 16 inject), so the step takes its kind as a
+    // constant and a group is written out around them: the plain steps in between carry no test of s and no branch, and a
+    // group that no band's state enters or leaves (STATE false) no test of the step number either.  (With s tested at run
+    // time in every step a group cost ~4 300 ticks against the loop's 350: 11 to 18 such groups per launch were ~27 us of
+    // each of a step's six launches -- DESIGN.md 4.5, round 12.)
+    enum { kPlain, kStore, kInjectB, kInjectA };
+    auto group_cpp = [&](int g, auto with_state) {
+        constexpr bool STATE = decltype(with_state)::value;
         const float xnext2 = load_x(g + 2);
-        auto step = [&](float &zc, const float zo, int s) {
+        auto step = [&](auto kind, float &zc, const float zo, int s) {
             const int stp = g * G + s;
-            zc = dpp_mov<kWaveRor1>(r.Zp, r.Zp) + r.G;                          // alpha
-            r.Zp = dpp_mov<kQp0003>(zo, zo) * C2;                               // delta
-            if (s == 8 || s == 15) {                                            // the slot: the port
+            zc = quad_dpp<kWaveRor1>(r.Zp) + r.G;                               // alpha
+            r.Zp = quad_dpp<kQp0003>(zo) * C2;                                  // delta
+            if constexpr (kind() == kStore) {                                   // the slot: the port
                 const int yi = stp + ss;
                 if (st_lane && (unsigned)yi < (unsigned)n32) ring2_st(dst0, (unsigned)yi * 4u, zc);
-            } else if (s == 9) {
-                const float xb = dpp_mov<kQp0101>(xcur, xcur);
+            } else if constexpr (kind() == kInjectB) {
+                const float xb = quad_dpp<kQp0101>(xcur);
                 r.Zp = inj_lane ? xb : r.Zp;
-            } else if (s == 16) {
+            } else if constexpr (kind() == kInjectA) {
                 r.Zp = inj_lane ? xnext : r.Zp;
             }
-            r.P = dpp_mov<kQp0033>(zc, zc) * C1;                                // beta
-            r.G = dpp_mov<kQp0012>(zc, zc) - r.P;                               // gamma
-            if (st_band && stp == t_in) r.G = s_init;
-            if (st_band && stp == n32 + t_in) s_save = r.G;
+            r.P = quad_dpp<kQp0033>(zc) * C1;                                   // beta
+            r.G = quad_dpp<kQp0012>(zc) - r.P;                                  // gamma
+            if constexpr (STATE) {
+                r.G = (st_band && stp == t_in) ? s_init : r.G;
+                s_save = (st_band && stp == n32 + t_in) ? r.G : s_save;
+            }
         };
+        using Plain = std::integral_constant<int, kPlain>;
+        auto plain_pairs = [&](int s0, int s1) {       // steps s0 .. s1, s0 odd, s1 even
 #pragma unroll 1
-        for (int s = 1; s <= G; s += 2) {
-            step(r.Z1, r.Z0, s);
-            step(r.Z0, r.Z1, s + 1);
-        }
+            for (int s = s0; s < s1; s += 2) {
+                step(Plain{}, r.Z1, r.Z0, s);
+                step(Plain{}, r.Z0, r.Z1, s + 1);
+            }
+        };
+        plain_pairs(1, 6);
+        step(Plain{}, r.Z1, r.Z0, 7);
+        step(std::integral_constant<int, kStore>{}, r.Z0, r.Z1, 8);
+        step(std::integral_constant<int, kInjectB>{}, r.Z1, r.Z0, 9);
+        step(Plain{}, r.Z0, r.Z1, 10);
+        plain_pairs(11, 14);
+        step(std::integral_constant<int, kStore>{}, r.Z1, r.Z0, 15);
+        step(std::integral_constant<int, kInjectA>{}, r.Z0, r.Z1, 16);
         xcur = xnext;
         xnext = xnext2;
     };
@@ -118,8 +156,12 @@ __device__ __forceinline__ void eq_quad_ring_wave(const float *in, float *out, l
     const int g_total = (n32 + 62 + G - 1) / G;         // groups -1 .. g_total - 1 (the model's n_groups)
     int g = -1;
     const int head_end = iters ? g0 : g_total;
+    // a band's state goes in behind step 4k + 2 <= 46 (groups 0 .. 2) and comes out behind step n + 4k + 2, which lies behind
+    // the asm run where there is one (16 g1 <= n + 1): with a run, the head's groups 3 .. g0 - 1 touch no state
 #pragma unroll 1
-    for (; g < head_end; ++g) group_cpp(g);
+    for (; g < head_end && (g < 3 || !iters); ++g) group_cpp(g, std::true_type{});
+#pragma unroll 1
+    for (; g < head_end; ++g) group_cpp(g, std::false_type{});
     if (iters) {
         const unsigned bytes = (unsigned)n32 * 4u;
         const ring64_rsrc_t rin = ring64_rsrc(src0, bytes), rout = ring64_rsrc(dst0, bytes);
@@ -128,6 +170,20 @@ __device__ __forceinline__ void eq_quad_ring_wave(const float *in, float *out, l
         unsigned voff_ld = conv ? (unsigned)(G * g0 + xs) * 4u : 0xFFFFF000u;
         const unsigned inc_ld = conv ? 4u * G * K : 0u, inc_st = st_lane ? 4u * G * K : 0u;
         unsigned cnt = 0u - (unsigned)__builtin_amdgcn_readfirstlane(iters);
+#ifdef OHS_EXPERIMENTS
+        if constexpr (FILL_SLOTS) {
+            unsigned fill = 0u;     // the fill's own register: F & F, whatever it holds
+            asm volatile(
+                "s_nop 4\n"
+                EQ_QUAD_RING_LOOP_FILL
+                : [Z0] "+{v2}"(r.Z0), [Z1] "+{v3}"(r.Z1), [Zp] "+{v4}"(r.Zp), [Gr] "+{v5}"(r.G), [P] "+{v6}"(r.P),
+                  [vs] "+{v0}"(voff_st), [vl] "+{v1}"(voff_ld), [x0] "+{v11}"(xcur), [x1] "+{v12}"(xnext), [x2] "+{v13}"(x2),
+                  [x3] "+{v14}"(x3), [x4] "+{v15}"(x4), [x5] "+{v16}"(x5), [x6] "+{v17}"(x6), [x7] "+{v18}"(x7),
+                  [F] "+{v19}"(fill), [cnt] "+s"(cnt)
+                : [C1] "{v7}"(C1), [C2] "{v8}"(C2), [incl] "{v9}"(inc_ld), [incs] "{v10}"(inc_st), [rin] "s"(rin), [rout] "s"(rout)
+                : "memory", "scc", "vcc");
+        } else
+#endif
         asm volatile(
             "s_nop 4\n"
             EQ_QUAD_RING_LOOP
@@ -139,7 +195,7 @@ __device__ __forceinline__ void eq_quad_ring_wave(const float *in, float *out, l
         // (x0, x1 now hold the inputs of groups g1, g1 + 1: the run's last inject A took x0, group g1's inject B is next)
         g = g1;
 #pragma unroll 1
-        for (; g < g_total; ++g) group_cpp(g);
+        for (; g < g_total; ++g) group_cpp(g, std::true_type{});
     }
     if (st_band) ring2_st(state0, state_off, s_save);
 }

@@ -31,6 +31,8 @@ struct Tuning {
     int eq_form = 0;                        // k_eq_ring's form: 0 = the library's choice, 1 = four chains per wave (16-lane rows), 2 = one chain
                                             // per wave, one band per pair of lanes (eq_ring64_body.hpp), 3 = one chain per wave,
                                             // one band per quad of lanes (eq_quad_ring_body.hpp: what the library chooses)
+    int eq_quad_fill = 0;                   // 1: the quad body's loop with a VOP2+DPP fill instruction in the slots that carry
+                                            // nothing instead of v_nop (experiments build only; a tie: DESIGN.md 4.5, round 12)
     int eq_wg_waves = 0;                    // 0: 1 wave per workgroup below one wave per CU, else 4
     int eq_lds = 0;                         // LDS reservation per EQ workgroup, bytes
     // ohs_batch_process

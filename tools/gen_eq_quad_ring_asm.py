@@ -5,7 +5,11 @@ tools/model_eq_quad_ring.py (group_program): what the model interprets is what t
 
 One iteration = K groups of 16 steps.  A step is alpha, delta, <slot>, beta, gamma -- four VOP2+DPP instructions and the issue
 slot that the DPP read-after-write hazard leaves free between delta and beta; the port's instructions and the loop's own
-sit in those slots, v_nop (VOP3: 8 bytes) where a slot has nothing to carry.  Every encoding is 8 bytes and 8-byte aligned
+sit in those slots, v_nop (VOP3: 8 bytes) where a slot has nothing to carry.  The second text, EQ_QUAD_RING_LOOP_FILL
+(experiments build only: Tuning::eq_quad_fill), has the model's fill there instead: v_and_b32_dpp on v19, a VOP2+DPP
+instruction that holds the vector unit for four cycles as a step instruction does, so that a wave beside this one cannot
+start an instruction there -- measured: a tie, the convolution's waves cost the loop nothing.
+Every encoding is 8 bytes and 8-byte aligned
 except the group's s_waitcnt, which shares its slot with a 4-byte partner (s_nop, in the last group the counter's s_add):
 81 issue slots per 16 samples.
 
@@ -16,6 +20,7 @@ Pinned registers:
     v2 Z0   v3 Z1   v4 Zp   v5 G   v6 P   v7 C1   v8 C2
     v9 / v10   the iteration's advance of v1 / v0: 64 K bytes in the lanes that take part, 0 elsewhere
     v11 ..     x0 .. x(K-1): the inputs of the next K groups, reloaded in place K groups ahead
+    v19        the fill's own register (EQ_QUAD_RING_LOOP_FILL only): no other instruction reads or writes it
     VCC  every lane but c, d of the conveyor quads (the inject is a v_cndmask with the quad_perm on x)
 """
 import os
@@ -26,11 +31,11 @@ sys.path.insert(0, HERE)
 import model_eq_quad_ring as model      # noqa: E402
 
 FULL = "row_mask:0xf bank_mask:0xf"
-REG = {"Z0": "v2", "Z1": "v3", "Zp": "v4", "G": "v5", "P": "v6", "C1": "v7", "C2": "v8"}
+REG = {"Z0": "v2", "Z1": "v3", "Zp": "v4", "G": "v5", "P": "v6", "C1": "v7", "C2": "v8", "F": "v19"}
 INJECT_PERM = {"A": "[0,1,2,3]", "B": "[0,1,0,1]"}
 
 
-def loop_asm(K):
+def loop_asm(K, fill=False):
     REG.update({f"x{k}": f"v{11 + k}" for k in range(K)})
     """One iteration = groups 0 .. K - 1 of the model's program as asm lines.  v0: store offsets (lanes a, d of the conveyor
     quads: the store of step 16 (g0 - 1) + 8, g0 = the iteration's first group), v1: load offsets (the conveyor's 16 lanes:
@@ -39,7 +44,7 @@ def loop_asm(K):
     wait = model.wait_count(K)
     for k in range(K):
         last = k == K - 1
-        for ins in model.group_program(k, K):
+        for ins in model.group_program(k, K, fill):
             op, step = ins[0], ins[1]
             s = step - model.G * k
             if op == "alpha":
@@ -63,31 +68,39 @@ def loop_asm(K):
                 out.append(f"s_waitcnt vmcnt({wait})")
             elif op == "nop4":
                 out.append("s_add_u32 %[cnt], %[cnt], 1" if last else "s_nop 0")
+            elif op == "fill":
+                out.append(f"v_and_b32_dpp {REG[ins[2]]}, {REG[ins[2]]}, {REG[ins[2]]} quad_perm:[0,1,2,3] {FULL}")
             elif op == "nop":
                 if last and s == 11:
                     out.append("v_add_u32_e64 v1, v1, v9")
                 elif last and s == 12:
                     out.append("v_add_u32_e64 v0, v0, v10")
                 else:
+                    assert not fill, (k, s)
                     out.append("v_nop_e64")
     return out
 
 
-def gen_loop(K=model.K_DEFAULT):
+def gen_loop(K=model.K_DEFAULT, fill=False):
     """the whole statement: VCC, the loop (%[cnt] counts up to 0), the wait for the last loads"""
-    return (["s_mov_b32 vcc_lo, -1", "s_mov_b32 vcc_hi, 0x3333ffff", ".p2align 5", "1:"] + loop_asm(K) +
+    return (["s_mov_b32 vcc_lo, -1", "s_mov_b32 vcc_hi, 0x3333ffff", ".p2align 5", "1:"] + loop_asm(K, fill) +
             ["s_cbranch_scc0 1b", "s_waitcnt vmcnt(0)", "s_nop 1"])
 
 
+def _macro(name, lines):
+    return f"#define {name} \\\n" + " \\\n".join('    "' + l + '\\n"' for l in lines) + "\n"
+
+
 def text(K=model.K_DEFAULT):
-    lines = gen_loop(K)
     return ("// generated by tools/gen_eq_quad_ring_asm.py -- do not edit\n"
-            f"#define EQ_QUAD_RING_K {K}\n"
-            "#define EQ_QUAD_RING_LOOP \\\n" + " \\\n".join('    "' + l + '\\n"' for l in lines) + "\n")
+            f"#define EQ_QUAD_RING_K {K}\n" + _macro("EQ_QUAD_RING_LOOP", gen_loop(K)) +
+            "// the same loop with the fill instruction in the slots that carry nothing (Tuning::eq_quad_fill)\n"
+            "#ifdef OHS_EXPERIMENTS\n" + _macro("EQ_QUAD_RING_LOOP_FILL", gen_loop(K, fill=True)) + "#endif\n")
 
 
 if __name__ == "__main__":
     model.check_hazards(model.K_DEFAULT)
+    model.check_hazards(model.K_DEFAULT, fill=True)
     out = os.path.join(os.path.dirname(HERE), "open_headstage_amd", "csrc", "eq_quad_ring_asm.inc")
     open(out, "w").write(text())
     print("wrote", out)

@@ -9,7 +9,8 @@ conveyor quad C1 = (1, 1, 0, 0), C2 = (0, 0, 1, 1).  A step (Zc = Z[step & 1], Z
 
     alpha   Zc = Zp(wave_ror:1) + G             a: x = y of the quad in front + 0   b: m2 + 0   c: t = m1 + s2   d: y = m0 + s1
     delta   Zp = Zo(quad_perm 0,0,0,3) * C2     a: m2 = b2 x   b: m1 = b1 x   c: m0 = b0 x   d: 1.0 y  (the next quad's a takes it)
-    <slot>  one issue slot that the DPP hazard leaves free: the port's instructions go here (else a no-op)
+    <slot>  one issue slot that the DPP hazard leaves free: the port's instructions go here; a slot with nothing to carry
+            holds a no-op or (group_program's fill) F = F(quad_perm 0,1,2,3) & F on a register that nothing else reads
     beta    P  = Zc(quad_perm 0,0,3,3) * C1     a, b: 1.0 x   c: p2 = a2 y   d: p1 = a1 y
     gamma   G  = Zc(quad_perm 0,0,1,2) - P      a, b: x - x = 0   c: s2' = m2 - p2   d: s1' = t - p1
 
@@ -49,6 +50,7 @@ LANES = 64
 G = 16                       # steps (= samples) per group
 Q0 = 12                      # first conveyor quad
 K_DEFAULT = 8                # groups between an input's request and its injection = x registers
+LOOP_OWN_SLOTS = (11, 12)    # steps of an iteration's last group whose slot carries the loop's own instructions
 TINY = np.finfo(F).tiny
 
 _lane = np.arange(LANES)
@@ -83,9 +85,14 @@ def lane_constants(table):
     return c1, c2
 
 
-def group_program(g, K=K_DEFAULT):
-    """The instructions of group g (steps 16g + 1 .. 16g + 16) in issue order: (op, step, ...)"""
+def group_program(g, K=K_DEFAULT, fill=False):
+    """The instructions of group g (steps 16g + 1 .. 16g + 16) in issue order: (op, step, ...).  fill: a slot that carries
+    nothing holds ("fill", step, "F") -- a VOP2+DPP instruction on a register F of its own, which keeps the vector unit for
+    the step instruction's four cycles where a no-op lets a wave beside this one issue -- instead of ("nop", step).  (The
+    experiments build's second loop; the product's has the no-ops: DESIGN.md 4.5, round 12.)  The two
+    slots of an iteration's last group that carry the loop's own offset advances (steps 11 and 12) stay ("nop", step)."""
     prog = []
+    own = (g + 1) % K == 0
     for s in range(1, G + 1):
         step = G * g + s
         zc, zo = f"Z{step & 1}", f"Z{(step - 1) & 1}"
@@ -102,6 +109,8 @@ def group_program(g, K=K_DEFAULT):
             prog.append(("store", step, zc))
         elif s == 16:
             prog.append(("inject", step, "A", f"x{(g + 1) % K}"))
+        elif fill and not (own and s in LOOP_OWN_SLOTS):
+            prog.append(("fill", step, "F"))
         else:
             prog.append(("nop", step))
         prog += [("beta", step, zc), ("gamma", step, zc), ("state", step)]
@@ -117,13 +126,13 @@ def wait_count(K=K_DEFAULT):
     return sum(1 for i in prog[ld + 1:at] if i[0] in ("load", "store"))
 
 
-def hazards(K=K_DEFAULT, extra=()):
+def hazards(K=K_DEFAULT, extra=(), fill=False):
     """(reader, step, register, distance) for every DPP read of the steady-state loop: distance = issue slots between the
     register's last VALU write and the read.  `extra`: instructions (op, dpp-read register, written register) put behind the
-    last step of every K groups (the loop's own: offset advances, counter)."""
+    last step of every K groups (the loop's own: offset advances, counter).  fill: the program with the fill instruction."""
     prog = []
     for g in range(2 * K, 4 * K):
-        prog += [i for i in group_program(g, K) if i[0] != "state"]
+        prog += [i for i in (group_program(g, K, True) if fill else group_program(g, K)) if i[0] != "state"]
         if (g + 1) % K == 0:
             prog += list(extra)
     last_write, out = {}, []
@@ -135,6 +144,7 @@ def hazards(K=K_DEFAULT, extra=()):
         elif op == "beta": dpp_read, write = ins[2], "P"
         elif op == "gamma": dpp_read, write = ins[2], "G"
         elif op == "inject": dpp_read, write = ins[3], "Zp"        # (x is written by a load: the wait covers it)
+        elif op == "fill": dpp_read, write = ins[2], ins[2]
         elif op == "valu": dpp_read, write = ins[1], ins[2]
         if dpp_read is not None and dpp_read in last_write and pos >= len(prog) // 2:     # (the second pass: all writers seen)
             out.append((op, ins[1], dpp_read, pos - last_write[dpp_read] - 1))
@@ -143,9 +153,9 @@ def hazards(K=K_DEFAULT, extra=()):
     return out
 
 
-def check_hazards(K=K_DEFAULT, verbose=False):
+def check_hazards(K=K_DEFAULT, verbose=False, fill=False):
     worst = {}
-    for op, step, reg, d in hazards(K):
+    for op, step, reg, d in hazards(K, fill=fill):
         key = (op, reg[:1] if reg.startswith("Z") and reg != "Zp" else reg)
         worst[key] = min(worst.get(key, 99), d)
     for (op, reg), d in sorted(worst.items()):
@@ -170,6 +180,7 @@ class Ring:
         self.C1, self.C2 = lane_constants(tab)
         self.K, self.mode = K, mode
         self.r = {k: np.zeros(LANES, F) for k in ["Z0", "Z1", "Zp", "G", "P"]}
+        self.r["F"] = np.zeros(LANES, np.uint32)        # the fill's own register
         for g in range(-1, K - 1):
             self.r[f"x{g % K}"] = self.load(g)
         self.y = np.zeros(self.n, F)
@@ -213,6 +224,8 @@ class Ring:
                 r["Zp"] = np.where(INJECT_LANES, r[ins[3]][QP_INJECT[ins[2]]], r["Zp"]).astype(F)
             elif o == "load":
                 r[ins[2]] = self.load(ins[3])
+            elif o == "fill":
+                r[ins[2]] = r[ins[2]][_perm([0, 1, 2, 3])] & r[ins[2]]
             elif o == "state":
                 for k in range(self.nb):
                     if step == 4 * k + 2:
@@ -226,11 +239,11 @@ def n_groups(n):
     return (n + 62 + G - 1) // G
 
 
-def ring_eq(x, table, state=None, K=K_DEFAULT, mode=0):
-    """One launch over x (float32 [n]) -> (y, new state [nb][2] = (s1, s2))"""
+def ring_eq(x, table, state=None, K=K_DEFAULT, mode=0, fill=False):
+    """One launch over x (float32 [n]) -> (y, new state [nb][2] = (s1, s2)); fill: the program with the fill instruction"""
     ring = Ring(x, table, state, K, mode)
     for g in range(-1, n_groups(ring.n)):
-        ring.run(group_program(g, K))
+        ring.run(group_program(g, K, True) if fill else group_program(g, K))
     assert np.all(ring.stored == 1), "every output is stored exactly once"
     return ring.y, ring.s_save
 
@@ -264,10 +277,10 @@ def random_table(rng, nb, fs=48000.0):
     return t
 
 
-def model_launches(x, table, sizes, K=K_DEFAULT, mode=0):
+def model_launches(x, table, sizes, K=K_DEFAULT, mode=0, fill=False):
     out, st, o = [], None, 0
     for n in sizes:
-        y, st = ring_eq(x[o:o + n], table, st, K, mode)
+        y, st = ring_eq(x[o:o + n], table, st, K, mode, fill)
         out.append(y)
         o += n
     return np.concatenate(out)
@@ -358,6 +371,11 @@ def run_asm(lines, v, x, y, stored, n, iters):
             elif op == "v_add_u32_e64":
                 d, a, b = (int(r[1:]) for r in t[1:4])
                 v[d] = (v[a] + v[b]).astype(np.uint32)
+            elif op == "v_and_b32_dpp":         # the fill: a register of its own, whatever it holds
+                d, a, b = (int(r[1:]) for r in t[1:4])
+                for k in (a, b):
+                    v.setdefault(k, np.zeros(LANES, np.uint32))
+                v[d] = dpp(v[a], re.search(r"quad_perm:\[[\d,]+\]", l).group(0)) & v[b]
             else:
                 assert op in ("v_nop_e64", "s_waitcnt", "s_nop", "s_add_u32"), l
 
@@ -419,6 +437,8 @@ if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     print(f"DPP read distances of the steady-state loop (K = {K_DEFAULT}, wait: vmcnt({wait_count()})):")
     check_hazards(verbose=True)
+    print("with the fill instruction in the slots that carry nothing:")
+    check_hazards(verbose=True, fill=True)
     for nb in range(1, 13):
         ok = check(nb, [700, 1, 333, 64, 1000])
         print(f"{nb:2d} bands, launches of 700 1 333 64 1000 samples: {'bit-exact' if ok else 'MISMATCH'}")
