@@ -289,6 +289,13 @@ int  ohs_sofa_resample_ir(const float *in, size_t n, float fs_in, float fs_out, 
  * out[p] (may be NULL, as may out) receives at most `capacity` samples of response p */
 int  ohs_sofa_speaker_irs(const ohs_sofa *sofa, float az_l, float el_l, float az_r, float el_r, float radius_m, float fs,
                           float *const out[4], size_t capacity, size_t lens[4]);
+/* K speakers -> out[n_channels][2][len], zero padded: per speaker what ohs_sofa_speaker_irs does per speaker (nearest measurement,
+ * the plugin's angle convention -- azimuth positive to the RIGHT --, resampled to fs; fs <= 0: the file's own samples), speaker c's
+ * left-ear response at out[c][0], its right-ear response at out[c][1]: the array ohs_batch_set_layout_irs takes.  1 <= n_channels
+ * <= 16.  *max_len = the longest response.  out == NULL queries *max_len; len < *max_len is OHS_ERR_INVALID_ARG (nothing is
+ * written).  No device needed. */
+int  ohs_sofa_layout_irs(const ohs_sofa *sofa, size_t n_channels, const float *az_deg, const float *el_deg,
+                         float radius_m, float fs, float *out, size_t len, size_t *max_len);
 int  ohs_engine_set_speakers(ohs_engine *e, const ohs_sofa *sofa, float az_l, float el_l, float az_r, float el_r,
                              float radius_m, float fs, unsigned *changed_mask);
 
@@ -536,6 +543,48 @@ int  ohs_batch_last_conv_ir_scheduled(const ohs_batch *b, int *scheduled);
 int  ohs_batch_process_ir_crossfaded(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
                                      size_t channel_stride, size_t seg_blocks, const unsigned *ir_idx, size_t idx_stride,
                                      const unsigned *prev_idx, void *hip_stream);
+/* ---- speaker layouts: K input channels (5.1, 7.1, ...) to a binaural pair in one kernel ----
+ * The reference's roadmap beyond its shipped code (ARCHITECTURE.md:118-119, TODO.md:268-269): "support 5.1 and 7.1 surround sound
+ * input, rendering a high-quality binaural mixdown".  Every channel c of a stream has a response to each ear, h[c][0] (left) and
+ * h[c][1] (right), and
+ *     y[s][e][n] = gain * sum_c sum_k h[c][e][k] * x[s][c][n - k],        continuous across calls.
+ * One kernel (k_conv_p1_layout, the block-512 family): per block one forward transform per PAIR of channels, the pairs' spectral
+ * products summed, ONE inverse transform -- against one forward and one inverse per pair, plus a summing pass, when the same mixdown
+ * is composed from ohs_batch_process calls on ceil(K / 2) handles.
+ *   Layout: ohs_batch_set_layout_irs(irs[n_channels][2][len]): channel c -> left ear irs[c][0], right ear irs[c][1];
+ *     1 <= n_channels <= 16, 1 <= len <= 512 (one partition).  Host array, copied before return.  It replaces any earlier layout and
+ *     zeroes the layout overlap of every stream (set_ir's rule, convolution.rs:135-138); n_channels == 0 frees the layout.  It
+ *     allocates and waits for the device: not for the audio path.  ohs_sofa_layout_irs builds the array from speaker angles.
+ *   Call: ohs_batch_process_layout processes n_blocks * 512 frames of every stream.  Sample (s, c, i) is read at
+ *     d_in[s * in_stream_stride + c * in_channel_stride + i], ear e of stream s is written at
+ *     d_out[s * out_stream_stride + e * out_channel_stride + i] (e = 0 left, 1 right); strides in floats.  Asynchronous on
+ *     hip_stream.  OUT OF PLACE ONLY: the input and output regions must not overlap (in-place calls are out of scope).
+ *   Gain and EQ order: the gain is the handle's (ohs_batch_set_gain), applied where the kernel stores, as in ohs_batch_process.  If
+ *     the handle's EQ is enabled (and any band is), it THEN filters the two ear channels of d_out in place, on the same stream
+ *     behind the convolution of the whole call, with the handle's table(s) and the handle's per-stream EQ state:
+ *         result = EQ(gain * conv(x)).
+ *     This differs from the stereo chain (EQ -> convolution -> gain): a headphone EQ belongs on the ear signals, and there it costs
+ *     two chains per stream instead of K.  The EQ is not overlapped with the convolution across time chunks (out of scope).
+ *   Layout overlap: the 512-frame overlap a call leaves is state of its own, independent of the handle's stereo convolution state:
+ *     ohs_batch_process* calls between layout calls do not touch it, layout calls do not touch the stereo state.  ohs_batch_reset
+ *     zeroes it (and the EQ state, as always).  The EQ state IS shared with the stereo calls.
+ *   Bits: the output does not depend on where the signal is cut into calls, nor on how many chunks per stream the launch uses
+ *     (ohs_batch_last_layout_launch).  With n_channels == 2 and the EQ off the call produces the bits of ohs_batch_process under
+ *     ohs_batch_set_conv_plan(1) with the paths Lsl = irs[0][0], Lsr = irs[0][1], Rsl = irs[1][0], Rsr = irs[1][1].
+ *   Odd n_channels: the last pair's second channel does not exist and is not read.
+ *   Out of scope: the node batch twin, the single-stream engine, responses longer than one partition (512 taps), combining with
+ *     the IR, EQ or gain schedules, in-place calls.  ohs_batch_last_conv_plan and ohs_batch_conv_plan_counts do not count layout
+ *     launches.
+ * OHS_ERR_INVALID_ARG, returned before anything is queued (the handle stays usable): a NULL argument; no layout uploaded;
+ * n_channels > 16; len == 0 or len > 512; strides smaller than the processed region; input and output regions that overlap;
+ * n_blocks > 2^24.  n_blocks == 0 is a no-op.  A HIP failure marks the handle failed until ohs_batch_reset, as in every other
+ * processing call. */
+int  ohs_batch_set_layout_irs(ohs_batch *b, size_t n_channels, const float *irs, size_t len);
+int  ohs_batch_process_layout(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
+                              size_t in_stream_stride, size_t in_channel_stride,
+                              size_t out_stream_stride, size_t out_channel_stride, void *hip_stream);
+/* pairs of channels and chunks per stream of the handle's most recent layout launch (0, 0: none yet) */
+int  ohs_batch_last_layout_launch(const ohs_batch *b, int *n_pairs, int *ranges_per_stream);
 /* The same as ohs_batch_process, but `hip_stream` is NOT made to wait for the last time chunk's convolution (it runs on an
  * internal stream underneath the EQ): d_out is complete on `hip_stream` only after ohs_batch_join (a
  * stream-side wait, asynchronous) or ohs_batch_sync.  Back-to-back deferred calls with the same buffers

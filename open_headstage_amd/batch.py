@@ -16,6 +16,13 @@ from ._ffi import check, fp, lib
 from .dsp import BLOCK_SIZE, BandConfig
 
 
+# Speaker layouts as plain data, channels in WAV order: (name, azimuth, elevation) in the plugin's degrees, azimuth positive to the
+# RIGHT.  (The LFE has no direction; it is rendered from the front.)
+LAYOUT_5_1 = (("L", -30.0, 0.0), ("R", 30.0, 0.0), ("C", 0.0, 0.0), ("LFE", 0.0, 0.0), ("Ls", -110.0, 0.0), ("Rs", 110.0, 0.0))
+LAYOUT_7_1 = (("L", -30.0, 0.0), ("R", 30.0, 0.0), ("C", 0.0, 0.0), ("LFE", 0.0, 0.0), ("Lb", -135.0, 0.0), ("Rb", 135.0, 0.0),
+              ("Ls", -90.0, 0.0), ("Rs", 90.0, 0.0))
+
+
 class BatchProcessor:
     def __init__(self, n_streams: int, num_bands: int = 10, device: int = 0, library=None):
         """library: the CDLL the handle lives in (default: the product library; _ffi.experiments_lib() for plan
@@ -24,6 +31,7 @@ class BatchProcessor:
         self.num_bands = int(num_bands)
         self.device = int(device)
         self._L = library
+        self._layout_k = 0      # channels of the layout set_layout_irs loaded (process_layout's shape check)
         h = C.c_void_p()
         self._check(self._lib.ohs_batch_create(self.device, self.n_streams, self.num_bands, C.byref(h)))
         self._h = h
@@ -308,6 +316,72 @@ class BatchProcessor:
             hip_stream = torch.cuda.current_stream(x.device).cuda_stream
         self.process_ir_scheduled_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, 2 * frames, frames, seg_blocks,
                                       ir_idx, mode, hip_stream)
+        return out
+
+    # -- speaker layouts: K channels -> two ears --------------------------------------------
+    def set_layout_irs(self, irs) -> None:
+        """The layout of process_layout: irs [K][2][len], channel c -> left ear irs[c][0], right ear irs[c][1]; K <= 16,
+        len <= 512.  Replaces any earlier layout and zeroes the layout overlap; an empty array frees it
+        (ohs_batch_set_layout_irs)."""
+        a = np.ascontiguousarray(irs, dtype=np.float32)
+        if a.size == 0:
+            self._check(self._lib.ohs_batch_set_layout_irs(self._h, 0, None, 0))
+            self._layout_k = 0
+            return
+        if a.ndim != 3 or a.shape[1] != 2:
+            raise ValueError(f"expected irs [n_channels][2][len], got {a.shape}")
+        self._check(self._lib.ohs_batch_set_layout_irs(self._h, a.shape[0], a.ctypes.data_as(fp), a.shape[2]))
+        self._layout_k = int(a.shape[0])
+
+    def set_layout_speakers(self, sofa, az, el=None, radius_m: float = 1.0, fs: float = 0.0) -> np.ndarray:
+        """One speaker per channel at the plugin's angles az[c], el[c] (degrees, azimuth positive to the right; el None: all 0),
+        or a preset such as LAYOUT_5_1 as `az`; -> the array [K][2][len] it loaded (ohs_sofa_layout_irs)."""
+        if el is None and len(az) and isinstance(az[0], (tuple, list)):
+            az, el = [r[1] for r in az], [r[2] for r in az]
+        if el is None:
+            el = [0.0] * len(az)
+        from .sofa import layout_irs
+        out = layout_irs(sofa, az, el, radius_m, fs)
+        if out.shape[2] > BLOCK_SIZE:
+            raise ValueError(f"a response of {out.shape[2]} taps: a layout holds one-partition responses (<= {BLOCK_SIZE} taps)")
+        self.set_layout_irs(out)
+        return out
+
+    def last_layout_launch(self):
+        """(pairs of channels, chunks per stream) of the most recent layout launch; (0, 0): none yet
+        (ohs_batch_last_layout_launch)"""
+        p, r = C.c_int(), C.c_int()
+        self._check(self._lib.ohs_batch_last_layout_launch(self._h, C.byref(p), C.byref(r)))
+        return int(p.value), int(r.value)
+
+    def process_layout_ptr(self, d_in: int, d_out: int, n_blocks: int, in_stream_stride: int, in_channel_stride: int,
+                           out_stream_stride: int, out_channel_stride: int, hip_stream: int = 0) -> None:
+        """ohs_batch_process_layout: n_blocks * 512 frames of every stream's K channels -> two ears; out of place only."""
+        self._check(self._lib.ohs_batch_process_layout(
+            self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(in_stream_stride), int(in_channel_stride),
+            int(out_stream_stride), int(out_channel_stride), C.c_void_p(hip_stream) if hip_stream else None))
+
+    def process_layout(self, x, out=None, hip_stream: int | None = None):
+        """x: contiguous float32 device tensor [streams, K, frames], frames a multiple of 512 -> [streams, 2, frames]:
+        gain * sum over channels of conv(h[c][ear], x[:, c]), then the handle's EQ on the two ears if it is enabled.
+        K is the layout's channel count; x may hold MORE channels than that -- the surplus is never read."""
+        import torch
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, channels, frames]")
+        S, ch, frames = x.shape
+        K = self._layout_k
+        if S != self.n_streams or frames % BLOCK_SIZE or ch < K:
+            raise ValueError(f"expected [{self.n_streams}, >= {K}, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
+        if x.device.index != self.device:
+            raise ValueError("tensor is on a different device than the BatchProcessor")
+        if out is None:
+            out = torch.empty((S, 2, frames), dtype=x.dtype, device=x.device)
+        elif tuple(out.shape) != (S, 2, frames) or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+            raise ValueError("out must be a contiguous [streams, 2, frames] tensor on x's device")
+        if hip_stream is None:
+            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+        self.process_layout_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, ch * frames, frames, 2 * frames, frames,
+                                hip_stream)
         return out
 
     def last_conv_ir_crossfaded(self) -> bool:

@@ -233,6 +233,7 @@ int ohs_batch_reset(ohs_batch *b)
     }
     c.cnt = 0;
     for (int p = 0; p < 4; ++p) c.since[p] = 0;
+    if (c.d_lay_ov) HIP_TRY(hipMemsetAsync(c.d_lay_ov, 0, c.S * 8 * 64 * sizeof(float2), b->st));     // (the layout's overlap)
     int rc = eq_reset(b->eq, b->st);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(b->st));
@@ -854,6 +855,79 @@ int ohs_batch_process_ir_crossfaded(ohs_batch *b, const float *d_in, float *d_ou
 {
     return batch_process_irs(b, d_in, d_out, n_blocks, stream_stride, channel_stride, seg_blocks, ir_idx, idx_stride,
                              OHS_IR_SWITCH_RING_OUT, true, prev_idx, hip_stream);
+}
+
+// ---- speaker layouts: K channels -> two ears in one kernel ---------------------------------------------------------
+int ohs_batch_set_layout_irs(ohs_batch *b, size_t n_channels, const float *irs, size_t len)
+{
+    if (!b) return fail(OHS_ERR_INVALID_ARG, "batch is NULL");
+    if (n_channels > 0 && !irs) return fail(OHS_ERR_INVALID_ARG, "irs is NULL");
+    if (n_channels > 16) return fail(OHS_ERR_INVALID_ARG, "n_channels must be at most 16");
+    if (n_channels > 0 && (len == 0 || len > (size_t)BS)) return fail(OHS_ERR_INVALID_ARG, "len must be 1 .. 512 (one partition)");
+    HIP_TRY(hipSetDevice(b->device));
+    DeviceWideSection dws;
+    HIP_TRY(hipDeviceSynchronize());
+    return conv_set_layout_irs(b->conv, b->ctx, n_channels, irs, len, b->st);
+}
+
+int ohs_batch_last_layout_launch(const ohs_batch *b, int *n_pairs, int *ranges_per_stream)
+{
+    if (!b || !n_pairs || !ranges_per_stream) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    *n_pairs = b->conv.last_lay_pairs;
+    *ranges_per_stream = b->conv.last_lay_ranges;
+    return OHS_OK;
+}
+
+// one strided region [n_outer][n_inner][frames] fits its strides: the inner index inside the outer stride, or the other way round
+static bool layout_strides_ok(size_t n_outer, size_t outer, size_t n_inner, size_t inner, size_t frames)
+{
+    if (n_inner > 1 && inner < frames) return false;
+    if (n_outer > 1 && outer < frames) return false;
+    if (n_outer <= 1 || n_inner <= 1) return true;
+    return outer >= (n_inner - 1) * inner + frames || inner >= (n_outer - 1) * outer + frames;
+}
+
+int ohs_batch_process_layout(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
+                             size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride, void *hip_stream)
+{
+    if (!b || !d_in || !d_out) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    ConvState &c = b->conv;
+    if (c.lay_K == 0 || !c.d_lay_cd) return fail(OHS_ERR_INVALID_ARG, "no layout uploaded (ohs_batch_set_layout_irs)");
+    if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
+    if (b->failed)
+        return fail(OHS_ERR_HIP, "this batch failed in the middle of an earlier call (" + b->fail_msg +
+                                     "): its per-stream state is half-advanced; ohs_batch_reset starts it afresh");
+    if (n_blocks == 0) return OHS_OK;
+    const size_t frames = n_blocks * BS, S = c.S, K = c.lay_K;
+    if (!layout_strides_ok(S, in_stream_stride, K, in_channel_stride, frames) ||
+        !layout_strides_ok(S, out_stream_stride, 2, out_channel_stride, frames))
+        return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
+    {   // out of place only: the two regions, first to last frame touched, must not meet
+        const float *in_end = d_in + (S - 1) * in_stream_stride + (K - 1) * in_channel_stride + frames;
+        const float *out_end = d_out + (S - 1) * out_stream_stride + out_channel_stride + frames;
+        if (!(in_end <= d_out || out_end <= d_in))
+            return fail(OHS_ERR_INVALID_ARG, "input and output regions overlap (the layout call is out of place only)");
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    auto body = [&]() -> int {
+        if (b->join_pending) {      // (a deferred call's last convolutions: the EQ state and d_out may be theirs)
+            HIP_TRY(hipStreamWaitEvent(st, b->chunk_done[(size_t)b->chunk_done_n - 1], 0));
+            b->join_pending = false;
+        }
+        int rc = conv_launch_layout(c, b->ctx, d_in, (long long)in_stream_stride, (long long)in_channel_stride, d_out,
+                                    (long long)out_stream_stride, (long long)out_channel_stride, (int)n_blocks, b->gain, st);
+        if (rc) return rc;
+        if (b->eq_enable && eq_any_enabled(b->eq))      // EQ(gain * conv(x)): the two ear channels, in place, behind the whole call
+            rc = eq_launch(b->eq, d_out, d_out, (long long)out_stream_stride, (long long)out_channel_stride, (long long)frames, st);
+        return rc;
+    };
+    const int rc = body();
+    if (rc == OHS_OK || rc == OHS_ERR_INVALID_ARG) return rc;
+    const std::string why = g_err;
+    b->failed = true;
+    b->fail_msg = why;
+    return fail(rc, why);
 }
 
 int ohs_batch_process_deferred(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,

@@ -29,7 +29,8 @@ void conv_free(ConvState &c)
     for (void *d : std::initializer_list<void *>{c.d_hist, c.d_pre, c.d_tails, c.d_tails_alt, c.d_cd, c.d_chunk_tails, c.d_cdm, c.d_W,
                                                  c.d_W1, c.d_merged, c.d_merged_alt, c.d_last_in, c.d_irt, c.d_cd_os, c.d_irl,
                                                  c.d_xhist, c.d_xhist_alt, c.d_lb_ring, c.d_lb_cd, c.d_lb_ab, c.d_lb_cd_alt,
-                                                 c.d_xb_cd, c.d_xb_ab, c.d_ptail, c.d_ptail_alt, c.d_irs_cd, c.d_irs_H, c.d_irs_t})
+                                                 c.d_xb_cd, c.d_xb_ab, c.d_ptail, c.d_ptail_alt, c.d_irs_cd, c.d_irs_H, c.d_irs_t,
+                                                 c.d_lay_cd, c.d_lay_ov, c.d_lay_ov_alt})
         if (d) hipFree(d);
 }
 
@@ -692,6 +693,83 @@ int conv_set_schedule_irs(ConvState &c, DeviceCtx *ctx, size_t n_sets, const flo
     return OHS_OK;
 }
 
+// The speaker layout of ohs_batch_process_layout.  irs[c][e] is row 2 c + e, so the four rows of pair p -- channel 2 p to both ears,
+// channel 2 p + 1 to both ears -- are the four paths Lsl, Lsr, Rsl, Rsr of a "set": the spectra by k_ir_spectrum, (C, D) by k_build_cd,
+// the block loop's layout by k_irs_tables, exactly as conv_set_schedule_irs builds a set (K = 2: the bits of a plain call on a handle
+// that loaded those four responses).  Odd K: the last pair's second channel has two all-zero rows.
+int conv_set_layout_irs(ConvState &c, DeviceCtx *ctx, size_t n_channels, const float *irs, size_t len, hipStream_t st)
+{
+    DeviceWideSection dws;      // (frees below)
+    for (void *d : std::initializer_list<void *>{c.d_lay_cd, c.d_lay_ov, c.d_lay_ov_alt})
+        if (d) hipFree(d);
+    c.d_lay_cd = nullptr; c.d_lay_ov = nullptr; c.d_lay_ov_alt = nullptr; c.lay_K = 0; c.lay_len = 0;
+    if (n_channels == 0) return OHS_OK;
+    const size_t P = (n_channels + 1) / 2;
+    std::vector<float> padded(P * 4 * (size_t)BS, 0.0f);
+    for (size_t r = 0; r < n_channels * 2; ++r) std::memcpy(&padded[r * BS], irs + r * len, len * sizeof(float));
+    float *d_t = nullptr;       // [P][4][512] scratch
+    float2 *d_H = nullptr;      // [P][4][1024] scratch
+    float2 *d_cd = nullptr;     // [P][2][1024] scratch
+    auto body = [&]() -> int {
+        HIP_TRY(hipMalloc(&d_t, padded.size() * sizeof(float)));
+        HIP_TRY(hipMalloc(&d_H, P * 4 * (size_t)NF * sizeof(float2)));
+        HIP_TRY(hipMalloc(&d_cd, P * 2 * (size_t)NF * sizeof(float2)));
+        HIP_TRY(hipMalloc(&c.d_lay_cd, P * (size_t)NF * sizeof(float4)));
+        HIP_TRY(hipMalloc(&c.d_lay_ov, c.S * 8 * 64 * sizeof(float2)));
+        HIP_TRY(hipMalloc(&c.d_lay_ov_alt, c.S * 8 * 64 * sizeof(float2)));
+        HIP_TRY(hipMemsetAsync(c.d_lay_ov, 0, c.S * 8 * 64 * sizeof(float2), st));
+        HIP_TRY(hipMemcpyAsync(d_t, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(launch_ir_spectrum(d_t, (int)padded.size(), (int)(P * 4), d_H, ctx->d_tw, st));
+        for (size_t p = 0; p < P; ++p) {
+            const float2 *h = d_H + p * 4 * (size_t)NF;
+            HIP_TRY(launch_build_cd(h, h + NF, h + 2 * NF, h + 3 * NF, d_cd + p * 2 * (size_t)NF, st));
+        }
+        HIP_TRY(launch_irs_tables(d_cd, (int)P, c.d_lay_cd, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return OHS_OK;
+    };
+    const int rc = body();
+    for (void *d : std::initializer_list<void *>{d_t, d_H, d_cd})
+        if (d) hipFree(d);
+    if (rc) {
+        for (void *d : std::initializer_list<void *>{c.d_lay_cd, c.d_lay_ov, c.d_lay_ov_alt})
+            if (d) hipFree(d);
+        c.d_lay_cd = nullptr; c.d_lay_ov = nullptr; c.d_lay_ov_alt = nullptr;
+        return rc;
+    }
+    c.lay_K = n_channels; c.lay_len = len;
+    return OHS_OK;
+}
+
+// Chunks per stream: conv_p1_chunks' rule for this kernel's resident waves, capped to 1 / 2 / 4 / 8 / 16 as conv_choose_plan caps
+// k_conv_p1_irs (every chunk but the first pays a dry block; there is no pre-pass)
+int conv_launch_layout(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
+                       float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st)
+{
+    if (!c.d_lay_cd || c.lay_K == 0) return fail(OHS_ERR_INVALID_ARG, "no layout uploaded (ohs_batch_set_layout_irs)");
+    if (n_blocks <= 0) return OHS_OK;
+    const long long want = conv_p1_chunks(ctx, c.S, n_blocks, 0, 8, conv_layout_waves_per_cu());
+    int K = 16;
+    while (K > want || K > n_blocks) K >>= 1;
+    ConvP1Args a{};
+    a.in = in; a.out = out;
+    a.in_stream_stride = in_ss; a.in_ch_stride = in_cs;
+    a.out_stream_stride = out_ss; a.out_ch_stride = out_cs;
+    a.n_blocks = n_blocks; a.n_streams = (int)c.S; a.chunks = K;
+    a.tw = ctx->d_tw; a.gain = gain; a.fp_mode = c.fp_mode;
+    a.xcd_lo = 0; a.xcd_n = 8;
+    for (int g = 0; g < 4; ++g) a.weights[g] = 1;
+    a.merged_in = c.d_lay_ov; a.merged_out = c.d_lay_ov_alt;
+    a.gain_seg = 1;
+    ConvLayoutArgs l;
+    l.cd = c.d_lay_cd; l.n_channels = (int)c.lay_K; l.n_pairs = (int)((c.lay_K + 1) / 2);
+    const hipError_t e = launch_conv_p1_layout(a, l, st);
+    if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_layout launch: ") + hipGetErrorString(e));
+    std::swap(c.d_lay_ov, c.d_lay_ov_alt);
+    c.last_lay_pairs = l.n_pairs; c.last_lay_ranges = K;
+    return OHS_OK;
+}
+
 // What four set_ir calls would load, without their resets: spectra, time-domain copies, every derived table invalid.
 int conv_adopt_schedule_set(ConvState &c, size_t set, hipStream_t st)
 {
@@ -718,9 +796,15 @@ int conv_adopt_schedule_set(ConvState &c, size_t set, hipStream_t st)
 // >= 97 % full.  (Rounds 1 and 2 asked for two rounds; since the chunk lengths follow the waves' age ranks one exact
 // round is the faster plan -- config 3 without EQ: 4096 waves 0.537-0.541 ms, 8192 waves 0.549-0.555, 3840 0.563,
 // 4352 0.81 -- and the pre-pass has half the boundary tails to compute.  Tuning::p1_rounds = 2 restores the old rule.)
-long long conv_p1_chunks(const DeviceCtx *ctx, size_t S, long long n_blocks, long long target_override, int xcd_n)
+// waves_per_cu == 0: k_conv_p1 and its kin, whose resident waves per CU follow the tuning (16 by default).  waves_per_cu > 0 is
+// the rule for ANOTHER kernel of the family with that many resident waves per CU -- k_conv_p1_layout, 12 -- and changes three
+// things: the round R = CUs x waves_per_cu; the one-chunk -> two-chunk rule below is off (it belongs to k_conv_p1's deal of
+// chunks over age ranks); and a short launch always prices 2 / 4 / 8 / 16 chunks as computing their own boundary tails,
+// because such a kernel has no pre-pass at all.
+long long conv_p1_chunks(const DeviceCtx *ctx, size_t S, long long n_blocks, long long target_override, int xcd_n, int waves_per_cu)
 {
-    const long long R = (long long)ctx->num_cus * xcd_n / 8 * conv_p1_waves_per_cu();
+    const int wpc = waves_per_cu > 0 ? waves_per_cu : conv_p1_waves_per_cu();
+    const long long R = (long long)ctx->num_cus * xcd_n / 8 * wpc;
     long long K;
     if (target_override > 0) {
         K = (target_override + (long long)S - 1) / (long long)S;
@@ -739,7 +823,7 @@ long long conv_p1_chunks(const DeviceCtx *ctx, size_t S, long long n_blocks, lon
     // One chunk per stream (4096 streams and more) leaves the age ranks nothing to balance: two chunks, dealt out over
     // ranks {0, 3} / {1, 2} (conv_kernels.hip: p1_wave_job), cost a second round but end together -- 4096 streams: 8.9 ->
     // 8.0 ms of convolution per step.
-    if (K == 1 && n_blocks >= 16 && target_override <= 0 && conv_p1_waves_per_cu() == 16) K = 2;
+    if (K == 1 && n_blocks >= 16 && target_override <= 0 && wpc == 16) K = 2;
     if (n_blocks < 4 * K && target_override <= 0) {
         // A short launch (the last, 2 % time chunk of an overlapped batch step: 19 blocks), a few blocks per wave at
         // best: every chunk boundary costs the pre-pass a block's work, and a wave count just above a round starts a second,
@@ -747,7 +831,7 @@ long long conv_p1_chunks(const DeviceCtx *ctx, size_t S, long long n_blocks, lon
         // tails (one more block per wave where the chunks' own waves compute them -- K = 2, 4, 8, 16 --, else a pre-pass
         // launch: its rounds + about a block time of launch); the smallest K of minimal cost (19 blocks x 256 streams:
         // K = 16, one round of at most 2 + 1 blocks, no pre-pass).
-        const bool own_ok = conv_p1_waves_per_cu() == 16;
+        const bool own_ok = wpc == 16 || waves_per_cu > 0;    // (the layout kernel's chunks always compute their own)
         long long best_k = std::min(K, n_blocks), best_cost = -1;
         for (long long k = 1; k <= std::min(K, n_blocks); ++k) {
             const long long rounds_main = ((long long)S * k + R - 1) / R, per_wave = (n_blocks + k - 1) / k;

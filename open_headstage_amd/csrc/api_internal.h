@@ -207,6 +207,13 @@ struct ConvState {
     bool tails_both = false;
     bool last_ir_scheduled = false; // the last conv_launch looked the set up per block (ohs_batch_last_conv_ir_scheduled)
     bool last_ir_crossfaded = false;    // ... with the crossfading kernel k_conv_p1_irs_xf (the query then reports 2)
+    // The speaker layout of ohs_batch_process_layout (ohs_batch_set_layout_irs): lay_K channels of two responses each (at most 512 taps),
+    // as the (C, D) table of every PAIR of channels that k_conv_p1_layout reads, and the layout's own merged overlap -- two slabs, the
+    // launch reads d_lay_ov and writes d_lay_ov_alt, then they swap.  Independent of everything above: the stereo calls never touch it.
+    size_t lay_K = 0, lay_len = 0;
+    float4 *d_lay_cd = nullptr;     // [ceil(lay_K / 2)][1024]
+    float2 *d_lay_ov = nullptr, *d_lay_ov_alt = nullptr;    // [S][8][64]
+    int last_lay_pairs = 0, last_lay_ranges = 0;    // the most recent layout launch (ohs_batch_last_layout_launch)
     // ohs_*_set_speakers: what it last loaded into each path (a set_ir from anywhere else forgets it), so that a
     // change of the speaker angles re-loads only the paths whose impulse response really changed
     std::vector<float> spk_ir[4];
@@ -253,7 +260,8 @@ bool conv_plan_auto_is_lb(size_t S, long long n_blocks, int Pmax);
 bool conv_plan_auto_is_xb(size_t S, long long n_blocks, int Pmax);      // ... and among those, the block-8192 kernel (out-of-place calls)
 int conv_os_chunks(const DeviceCtx *ctx, size_t S, long long n_blocks, bool in_place);
 // time chunks per stream of the one-partition kernel's launch plan (also what ohs_batch_kernel_bytes prices)
-long long conv_p1_chunks(const DeviceCtx *ctx, size_t S, long long n_blocks, long long target_override, int xcd_n = 8);
+long long conv_p1_chunks(const DeviceCtx *ctx, size_t S, long long n_blocks, long long target_override, int xcd_n = 8,
+                         int waves_per_cu = 0);      // (0: k_conv_p1's; k_conv_p1_layout passes its own)
 // a gain per segment of seg_blocks blocks (device memory): block t of the launch, block blk_off + t of the call, leaves with
 // tab[(blk_off + t) / seg_blocks].  NULL (or tab == NULL): the scalar `gain`.
 // stream_stride: stream s reads its row at tab + s * stream_stride (0: one row for all streams).
@@ -284,6 +292,12 @@ int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, 
                 const ConvGains *gains = nullptr, const ConvIrs *irs = nullptr);
 // the set table (host array irs[n_sets][4][len], 1 <= len <= 512; n_sets == 0 frees it); the caller has drained the device
 int conv_set_schedule_irs(ConvState &c, DeviceCtx *ctx, size_t n_sets, const float *irs, size_t len, hipStream_t st);
+// the speaker layout (host array irs[n_channels][2][len], 1 <= len <= 512; n_channels == 0 frees it) and its zeroed overlap; the
+// caller has drained the device
+int conv_set_layout_irs(ConvState &c, DeviceCtx *ctx, size_t n_channels, const float *irs, size_t len, hipStream_t st);
+// n_blocks of every stream's lay_K channels -> two ears, times gain; out of place (the caller checks), asynchronous on st
+int conv_launch_layout(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
+                       float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st);
 // the handle's four responses become set `set` of the table, overlaps and history untouched (asynchronous on st)
 int conv_adopt_schedule_set(ConvState &c, size_t set, hipStream_t st);
 // the per-path overlaps from the lazy state with the CURRENT spectra, the lazy state kept valid beside them (tails_both)

@@ -1384,6 +1384,152 @@ __global__ __launch_bounds__(64 * kP1Waves) void k_conv_p1_irs_xf(const ConvP1Ar
 #undef OHS_P1_PRE_PRODUCT
 #undef OHS_P1_PRODUCT
 
+// k_conv_p1_layout (ohs_batch_process_layout; kernels.h: ConvLayoutArgs): K input channels -> two ears.  The packed product already
+// sums a pair of channels into W = Y_l + j Y_r, and the sum over pairs is linear in W: per block, one forward transform and one
+// product per pair of channels, all accumulated in the same sixteen registers, then ONE inverse transform, the overlap-add and the
+// store.  Pair 0's product is p1_spectral_product_paired_global (K = 2: the bits of k_conv_p1_irs on one set, which are k_conv_p1's);
+// pair p >= 1 adds the same expression to w.  (C_p, D_p) come from the device table L.cd ([pair][1024] float4, launch_irs_tables with
+// a pair as a "set"): an L2 hit, as in k_conv_p1_irs.  Odd K: the last pair's second channel is not read -- its imaginary input is
+// zero, and so are its two responses in the table.
+// A body of its own, not an includer of conv_p1_body.inc: the accumulator stays alive across every forward transform but the
+// first, which does not fit the 128 registers a 16-wave workgroup leaves a wave (w 32 + v 32 + overlap 16 + the next pair's
+// prefetch 16 = 96 under the transform's own ~80: k_conv_p1_irs_xf's comment tells the same story for 80 of them).  So this kernel
+// runs THREE waves per SIMD (a budget of 168 registers per wave, of which it uses 157), in workgroups of kLayoutWaves waves with one
+// slab each and no (C, D) area.  The call is out of place, so a
+// stream's chunks need not share a workgroup and there is no barrier behind the table fill: wave gw is chunk gw % chunks of stream
+// gw / chunks, the chunks are equal block ranges, and every chunk but the first runs one dry block in front of its range.
+// Prefetch: pair p + 1's sixteen dwords are requested in front of pair p's forward transform, the next block's pair 0 in front of
+// the inverse transform -- both a whole transform ahead of their use, which the register budget of three waves allows.
+#ifndef OHS_LAYOUT_WAVES
+#define OHS_LAYOUT_WAVES 4
+#endif
+#ifndef OHS_LAYOUT_WAVES_PER_SIMD
+#define OHS_LAYOUT_WAVES_PER_SIMD 3
+#endif
+constexpr int kLayoutWaves = OHS_LAYOUT_WAVES;              // per workgroup: one wave per SIMD, three workgroups per CU
+constexpr int kLayoutWavesPerSimd = OHS_LAYOUT_WAVES_PER_SIMD;
+static_assert((4 * kLayoutWavesPerSimd) % kLayoutWaves == 0, "k_conv_p1_layout: whole workgroups per CU");
+static_assert((kTabComplex + kLayoutWaves * kWaveLdsComplex) * sizeof(float2) * (4 * kLayoutWavesPerSimd / kLayoutWaves) <= 160 * 1024,
+              "k_conv_p1_layout: LDS plan");
+
+// w += Z C + conj(Zm) D: the expression of p1_spectral_product_paired_global, added to the accumulator
+__device__ __forceinline__ void p1_spectral_product_paired_global_add(const float2 (&z)[16], float2 (&w)[16], const float4 *cdp, int lane)
+{
+    constexpr int G = OHS_P1_IRS_GROUP;
+    const bool lane32 = lane == 32;
+#pragma unroll
+    for (int g = 0; g < 16 / G; ++g) {
+        float4 q[G];
+        OHS_P1_IRS_FENCE
+#pragma unroll
+        for (int j = 0; j < G; ++j) q[j] = cdp[(G * g + j) * 64];
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            const int i = G * g + j;
+            const float2 zz = z[i], m = paired_mirror(z, i >> 2, i & 3, lane32);
+            const float2 c = make_float2(q[j].x, q[j].y), d = make_float2(q[j].z, q[j].w);
+            w[i].x += fmaf(m.y, d.y, fmaf(m.x, d.x, fmaf(-zz.y, c.y, zz.x * c.x)));
+            w[i].y += fmaf(-m.y, d.x, fmaf(m.x, d.y, fmaf(zz.y, c.x, zz.x * c.y)));
+        }
+    }
+}
+
+__global__ __launch_bounds__(64 * kLayoutWaves, kLayoutWavesPerSimd) void k_conv_p1_layout(const ConvP1Args A, const ConvLayoutArgs L)
+{
+    const long long wg = p1_xcd_block(A);
+    if (wg < 0) return;
+    ohs_set_fp_mode(A.fp_mode);
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    float2 *tab = smem;
+    fill_twiddle_tables(tab, A.tw, threadIdx.x, 64 * kLayoutWaves);
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const unsigned ul = (unsigned)lane;     // (audio and table accesses are wave-uniform base + lane: the bases stay in SGPRs)
+    float2 *lds = smem + kTabComplex + wave * kWaveLdsComplex;
+    const long long gw = wg * kLayoutWaves + wave;
+    if (gw >= (long long)A.n_streams * A.chunks) return;
+    const int s = __builtin_amdgcn_readfirstlane((int)(gw / A.chunks));
+    const int ck = __builtin_amdgcn_readfirstlane((int)(gw % A.chunks));
+    // equal ranges; the host keeps chunks <= n_blocks, so none is empty
+    const int b0 = __builtin_amdgcn_readfirstlane((int)((long long)ck * A.n_blocks / A.chunks));
+    const int b1 = __builtin_amdgcn_readfirstlane((int)((long long)(ck + 1) * A.n_blocks / A.chunks));
+    if (b0 >= b1) return;
+    const int t_first = ck > 0 ? b0 - 1 : b0;       // (the dry block: its overlap is all that is wanted)
+    const int P = L.n_pairs, K = L.n_channels;
+
+    const float *in_s = A.in + (size_t)s * A.in_stream_stride;
+    float *ql = A.out + (size_t)s * A.out_stream_stride + (size_t)t_first * kBlock;
+
+    float2 tail[8];
+    if (ck == 0) {
+        const float2 *mt = A.merged_in + (size_t)s * (8 * 64);
+#pragma unroll
+        for (int a = 0; a < 8; ++a) tail[a] = mt[a * 64 + ul];
+    } else {
+#pragma unroll
+        for (int a = 0; a < 8; ++a) tail[a] = make_float2(0.0f, 0.0f);
+    }
+    // the frames of channels 2 p (xa) and 2 p + 1 (xb) of block t; a channel beyond K - 1 is not read
+    float xa[8], xb[8];
+    auto request = [&](int t, int p) {
+        unsigned u = ul;
+        asm volatile("" : "+v"(u));     // (the per-lane address is formed here, two additions, not carried across the transforms)
+        const float *pa = in_s + (size_t)(2 * p) * A.in_ch_stride + (size_t)t * kBlock + u;
+#pragma unroll
+        for (int a = 0; a < 8; ++a) xa[a] = OHS_P1_LD(&pa[64 * a]);
+        if (2 * p + 1 < K) {
+            const float *pb = pa + A.in_ch_stride;
+#pragma unroll
+            for (int a = 0; a < 8; ++a) xb[a] = OHS_P1_LD(&pb[64 * a]);
+        } else {
+#pragma unroll
+            for (int a = 0; a < 8; ++a) xb[a] = 0.0f;
+        }
+    };
+    request(t_first, 0);
+    const PairedPlan plan = paired_plan(lane);
+    for (int t = t_first; t < b1; ++t) {
+        const bool dry = t < b0;
+        float2 w[16];
+        for (int p = 0; p < P; ++p) {
+            float2 v[16];
+#pragma unroll
+            for (int a = 0; a < 8; ++a) {
+                v[a] = make_float2(xa[a], xb[a]);
+                v[a + 8] = make_float2(0.0f, 0.0f);
+            }
+            if (p + 1 < P) request(t, p + 1);
+            wave_fft_fwd_paired(v, lds, tab, lane, plan);
+            unsigned u = ul;
+            asm volatile("" : "+v"(u));
+            const float4 *cdp = L.cd + (size_t)p * kFft + u;
+            if (p == 0) p1_spectral_product_paired_global(v, w, cdp, lane);
+            else p1_spectral_product_paired_global_add(v, w, cdp, lane);
+        }
+        // behind the launch's last block the prefetch re-reads that block (its own frames: in bounds; the values are never used)
+        request(t + 1 < A.n_blocks ? t + 1 : t, 0);
+        wave_fft_inv_paired(w, lds, tab, lane, plan);
+        if (!dry) {
+            unsigned u = ul;
+            asm volatile("" : "+v"(u));
+            float *pl = ql + u, *pr = pl + A.out_ch_stride;
+#pragma unroll
+            for (int a = 0; a < 8; ++a) {
+                OHS_P1_ST(&pl[64 * a], (w[a].x + tail[a].x) * A.gain);          // (1/N is in C and D)
+                OHS_P1_ST(&pr[64 * a], (w[a].y + tail[a].y) * A.gain);
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < 8; ++a) tail[a] = w[a + 8];
+        ql += kBlock;
+    }
+    if (b1 == A.n_blocks) {         // the overlap the call leaves behind
+        float2 *mo = A.merged_out + (size_t)s * (8 * 64);
+#pragma unroll
+        for (int a = 0; a < 8; ++a) mo[a * 64 + ul] = tail[a];
+    }
+}
+
 // pre-pass, two small kernels that read INPUT frames only -- which is why they run before the main kernel stores over
 // them (in place) -- one transform pair per wave:
 //   k_conv_p1_state  wave (s, speaker): the overlap the launch's last block leaves behind in the reference's per-path
@@ -1712,6 +1858,27 @@ hipError_t launch_conv_p1_irs_xf(const ConvP1Args &a, const ConvIrXfArgs &i, hip
     const dim3 grid(xcd_grid((unsigned)((waves + kP1Waves - 1) / kP1Waves), a.xcd_n));
     if (ev_start || ev_stop) hipExtLaunchKernelGGL(k_conv_p1_irs_xf, grid, dim3(64 * kP1Waves), shmem_main, st, ev_start, ev_stop, 0, a, i);
     else hipLaunchKernelGGL(k_conv_p1_irs_xf, grid, dim3(64 * kP1Waves), shmem_main, st, a, i);
+    return hipGetLastError();
+}
+
+int conv_layout_waves_per_cu() { return 4 * kLayoutWavesPerSimd; }
+
+// the layout kernel: one launch, no pre-pass, out of place
+hipError_t launch_conv_p1_layout(const ConvP1Args &a, const ConvLayoutArgs &l, hipStream_t st)
+{
+    if (a.n_blocks <= 0 || a.n_streams <= 0 || a.chunks > a.n_blocks) return hipErrorInvalidValue;
+    if (!(a.chunks == 1 || a.chunks == 2 || a.chunks == 4 || a.chunks == 8 || a.chunks == 16)) return hipErrorInvalidValue;
+    // (no 32-bit limit on n_blocks * 512 as in the launchers above: the kernel forms every frame offset in 64 bits)
+    if (a.xcd_n < 1 || a.xcd_n > 8 || a.xcd_lo < 0 || a.xcd_lo + a.xcd_n > 8) return hipErrorInvalidValue;
+    if (!a.in || !a.out || !a.merged_in || !a.merged_out || a.merged_in == a.merged_out || !a.tw) return hipErrorInvalidValue;
+    if (!l.cd || l.n_channels < 1 || l.n_pairs != (l.n_channels + 1) / 2) return hipErrorInvalidValue;
+    const size_t shmem = (kTabComplex + kLayoutWaves * kWaveLdsComplex) * sizeof(float2);
+    static std::atomic<unsigned long long> lds_ok{0};
+    hipError_t e = allow_large_lds(reinterpret_cast<const void *>(k_conv_p1_layout), shmem, lds_ok);
+    if (e != hipSuccess) return e;
+    const long long waves = (long long)a.n_streams * a.chunks;
+    const dim3 grid(xcd_grid((unsigned)((waves + kLayoutWaves - 1) / kLayoutWaves), a.xcd_n));
+    hipLaunchKernelGGL(k_conv_p1_layout, grid, dim3(64 * kLayoutWaves), shmem, st, a, l);
     return hipGetLastError();
 }
 

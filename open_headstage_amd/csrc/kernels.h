@@ -266,6 +266,19 @@ hipError_t launch_conv_p1_irs_xf(const ConvP1Args &a, const ConvIrXfArgs &i, hip
                                  hipEvent_t ev_stop = nullptr);
 // launch_conv_p1_state_irs for a call block i.off that may have faded: the per-path overlaps state(x g, old set) + state(x f, its set)
 hipError_t launch_conv_p1_state_irs_xf(const ConvP1Args &a, const ConvIrXfArgs &i, hipStream_t st);
+// K input channels -> two ears (ohs_batch_process_layout): k_conv_p1_layout, one forward transform and one product per PAIR of
+// channels accumulated in one spectrum, one inverse transform per block.  A second kernel argument beside ConvP1Args, of which the
+// kernel reads: in / out and their strides (in_ch_stride: channel c of a stream at c * in_ch_stride), n_blocks, n_streams, chunks,
+// tw, gain, fp_mode, xcd_lo / xcd_n, merged_in (never NULL: the layout overlap the call starts from) and merged_out (a different
+// slab; the host swaps them).  Out of place only.
+struct ConvLayoutArgs {
+    const float4 *cd;           // [pair][1024] (C[i], D[i]) of channels 2 p and 2 p + 1 in the paired layout (launch_irs_tables)
+    int n_pairs;                // ceil(n_channels / 2)
+    int n_channels;             // odd: channel 2 n_pairs - 1 is not read (and its two responses in cd are zero)
+};
+int conv_layout_waves_per_cu();  // resident waves of k_conv_p1_layout per CU
+// a.chunks: 1, 2, 4, 8 or 16, <= a.n_blocks; every chunk but the first runs one dry block in front of its range
+hipError_t launch_conv_p1_layout(const ConvP1Args &a, const ConvLayoutArgs &l, hipStream_t st);
 // cd[set][2][1024] (launch_build_cd per set) -> dst[set][1024] in the block loop's layout
 hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st);
 // CD[0][..] = (A - jB)/2, CD[1][..] = (A + jB)/2 from four single-partition spectra

@@ -136,6 +136,23 @@ def speaker_irs_plugin_angles(sofa: MySofa, az_l: float = -30.0, el_l: float = 0
     return outs
 
 
+def layout_irs(sofa: MySofa, az, el, radius_m: float = 1.0, fs: float = 0.0, length: int | None = None) -> np.ndarray:
+    """[K][2][len] for K speakers at the PLUGIN's angles az[c], el[c] (degrees, azimuth positive to the right): speaker c's
+    left-ear and right-ear responses, zero-padded to `length` (default: the longest response) -- ohs_sofa_layout_irs, the array
+    BatchProcessor.set_layout_irs takes."""
+    azf = np.ascontiguousarray(az, np.float32).ravel()
+    elf = np.ascontiguousarray(el, np.float32).ravel()
+    if azf.size != elf.size:
+        raise ValueError("az and el must have one entry per speaker")
+    n = C.c_size_t()
+    check(lib().ohs_sofa_layout_irs(sofa._h, azf.size, azf.ctypes.data_as(fp), elf.ctypes.data_as(fp), radius_m, fs, None, 0, C.byref(n)))
+    ln = int(n.value) if length is None else int(length)
+    out = np.zeros((azf.size, 2, max(ln, 1)), np.float32)
+    check(lib().ohs_sofa_layout_irs(sofa._h, azf.size, azf.ctypes.data_as(fp), elf.ctypes.data_as(fp), radius_m, fs,
+                                    out.ctypes.data_as(fp), ln, C.byref(n)))
+    return out
+
+
 def load_into(target, irs) -> None:
     """get_hrtf_irs -> set_ir wiring: target is a ConvolutionEngine or a BatchProcessor."""
     for p, h in zip((ConvolutionPath.Lsl, ConvolutionPath.Lsr, ConvolutionPath.Rsl, ConvolutionPath.Rsr), irs):
