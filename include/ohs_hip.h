@@ -296,6 +296,14 @@ int  ohs_sofa_speaker_irs(const ohs_sofa *sofa, float az_l, float el_l, float az
  * written).  No device needed. */
 int  ohs_sofa_layout_irs(const ohs_sofa *sofa, size_t n_channels, const float *az_deg, const float *el_deg,
                          float radius_m, float fs, float *out, size_t len, size_t *max_len);
+/* A table of layouts for ohs_batch_set_layout_schedule_irs, one set per head yaw: out[n_yaws][n_channels][2][len], set j being what
+ * ohs_sofa_layout_irs gives with every speaker at az_deg[c] - yaw_deg[j], wrapped into [-180, 180) (azimuth is positive to the RIGHT,
+ * and so is yaw: a head turned to the right by yaw sees every speaker that far to the left).  All sets share one length:
+ * *needed_len = the longest response of any set.  out == NULL queries *needed_len; len < *needed_len is OHS_ERR_INVALID_ARG (nothing
+ * is written).  1 <= n_channels <= 16, 1 <= n_yaws <= 65536.  No device needed. */
+int  ohs_sofa_layout_yaw_irs(const ohs_sofa *sofa, size_t n_channels, const float *az_deg, const float *el_deg,
+                             float radius_m, float fs, size_t n_yaws, const float *yaw_deg, float *out, size_t len,
+                             size_t *needed_len);
 int  ohs_engine_set_speakers(ohs_engine *e, const ohs_sofa *sofa, float az_l, float el_l, float az_r, float el_r,
                              float radius_m, float fs, unsigned *changed_mask);
 
@@ -553,7 +561,8 @@ int  ohs_batch_process_ir_crossfaded(ohs_batch *b, const float *d_in, float *d_o
  * is composed from ohs_batch_process calls on ceil(K / 2) handles.
  *   Layout: ohs_batch_set_layout_irs(irs[n_channels][2][len]): channel c -> left ear irs[c][0], right ear irs[c][1];
  *     1 <= n_channels <= 16, 1 <= len <= 512 (one partition).  Host array, copied before return.  It replaces any earlier layout and
- *     zeroes the layout overlap of every stream (set_ir's rule, convolution.rs:135-138); n_channels == 0 frees the layout.  It
+ *     zeroes the layout overlap of every stream (set_ir's rule, convolution.rs:135-138); n_channels == 0 frees the layout -- and,
+ *     where a table of layouts (ohs_batch_set_layout_schedule_irs) keeps the overlap alive, zeroes that shared overlap too.  It
  *     allocates and waits for the device: not for the audio path.  ohs_sofa_layout_irs builds the array from speaker angles.
  *   Call: ohs_batch_process_layout processes n_blocks * 512 frames of every stream.  Sample (s, c, i) is read at
  *     d_in[s * in_stream_stride + c * in_channel_stride + i], ear e of stream s is written at
@@ -573,7 +582,8 @@ int  ohs_batch_process_ir_crossfaded(ohs_batch *b, const float *d_in, float *d_o
  *     ohs_batch_set_conv_plan(1) with the paths Lsl = irs[0][0], Lsr = irs[0][1], Rsl = irs[1][0], Rsr = irs[1][1].
  *   Odd n_channels: the last pair's second channel does not exist and is not read.
  *   Out of scope: the node batch twin, the single-stream engine, responses longer than one partition (512 taps), combining with
- *     the IR, EQ or gain schedules, in-place calls.  ohs_batch_last_conv_plan and ohs_batch_conv_plan_counts do not count layout
+ *     the EQ or gain schedules, in-place calls (a schedule of LAYOUTS is ohs_batch_process_layout_scheduled below).
+ *     ohs_batch_last_conv_plan and ohs_batch_conv_plan_counts do not count layout
  *     launches.
  * OHS_ERR_INVALID_ARG, returned before anything is queued (the handle stays usable): a NULL argument; no layout uploaded;
  * n_channels > 16; len == 0 or len > 512; strides smaller than the processed region; input and output regions that overlap;
@@ -585,6 +595,53 @@ int  ohs_batch_process_layout(ohs_batch *b, const float *d_in, float *d_out, siz
                               size_t out_stream_stride, size_t out_channel_stride, void *hip_stream);
 /* pairs of channels and chunks per stream of the handle's most recent layout launch (0, 0: none yet) */
 int  ohs_batch_last_layout_launch(const ohs_batch *b, int *n_pairs, int *ranges_per_stream);
+/* ---- head-tracked speaker layouts: a table of layouts, walked per stream and segment inside one kernel ----
+ * A virtual 5.1 / 7.1 room over headphones is the case in which the head turns and EVERY speaker's pair of responses changes
+ * together: the layout call above with a set of layouts per segment, as ohs_batch_process_ir_crossfaded has a set of four responses
+ * per segment.  One kernel (k_conv_p1_layout_irs, a sibling of k_conv_p1_layout): the set index is one scalar load per block; a
+ * fading block runs 2 P forward transforms and products -- the old set's, then the new one's -- into one spectrum and ONE inverse
+ * transform.
+ *   Table: ohs_batch_set_layout_schedule_irs(irs[n_sets][n_channels][2][len]): set j, channel c -> left ear irs[j][c][0], right ear
+ *     irs[j][c][1]; 1 <= n_channels <= 16, 1 <= len <= 512 (one partition), 1 <= n_sets <= 65536.  Host array, copied before return.
+ *     It replaces any earlier table and zeroes the layout overlap of every stream; n_sets == 0 frees the table.  The table is
+ *     independent of the single layout of ohs_batch_set_layout_irs: either may exist without the other (the overlap lives while
+ *     either does).  It allocates and waits for the device: not for the audio path.  ohs_sofa_layout_yaw_irs builds the array from
+ *     speaker angles and head yaws.
+ *   Call: strides, gain, the out-of-place-only rule, result = EQ(gain * conv(x)) and the shared EQ state are those of
+ *     ohs_batch_process_layout; K is the table's channel count.  Segments of seg_blocks blocks, set_idx, idx_stride (0: one row for
+ *     all streams, else >= the number of segments: stream s reads set_idx[s * idx_stride + k]) and prev_idx (one entry when
+ *     idx_stride == 0, else one per stream; NULL: the call's start is no boundary) are those of ohs_batch_process_ir_crossfaded.
+ *     prev_idx is read under OHS_LAYOUT_SWITCH_CROSSFADE only.
+ *   Block t of stream s has the set `cur` of its segment.  Under CROSSFADE it also has `old`: the previous segment's set in the first
+ *     block of a segment, prev_idx[s] in the first block of the call, `cur` everywhere else.  Under RING_OUT old = cur always: a new
+ *     set serves from its segment's first frame on, the earlier one's tail rings out.
+ *     old == cur: the block is ohs_batch_process_layout's block on set cur, with its arithmetic and its bits.
+ *     old != cur: with f[n] = n / 512 and g[n] = (512 - n) / 512 (exact in f32; one multiplication per sample and channel), x g goes
+ *       through all K x 2 responses of `old` and x f through all of `cur`; the 2 P products are accumulated in pair order, `old`
+ *       first, in one spectrum with one inverse transform; the frames leave as (w + overlap) * gain, the upper half is the overlap
+ *       the block leaves.  (With K = 2 the result is ohs_batch_process_ir_crossfaded's within rounding, not in bits: that call sums
+ *       two inverse transforms.)
+ *   Overlap: the handle's layout overlap, shared with ohs_batch_process_layout -- the two calls continue one another.
+ *     ohs_batch_reset zeroes it.  The bits do not depend on where the signal is cut into calls (prev_idx naming the set in front of
+ *     the cut) nor on the chunks per stream.
+ *   Launches: a shared row naming one set throughout, with prev_idx NULL or equal to it, is served by k_conv_p1_layout on that set's
+ *     slice of the table (ohs_batch_last_layout_scheduled: 0); every other call is one launch of k_conv_p1_layout_irs (1).
+ *     ohs_batch_last_layout_launch reports the table's pairs and the chunks, as before.
+ *   Out of scope: the node batch twin, responses beyond one partition, in-place calls, a CUT mode, fade lengths other than one block,
+ *     the EQ overlapped with the convolution.
+ * OHS_ERR_INVALID_ARG, returned before anything is queued (the handle stays usable): everything ohs_batch_process_layout refuses
+ * (with "no table uploaded" in place of "no layout"); seg_blocks == 0; a NULL set_idx; an index or prev_idx entry >= n_sets; a
+ * non-zero idx_stride below the number of segments; an unknown switch_mode; at upload n_sets > 65536, n_channels == 0 or > 16,
+ * len == 0 or > 512, a NULL irs. */
+int  ohs_batch_set_layout_schedule_irs(ohs_batch *b, size_t n_sets, size_t n_channels, const float *irs, size_t len);
+enum { OHS_LAYOUT_SWITCH_RING_OUT = 0, OHS_LAYOUT_SWITCH_CROSSFADE = 1 };
+int  ohs_batch_process_layout_scheduled(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
+                                        size_t in_stream_stride, size_t in_channel_stride,
+                                        size_t out_stream_stride, size_t out_channel_stride,
+                                        size_t seg_blocks, const unsigned *set_idx, size_t idx_stride, const unsigned *prev_idx,
+                                        int switch_mode, void *hip_stream);
+/* 0: k_conv_p1_layout served the handle's most recent layout launch (also: none yet), 1: k_conv_p1_layout_irs */
+int  ohs_batch_last_layout_scheduled(const ohs_batch *b, int *scheduled);
 /* The same as ohs_batch_process, but `hip_stream` is NOT made to wait for the last time chunk's convolution (it runs on an
  * internal stream underneath the EQ): d_out is complete on `hip_stream` only after ohs_batch_join (a
  * stream-side wait, asynchronous) or ohs_batch_sync.  Back-to-back deferred calls with the same buffers

@@ -101,6 +101,8 @@ PROTOTYPES = {
     "ohs_sofa_speaker_irs": (C.c_int, [vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                        C.POINTER(fp), C.c_size_t, C.POINTER(C.c_size_t)]),
     "ohs_sofa_layout_irs": (C.c_int, [vp, C.c_size_t, fp, fp, C.c_float, C.c_float, fp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ohs_sofa_layout_yaw_irs": (C.c_int, [vp, C.c_size_t, fp, fp, C.c_float, C.c_float, C.c_size_t, fp, fp, C.c_size_t,
+                                          C.POINTER(C.c_size_t)]),
     "ohs_engine_set_speakers": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint)]),
     "ohs_batch_set_speakers": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint)]),
     "ohs_node_batch_set_speakers": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint)]),
@@ -142,6 +144,11 @@ PROTOTYPES = {
     "ohs_batch_set_layout_irs": (C.c_int, [vp, C.c_size_t, fp, C.c_size_t]),
     "ohs_batch_process_layout": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp]),
     "ohs_batch_last_layout_launch": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ohs_batch_set_layout_schedule_irs": (C.c_int, [vp, C.c_size_t, C.c_size_t, fp, C.c_size_t]),
+    "ohs_batch_process_layout_scheduled": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                      C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32),
+                                                      C.c_int, vp]),
+    "ohs_batch_last_layout_scheduled": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "ohs_batch_join": (C.c_int, [vp, vp]),
     "ohs_batch_sync": (C.c_int, [vp, vp]),
     "ohs_batch_process_host": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),

@@ -32,6 +32,7 @@ class BatchProcessor:
         self.device = int(device)
         self._L = library
         self._layout_k = 0      # channels of the layout set_layout_irs loaded (process_layout's shape check)
+        self._table_k = 0       # channels of the table set_layout_table loaded (process_layout_scheduled's shape check)
         h = C.c_void_p()
         self._check(self._lib.ohs_batch_create(self.device, self.n_streams, self.num_bands, C.byref(h)))
         self._h = h
@@ -382,6 +383,94 @@ class BatchProcessor:
             hip_stream = torch.cuda.current_stream(x.device).cuda_stream
         self.process_layout_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, ch * frames, frames, 2 * frames, frames,
                                 hip_stream)
+        return out
+
+    # -- head-tracked speaker layouts: a table of layouts per stream and segment ------------------
+    def set_layout_table(self, irs) -> None:
+        """The table of process_layout_scheduled: irs [n_sets][K][2][len], set j, channel c -> left ear irs[j][c][0], right ear
+        irs[j][c][1]; K <= 16, len <= 512, n_sets <= 65536.  Replaces any earlier table and zeroes the layout overlap; an empty array
+        frees it (ohs_batch_set_layout_schedule_irs)."""
+        a = np.ascontiguousarray(irs, dtype=np.float32)
+        if a.size == 0:
+            self._check(self._lib.ohs_batch_set_layout_schedule_irs(self._h, 0, 0, None, 0))
+            self._table_k = 0
+            return
+        if a.ndim != 4 or a.shape[2] != 2:
+            raise ValueError(f"expected irs [n_sets][n_channels][2][len], got {a.shape}")
+        self._check(self._lib.ohs_batch_set_layout_schedule_irs(self._h, a.shape[0], a.shape[1], a.ctypes.data_as(fp), a.shape[3]))
+        self._table_k = int(a.shape[1])
+
+    def set_layout_table_yaws(self, sofa, layout, yaws, el=None, radius_m: float = 1.0, fs: float = 0.0) -> np.ndarray:
+        """One layout per head yaw (degrees, positive to the right, like the azimuth): `layout` a preset such as LAYOUT_5_1 or the
+        azimuths az[c] (then el[c], None: all 0); -> the array [n_yaws][K][2][len] it loaded (ohs_sofa_layout_yaw_irs)."""
+        if el is None and len(layout) and isinstance(layout[0], (tuple, list)):
+            layout, el = [r[1] for r in layout], [r[2] for r in layout]
+        if el is None:
+            el = [0.0] * len(layout)
+        from .sofa import layout_yaw_irs
+        out = layout_yaw_irs(sofa, layout, el, yaws, radius_m, fs)
+        if out.shape[3] > BLOCK_SIZE:
+            raise ValueError(f"a response of {out.shape[3]} taps: a layout holds one-partition responses (<= {BLOCK_SIZE} taps)")
+        self.set_layout_table(out)
+        return out
+
+    def last_layout_scheduled(self) -> bool:
+        """whether k_conv_p1_layout_irs served the most recent layout launch (ohs_batch_last_layout_scheduled)"""
+        v = C.c_int()
+        self._check(self._lib.ohs_batch_last_layout_scheduled(self._h, C.byref(v)))
+        return bool(v.value)
+
+    def process_layout_scheduled_ptr(self, d_in: int, d_out: int, n_blocks: int, in_stream_stride: int, in_channel_stride: int,
+                                     out_stream_stride: int, out_channel_stride: int, seg_blocks: int, idx, prev=None,
+                                     crossfade: bool = True, hip_stream: int = 0) -> None:
+        """ohs_batch_process_layout_scheduled: process_layout_ptr with a set of the table per stream and segment of seg_blocks
+        blocks.  idx: [n_segs] for all streams or [n_streams][n_segs]; prev: the set in front of the call's first block -- a scalar
+        for a 1-D idx, [n_streams] for rows per stream --, or None: the call's start is no boundary (read when crossfade only)."""
+        n_segs = -(-int(n_blocks) // int(seg_blocks)) if seg_blocks else 0
+        if idx is None:
+            raise ValueError("idx is required")
+        a = np.ascontiguousarray(idx, dtype=np.uint32)
+        if a.ndim == 1:
+            if a.size < n_segs:
+                raise ValueError(f"idx needs {n_segs} entries")
+            stride = 0
+        elif a.ndim == 2 and a.shape[0] == self.n_streams and a.shape[1] >= n_segs:
+            stride = int(a.shape[1])
+        else:
+            raise ValueError(f"idx: expected [{self.n_streams}][>= {n_segs}] or [>= {n_segs}], got {a.shape}")
+        pp = None
+        if prev is not None:
+            pv = np.ascontiguousarray(prev, dtype=np.uint32).reshape(-1)
+            if pv.size != (self.n_streams if stride else 1):
+                raise ValueError(f"prev: expected {self.n_streams if stride else 1} entries, got {pv.size}")
+            pp = pv.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._check(self._lib.ohs_batch_process_layout_scheduled(
+            self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(in_stream_stride), int(in_channel_stride),
+            int(out_stream_stride), int(out_channel_stride), int(seg_blocks), a.ctypes.data_as(C.POINTER(C.c_uint32)), stride, pp,
+            1 if crossfade else 0, C.c_void_p(hip_stream) if hip_stream else None))
+
+    def process_layout_scheduled(self, x, idx, seg_blocks: int, prev=None, crossfade: bool = True, out=None,
+                                 hip_stream: int | None = None):
+        """process_layout() with a set of the table per stream and segment of seg_blocks * 512 frames; crossfade: fade from the old
+        set to the new one over the first block of every segment that changes the set (False: the old set's tail rings out).
+        x, out as in process_layout(); K is the table's channel count."""
+        import torch
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, channels, frames]")
+        S, ch, frames = x.shape
+        K = self._table_k
+        if S != self.n_streams or frames % BLOCK_SIZE or ch < K:
+            raise ValueError(f"expected [{self.n_streams}, >= {K}, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
+        if x.device.index != self.device:
+            raise ValueError("tensor is on a different device than the BatchProcessor")
+        if out is None:
+            out = torch.empty((S, 2, frames), dtype=x.dtype, device=x.device)
+        elif tuple(out.shape) != (S, 2, frames) or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+            raise ValueError("out must be a contiguous [streams, 2, frames] tensor on x's device")
+        if hip_stream is None:
+            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+        self.process_layout_scheduled_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, ch * frames, frames, 2 * frames,
+                                          frames, seg_blocks, idx, prev, crossfade, hip_stream)
         return out
 
     def last_conv_ir_crossfaded(self) -> bool:

@@ -724,6 +724,46 @@ int ohs_batch_last_conv_ir_scheduled(const ohs_batch *b, int *scheduled)
     return OHS_OK;
 }
 
+// Rows of set indices (and prev_idx behind them) into the next staging slot (ohs_batch_process_scheduled's slots) and one copy to the
+// device on st: n_rows_src rows of n_segs entries, read idx_stride apart and packed n_segs apart, then n_prev entries of prev.  The
+// slot is free once the call that used it last has completed; *out is set as soon as the slot is taken, so that the caller can
+// close it with stage_rows_done whatever happens afterwards.
+static int stage_rows(ohs_batch *b, const unsigned *idx, size_t idx_stride, size_t n_rows_src, size_t n_segs, const unsigned *prev,
+                      size_t n_prev, hipStream_t st, ohs_batch::SchedSlot **out)
+{
+    const size_t n_rows = n_rows_src * n_segs, n_tab = n_rows + n_prev;
+    ohs_batch::SchedSlot &slot = b->sched_slot[b->sched_next];
+    b->sched_next = (b->sched_next + 1) % ohs_batch::kSchedSlots;
+    if (slot.in_use) HIP_TRY(hipEventSynchronize(slot.done));
+    slot.in_use = false;
+    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    *out = &slot;
+    if (2 * slot.cap < n_tab) {
+        if (slot.h) hipHostFree(slot.h);
+        if (slot.d) {
+            DeviceWideSection dws;
+            hipFree(slot.d);
+        }
+        slot.h = nullptr; slot.d = nullptr; slot.cap = 0;
+        const size_t cap = std::max<size_t>(1024, n_tab / 2 + n_tab / 4 + 1);
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&slot.h), 2 * cap * sizeof(unsigned), hipHostMallocDefault));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&slot.d), 2 * cap * sizeof(unsigned)));
+        slot.cap = cap;
+    }
+    for (size_t r = 0; r < n_rows_src; ++r) std::memcpy(slot.h + r * n_segs, idx + r * idx_stride, n_segs * sizeof(unsigned));
+    if (n_prev) std::memcpy(slot.h + n_rows, prev, n_prev * sizeof(unsigned));
+    HIP_TRY(hipMemcpyAsync(slot.d, slot.h, n_tab * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    return OHS_OK;
+}
+
+// behind the launches that read the slot
+static void stage_rows_done(ohs_batch::SchedSlot *slot, hipStream_t st)
+{
+    if (!slot) return;
+    if (hipEventRecord(slot->done, st) == hipSuccess) slot->in_use = true;
+    else hipStreamSynchronize(st);
+}
+
 // ohs_batch_process_ir_scheduled (crossfade false) and ohs_batch_process_ir_crossfaded (crossfade true; switch_mode RING_OUT, prev_idx
 // optional) share the validation pass, the staging slot and the state rules
 static int batch_process_irs(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
@@ -803,38 +843,21 @@ static int batch_process_irs(ohs_batch *b, const float *d_in, float *d_out, size
     // the rows' staging slot (ohs_batch_process_scheduled's): rows packed n_segs apart; equal rows travel as one
     // (the crossfaded call's prev_idx travels behind the rows)
     const size_t n_rows = (rows_differ ? S : 1) * n_segs, n_prev = (crossfade && prev_idx) ? (prev_differ ? S : 1) : 0;
-    const size_t n_tab = n_rows + n_prev;
-    ohs_batch::SchedSlot &slot = b->sched_slot[b->sched_next];
-    b->sched_next = (b->sched_next + 1) % ohs_batch::kSchedSlots;
-    if (slot.in_use) HIP_TRY(hipEventSynchronize(slot.done));
-    slot.in_use = false;
-    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
-    if (2 * slot.cap < n_tab) {
-        if (slot.h) hipHostFree(slot.h);
-        if (slot.d) {
-            DeviceWideSection dws;
-            hipFree(slot.d);
-        }
-        slot.h = nullptr; slot.d = nullptr; slot.cap = 0;
-        const size_t cap = std::max<size_t>(1024, n_tab / 2 + n_tab / 4 + 1);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&slot.h), 2 * cap * sizeof(unsigned), hipHostMallocDefault));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&slot.d), 2 * cap * sizeof(unsigned)));
-        slot.cap = cap;
+    ohs_batch::SchedSlot *slot = nullptr;
+    {
+        const int rcs = stage_rows(b, ir_idx, idx_stride, rows_differ ? S : 1, n_segs, prev_idx, n_prev, st, &slot);
+        if (rcs) return rcs;
     }
-    for (size_t r = 0; r < (rows_differ ? S : 1); ++r) std::memcpy(slot.h + r * n_segs, ir_idx + r * idx_stride, n_segs * sizeof(unsigned));
-    if (n_prev) std::memcpy(slot.h + n_rows, prev_idx, n_prev * sizeof(unsigned));
-    HIP_TRY(hipMemcpyAsync(slot.d, slot.h, n_tab * sizeof(unsigned), hipMemcpyHostToDevice, st));
     ConvIrs ci;
-    ci.tab = slot.d; ci.seg_blocks = (int)seg_blocks; ci.stream_stride = rows_differ ? (int)n_segs : 0; ci.call_blocks = (int)n_blocks;
+    ci.tab = slot->d; ci.seg_blocks = (int)seg_blocks; ci.stream_stride = rows_differ ? (int)n_segs : 0; ci.call_blocks = (int)n_blocks;
     ci.cut = cut;
     ci.per_stream_state = !shared;      // (a shared row is adopted below: the handle's spectra rebuild the overlaps when asked)
     if (crossfade) {
         ci.xfade = true; ci.faded_end = faded_end;
-        if (n_prev) { ci.prev = slot.d + n_rows; ci.prev_stride = prev_differ ? 1 : 0; }
+        if (n_prev) { ci.prev = slot->d + n_rows; ci.prev_stride = prev_differ ? 1 : 0; }
     }
     const int rc = batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false, nullptr, &ci);
-    if (hipEventRecord(slot.done, st) == hipSuccess) slot.in_use = true;
-    else hipStreamSynchronize(st);
+    stage_rows_done(slot, st);
     if (rc) return rc;
     // one row for all streams: the handle's responses ARE the last segment's now (what ohs_batch_process_scheduled does with its table)
     if (shared) return conv_adopt_schedule_set(c, ir_idx[n_segs - 1], st);
@@ -923,6 +946,114 @@ int ohs_batch_process_layout(ohs_batch *b, const float *d_in, float *d_out, size
         return rc;
     };
     const int rc = body();
+    if (rc == OHS_OK || rc == OHS_ERR_INVALID_ARG) return rc;
+    const std::string why = g_err;
+    b->failed = true;
+    b->fail_msg = why;
+    return fail(rc, why);
+}
+
+// ---- head-tracked speaker layouts: a table of layouts walked per stream and segment ----------------------------------
+int ohs_batch_set_layout_schedule_irs(ohs_batch *b, size_t n_sets, size_t n_channels, const float *irs, size_t len)
+{
+    if (!b) return fail(OHS_ERR_INVALID_ARG, "batch is NULL");
+    if (n_sets > 0) {
+        if (!irs) return fail(OHS_ERR_INVALID_ARG, "irs is NULL");
+        if (n_sets > 65536) return fail(OHS_ERR_INVALID_ARG, "n_sets must be at most 65536");
+        if (n_channels == 0 || n_channels > 16) return fail(OHS_ERR_INVALID_ARG, "n_channels must be 1 .. 16");
+        if (len == 0 || len > (size_t)BS) return fail(OHS_ERR_INVALID_ARG, "len must be 1 .. 512 (one partition)");
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    DeviceWideSection dws;
+    HIP_TRY(hipDeviceSynchronize());
+    return conv_set_layout_schedule_irs(b->conv, b->ctx, n_sets, n_channels, irs, len, b->st);
+}
+
+int ohs_batch_last_layout_scheduled(const ohs_batch *b, int *scheduled)
+{
+    if (!b || !scheduled) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    *scheduled = b->conv.last_lay_scheduled ? 1 : 0;
+    return OHS_OK;
+}
+
+int ohs_batch_process_layout_scheduled(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
+                                       size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride,
+                                       size_t seg_blocks, const unsigned *set_idx, size_t idx_stride, const unsigned *prev_idx,
+                                       int switch_mode, void *hip_stream)
+{
+    if (!b || !d_in || !d_out || !set_idx) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    if (seg_blocks == 0) return fail(OHS_ERR_INVALID_ARG, "seg_blocks is 0");
+    if (switch_mode != OHS_LAYOUT_SWITCH_RING_OUT && switch_mode != OHS_LAYOUT_SWITCH_CROSSFADE)
+        return fail(OHS_ERR_INVALID_ARG, "switch_mode must be OHS_LAYOUT_SWITCH_RING_OUT or OHS_LAYOUT_SWITCH_CROSSFADE");
+    ConvState &c = b->conv;
+    if (c.lays_n == 0 || !c.d_lays_cd) return fail(OHS_ERR_INVALID_ARG, "no table uploaded (ohs_batch_set_layout_schedule_irs)");
+    if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
+    if (b->failed)
+        return fail(OHS_ERR_HIP, "this batch failed in the middle of an earlier call (" + b->fail_msg +
+                                     "): its per-stream state is half-advanced; ohs_batch_reset starts it afresh");
+    if (n_blocks == 0) return OHS_OK;
+    seg_blocks = std::min(seg_blocks, n_blocks);
+    const size_t frames = n_blocks * BS, S = c.S, K = c.lays_K, n_segs = (n_blocks + seg_blocks - 1) / seg_blocks;
+    if (idx_stride != 0 && idx_stride < n_segs)
+        return fail(OHS_ERR_INVALID_ARG, "idx_stride is 0 (one row for all streams) or >= the number of segments");
+    if (S * n_segs > (size_t)0x7fffffff) return fail(OHS_ERR_INVALID_ARG, "schedule too large");
+    const bool fade = switch_mode == OHS_LAYOUT_SWITCH_CROSSFADE, shared = idx_stride == 0;
+    if (!fade) prev_idx = nullptr;      // (read under CROSSFADE only)
+    // one pass over the rows: the range check, whether anything varies along a row, whether the rows differ; prev_idx beside them
+    const size_t rows = shared ? 1 : S;
+    bool vary = false, rows_differ = false, prev_differ = false, prev_boundary = false;
+    for (size_t r = 0; r < rows; ++r) {
+        const unsigned *row = set_idx + r * idx_stride;
+        for (size_t k = 0; k < n_segs; ++k) {
+            if (row[k] >= c.lays_n) return fail(OHS_ERR_INVALID_ARG, "set_idx entry out of range");
+            vary = vary || row[k] != row[0];
+            rows_differ = rows_differ || row[k] != set_idx[k];
+        }
+        if (prev_idx) {
+            if (prev_idx[r] >= c.lays_n) return fail(OHS_ERR_INVALID_ARG, "prev_idx entry out of range");
+            prev_differ = prev_differ || prev_idx[r] != prev_idx[0];
+            prev_boundary = prev_boundary || prev_idx[r] != row[0];
+        }
+    }
+    if (!layout_strides_ok(S, in_stream_stride, K, in_channel_stride, frames) ||
+        !layout_strides_ok(S, out_stream_stride, 2, out_channel_stride, frames))
+        return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
+    {   // out of place only: the two regions, first to last frame touched, must not meet
+        const float *in_end = d_in + (S - 1) * in_stream_stride + (K - 1) * in_channel_stride + frames;
+        const float *out_end = d_out + (S - 1) * out_stream_stride + out_channel_stride + frames;
+        if (!(in_end <= d_out || out_end <= d_in))
+            return fail(OHS_ERR_INVALID_ARG, "input and output regions overlap (the layout call is out of place only)");
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    // one set throughout, for all streams, and no boundary at the call's start: k_conv_p1_layout on that set's slice of the table
+    const bool plain = shared && !vary && !prev_boundary;
+    ohs_batch::SchedSlot *slot = nullptr;
+    auto body = [&]() -> int {
+        if (b->join_pending) {      // (a deferred call's last convolutions: the EQ state and d_out may be theirs)
+            HIP_TRY(hipStreamWaitEvent(st, b->chunk_done[(size_t)b->chunk_done_n - 1], 0));
+            b->join_pending = false;
+        }
+        ConvLayoutRows lr;
+        if (!plain) {
+            // the rows' staging slot (the IR-scheduled calls'): rows packed n_segs apart, equal rows travel as one; prev_idx behind them
+            const size_t n_rows = (rows_differ ? S : 1) * n_segs, n_prev = prev_idx ? (prev_differ ? S : 1) : 0;
+            const int rcs = stage_rows(b, set_idx, idx_stride, rows_differ ? S : 1, n_segs, prev_idx, n_prev, st, &slot);
+            if (rcs) return rcs;
+            lr.tab = slot->d; lr.seg_blocks = (int)seg_blocks; lr.stream_stride = rows_differ ? (int)n_segs : 0;
+            lr.fade = fade;
+            if (n_prev) { lr.prev = slot->d + n_rows; lr.prev_stride = prev_differ ? 1 : 0; }
+        }
+        int rc = conv_launch_layout_scheduled(c, b->ctx, d_in, (long long)in_stream_stride, (long long)in_channel_stride, d_out,
+                                              (long long)out_stream_stride, (long long)out_channel_stride, (int)n_blocks, b->gain, st,
+                                              plain ? nullptr : &lr, set_idx[0]);
+        if (rc) return rc;
+        if (b->eq_enable && eq_any_enabled(b->eq))      // EQ(gain * conv(x)): the two ear channels, in place, behind the whole call
+            rc = eq_launch(b->eq, d_out, d_out, (long long)out_stream_stride, (long long)out_channel_stride, (long long)frames, st);
+        return rc;
+    };
+    const int rc = body();
+    stage_rows_done(slot, st);
     if (rc == OHS_OK || rc == OHS_ERR_INVALID_ARG) return rc;
     const std::string why = g_err;
     b->failed = true;

@@ -30,7 +30,7 @@ void conv_free(ConvState &c)
                                                  c.d_W1, c.d_merged, c.d_merged_alt, c.d_last_in, c.d_irt, c.d_cd_os, c.d_irl,
                                                  c.d_xhist, c.d_xhist_alt, c.d_lb_ring, c.d_lb_cd, c.d_lb_ab, c.d_lb_cd_alt,
                                                  c.d_xb_cd, c.d_xb_ab, c.d_ptail, c.d_ptail_alt, c.d_irs_cd, c.d_irs_H, c.d_irs_t,
-                                                 c.d_lay_cd, c.d_lay_ov, c.d_lay_ov_alt})
+                                                 c.d_lay_cd, c.d_lay_ov, c.d_lay_ov_alt, c.d_lays_cd})
         if (d) hipFree(d);
 }
 
@@ -693,6 +693,67 @@ int conv_set_schedule_irs(ConvState &c, DeviceCtx *ctx, size_t n_sets, const flo
     return OHS_OK;
 }
 
+// units "sets" of four responses each -> dst[units][1024] float4.  rows(u, r) is response r (0 .. 3) of unit u, `len` taps, or nullptr
+// for an all-zero one.  Built in slices of 1 024 units, host staging and device scratch alike, so that neither grows with the table
+// (and k_irs_tables' grid stays small).
+template <class Rows>
+static int layout_build_tables(DeviceCtx *ctx, size_t units, size_t len, Rows rows, float4 *dst, hipStream_t st)
+{
+    constexpr size_t kSlice = 1024;
+    const size_t slice = std::min(units, kSlice);
+    std::vector<float> padded;  // [slice][4][512]
+    try {
+        padded.resize(slice * 4 * (size_t)BS);
+    } catch (const std::bad_alloc &) {
+        return fail(OHS_ERR_HIP, "out of host memory for the table's staging");
+    }
+    float *d_t = nullptr;       // [slice][4][512] scratch
+    float2 *d_H = nullptr;      // [slice][4][1024] scratch
+    float2 *d_cd = nullptr;     // [slice][2][1024] scratch
+    auto body = [&]() -> int {
+        HIP_TRY(hipMalloc(&d_t, slice * 4 * (size_t)BS * sizeof(float)));
+        HIP_TRY(hipMalloc(&d_H, slice * 4 * (size_t)NF * sizeof(float2)));
+        HIP_TRY(hipMalloc(&d_cd, slice * 2 * (size_t)NF * sizeof(float2)));
+        for (size_t u0 = 0; u0 < units; u0 += slice) {
+            const size_t n = std::min(slice, units - u0);
+            std::fill(padded.begin(), padded.end(), 0.0f);
+            for (size_t u = 0; u < n; ++u)
+                for (size_t r = 0; r < 4; ++r)
+                    if (const float *src = rows(u0 + u, r)) std::memcpy(&padded[(u * 4 + r) * BS], src, len * sizeof(float));
+            HIP_TRY(hipMemcpyAsync(d_t, padded.data(), n * 4 * (size_t)BS * sizeof(float), hipMemcpyHostToDevice, st));
+            HIP_TRY(launch_ir_spectrum(d_t, (int)(n * 4 * (size_t)BS), (int)(n * 4), d_H, ctx->d_tw, st));
+            for (size_t p = 0; p < n; ++p) {
+                const float2 *h = d_H + p * 4 * (size_t)NF;
+                HIP_TRY(launch_build_cd(h, h + NF, h + 2 * NF, h + 3 * NF, d_cd + p * 2 * (size_t)NF, st));
+            }
+            HIP_TRY(launch_irs_tables(d_cd, (int)n, dst + u0 * (size_t)NF, st));
+            HIP_TRY(hipStreamSynchronize(st));      // (staging and scratch are reused by the next slice)
+        }
+        return OHS_OK;
+    };
+    const int rc = body();
+    for (void *d : std::initializer_list<void *>{d_t, d_H, d_cd})
+        if (d) hipFree(d);
+    return rc;
+}
+
+// the layout overlap, shared by the single layout and the table of layouts: allocated while either exists, zeroed by every upload
+static int layout_overlap_zeroed(ConvState &c, hipStream_t st)
+{
+    if (!c.d_lay_ov) HIP_TRY(hipMalloc(&c.d_lay_ov, c.S * 8 * 64 * sizeof(float2)));
+    if (!c.d_lay_ov_alt) HIP_TRY(hipMalloc(&c.d_lay_ov_alt, c.S * 8 * 64 * sizeof(float2)));
+    HIP_TRY(hipMemsetAsync(c.d_lay_ov, 0, c.S * 8 * 64 * sizeof(float2), st));
+    return OHS_OK;
+}
+
+static void layout_overlap_release_if_unused(ConvState &c)
+{
+    if (c.d_lay_cd || c.d_lays_cd) return;
+    for (void *d : std::initializer_list<void *>{c.d_lay_ov, c.d_lay_ov_alt})
+        if (d) hipFree(d);
+    c.d_lay_ov = nullptr; c.d_lay_ov_alt = nullptr;
+}
+
 // The speaker layout of ohs_batch_process_layout.  irs[c][e] is row 2 c + e, so the four rows of pair p -- channel 2 p to both ears,
 // channel 2 p + 1 to both ears -- are the four paths Lsl, Lsr, Rsl, Rsr of a "set": the spectra by k_ir_spectrum, (C, D) by k_build_cd,
 // the block loop's layout by k_irs_tables, exactly as conv_set_schedule_irs builds a set (K = 2: the bits of a plain call on a handle
@@ -700,44 +761,73 @@ int conv_set_schedule_irs(ConvState &c, DeviceCtx *ctx, size_t n_sets, const flo
 int conv_set_layout_irs(ConvState &c, DeviceCtx *ctx, size_t n_channels, const float *irs, size_t len, hipStream_t st)
 {
     DeviceWideSection dws;      // (frees below)
-    for (void *d : std::initializer_list<void *>{c.d_lay_cd, c.d_lay_ov, c.d_lay_ov_alt})
-        if (d) hipFree(d);
-    c.d_lay_cd = nullptr; c.d_lay_ov = nullptr; c.d_lay_ov_alt = nullptr; c.lay_K = 0; c.lay_len = 0;
-    if (n_channels == 0) return OHS_OK;
-    const size_t P = (n_channels + 1) / 2;
-    std::vector<float> padded(P * 4 * (size_t)BS, 0.0f);
-    for (size_t r = 0; r < n_channels * 2; ++r) std::memcpy(&padded[r * BS], irs + r * len, len * sizeof(float));
-    float *d_t = nullptr;       // [P][4][512] scratch
-    float2 *d_H = nullptr;      // [P][4][1024] scratch
-    float2 *d_cd = nullptr;     // [P][2][1024] scratch
-    auto body = [&]() -> int {
-        HIP_TRY(hipMalloc(&d_t, padded.size() * sizeof(float)));
-        HIP_TRY(hipMalloc(&d_H, P * 4 * (size_t)NF * sizeof(float2)));
-        HIP_TRY(hipMalloc(&d_cd, P * 2 * (size_t)NF * sizeof(float2)));
-        HIP_TRY(hipMalloc(&c.d_lay_cd, P * (size_t)NF * sizeof(float4)));
-        HIP_TRY(hipMalloc(&c.d_lay_ov, c.S * 8 * 64 * sizeof(float2)));
-        HIP_TRY(hipMalloc(&c.d_lay_ov_alt, c.S * 8 * 64 * sizeof(float2)));
-        HIP_TRY(hipMemsetAsync(c.d_lay_ov, 0, c.S * 8 * 64 * sizeof(float2), st));
-        HIP_TRY(hipMemcpyAsync(d_t, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice, st));
-        HIP_TRY(launch_ir_spectrum(d_t, (int)padded.size(), (int)(P * 4), d_H, ctx->d_tw, st));
-        for (size_t p = 0; p < P; ++p) {
-            const float2 *h = d_H + p * 4 * (size_t)NF;
-            HIP_TRY(launch_build_cd(h, h + NF, h + 2 * NF, h + 3 * NF, d_cd + p * 2 * (size_t)NF, st));
+    if (c.d_lay_cd) hipFree(c.d_lay_cd);
+    c.d_lay_cd = nullptr; c.lay_K = 0; c.lay_len = 0;
+    if (n_channels == 0) {
+        layout_overlap_release_if_unused(c);
+        if (c.d_lay_ov) {       // (a table of layouts keeps the slabs: zeroed, as behind every upload)
+            HIP_TRY(hipMemsetAsync(c.d_lay_ov, 0, c.S * 8 * 64 * sizeof(float2), st));
+            HIP_TRY(hipStreamSynchronize(st));
         }
-        HIP_TRY(launch_irs_tables(d_cd, (int)P, c.d_lay_cd, st));
+        return OHS_OK;
+    }
+    const size_t P = (n_channels + 1) / 2;
+    // (unit p = pair p: rows irs[2 p][0], irs[2 p][1], irs[2 p + 1][0], irs[2 p + 1][1]; an odd last channel has a zero partner)
+    auto rows = [&](size_t p, size_t r) -> const float * { return 4 * p + r < 2 * n_channels ? irs + (4 * p + r) * len : nullptr; };
+    auto body = [&]() -> int {
+        HIP_TRY(hipMalloc(&c.d_lay_cd, P * (size_t)NF * sizeof(float4)));
+        const int rco = layout_overlap_zeroed(c, st);
+        if (rco) return rco;
+        const int rct = layout_build_tables(ctx, P, len, rows, c.d_lay_cd, st);
+        if (rct) return rct;
         HIP_TRY(hipStreamSynchronize(st));
         return OHS_OK;
     };
     const int rc = body();
-    for (void *d : std::initializer_list<void *>{d_t, d_H, d_cd})
-        if (d) hipFree(d);
     if (rc) {
-        for (void *d : std::initializer_list<void *>{c.d_lay_cd, c.d_lay_ov, c.d_lay_ov_alt})
-            if (d) hipFree(d);
-        c.d_lay_cd = nullptr; c.d_lay_ov = nullptr; c.d_lay_ov_alt = nullptr;
+        if (c.d_lay_cd) hipFree(c.d_lay_cd);
+        c.d_lay_cd = nullptr;
+        layout_overlap_release_if_unused(c);
         return rc;
     }
     c.lay_K = n_channels; c.lay_len = len;
+    return OHS_OK;
+}
+
+// The table of layouts of ohs_batch_process_layout_scheduled: set j, pair p is "set" j * P + p of the same chain, so a block on set j
+// has the bits of ohs_batch_process_layout on a handle that loaded irs[j].
+int conv_set_layout_schedule_irs(ConvState &c, DeviceCtx *ctx, size_t n_sets, size_t n_channels, const float *irs, size_t len,
+                                 hipStream_t st)
+{
+    DeviceWideSection dws;      // (frees below)
+    if (c.d_lays_cd) hipFree(c.d_lays_cd);
+    c.d_lays_cd = nullptr; c.lays_n = 0; c.lays_K = 0; c.lays_len = 0;
+    if (n_sets == 0) {
+        layout_overlap_release_if_unused(c);
+        return OHS_OK;
+    }
+    const size_t P = (n_channels + 1) / 2, units = n_sets * P;
+    auto rows = [&](size_t u, size_t r) -> const float * {      // (unit u = set u / P, pair u % P)
+        const size_t j = u / P, q = 4 * (u % P) + r;
+        return q < 2 * n_channels ? irs + (j * 2 * n_channels + q) * len : nullptr;
+    };
+    auto body = [&]() -> int {
+        HIP_TRY(hipMalloc(&c.d_lays_cd, units * (size_t)NF * sizeof(float4)));
+        const int rco = layout_overlap_zeroed(c, st);
+        if (rco) return rco;
+        const int rct = layout_build_tables(ctx, units, len, rows, c.d_lays_cd, st);
+        if (rct) return rct;
+        HIP_TRY(hipStreamSynchronize(st));
+        return OHS_OK;
+    };
+    const int rc = body();
+    if (rc) {
+        if (c.d_lays_cd) hipFree(c.d_lays_cd);
+        c.d_lays_cd = nullptr;
+        layout_overlap_release_if_unused(c);
+        return rc;
+    }
+    c.lays_n = n_sets; c.lays_K = n_channels; c.lays_len = len;
     return OHS_OK;
 }
 
@@ -766,7 +856,47 @@ int conv_launch_layout(ConvState &c, DeviceCtx *ctx, const float *in, long long 
     const hipError_t e = launch_conv_p1_layout(a, l, st);
     if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_layout launch: ") + hipGetErrorString(e));
     std::swap(c.d_lay_ov, c.d_lay_ov_alt);
-    c.last_lay_pairs = l.n_pairs; c.last_lay_ranges = K;
+    c.last_lay_pairs = l.n_pairs; c.last_lay_ranges = K; c.last_lay_scheduled = false;
+    return OHS_OK;
+}
+
+// The scheduled layout call: conv_launch_layout's plan -- the same chunks per stream, the same overlap slabs --, on the table of layouts
+int conv_launch_layout_scheduled(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
+                                 float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st,
+                                 const ConvLayoutRows *rows, size_t one_set)
+{
+    if (!c.d_lays_cd || c.lays_n == 0) return fail(OHS_ERR_INVALID_ARG, "no table uploaded (ohs_batch_set_layout_schedule_irs)");
+    if (!rows && one_set >= c.lays_n) return fail(OHS_ERR_INVALID_ARG, "set index out of range");
+    if (n_blocks <= 0) return OHS_OK;
+    const long long want = conv_p1_chunks(ctx, c.S, n_blocks, 0, 8, conv_layout_waves_per_cu());
+    int K = 16;
+    while (K > want || K > n_blocks) K >>= 1;
+    ConvP1Args a{};
+    a.in = in; a.out = out;
+    a.in_stream_stride = in_ss; a.in_ch_stride = in_cs;
+    a.out_stream_stride = out_ss; a.out_ch_stride = out_cs;
+    a.n_blocks = n_blocks; a.n_streams = (int)c.S; a.chunks = K;
+    a.tw = ctx->d_tw; a.gain = gain; a.fp_mode = c.fp_mode;
+    a.xcd_lo = 0; a.xcd_n = 8;
+    for (int g = 0; g < 4; ++g) a.weights[g] = 1;
+    a.merged_in = c.d_lay_ov; a.merged_out = c.d_lay_ov_alt;
+    a.gain_seg = 1;
+    const int P = (int)((c.lays_K + 1) / 2);
+    hipError_t e;
+    if (!rows) {
+        ConvLayoutArgs l;
+        l.cd = c.d_lays_cd + one_set * (size_t)P * NF; l.n_channels = (int)c.lays_K; l.n_pairs = P;
+        e = launch_conv_p1_layout(a, l, st);
+    } else {
+        ConvLayoutIrArgs l;
+        l.cd = c.d_lays_cd; l.n_channels = (int)c.lays_K; l.n_pairs = P;
+        l.tab = rows->tab; l.stream = rows->stream_stride; l.seg = rows->seg_blocks;
+        l.prev = rows->fade ? rows->prev : nullptr; l.prev_stream = rows->prev_stride; l.fade = rows->fade ? 1 : 0;
+        e = launch_conv_p1_layout_irs(a, l, st);
+    }
+    if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_layout_irs launch: ") + hipGetErrorString(e));
+    std::swap(c.d_lay_ov, c.d_lay_ov_alt);
+    c.last_lay_pairs = P; c.last_lay_ranges = K; c.last_lay_scheduled = rows != nullptr;
     return OHS_OK;
 }
 

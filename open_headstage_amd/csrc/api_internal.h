@@ -214,6 +214,12 @@ struct ConvState {
     float4 *d_lay_cd = nullptr;     // [ceil(lay_K / 2)][1024]
     float2 *d_lay_ov = nullptr, *d_lay_ov_alt = nullptr;    // [S][8][64]
     int last_lay_pairs = 0, last_lay_ranges = 0;    // the most recent layout launch (ohs_batch_last_layout_launch)
+    // The table of layouts of ohs_batch_process_layout_scheduled (ohs_batch_set_layout_schedule_irs): lays_n sets of lays_K channels,
+    // the (C, D) table of every (set, pair) that k_conv_p1_layout_irs reads.  Independent of the single layout above -- either may
+    // exist without the other --, but both calls continue ONE overlap: d_lay_ov / d_lay_ov_alt live while either exists.
+    size_t lays_n = 0, lays_K = 0, lays_len = 0;
+    float4 *d_lays_cd = nullptr;    // [lays_n][ceil(lays_K / 2)][1024]
+    bool last_lay_scheduled = false;    // k_conv_p1_layout_irs served the most recent layout launch (ohs_batch_last_layout_scheduled)
     // ohs_*_set_speakers: what it last loaded into each path (a set_ir from anywhere else forgets it), so that a
     // change of the speaker angles re-loads only the paths whose impulse response really changed
     std::vector<float> spk_ir[4];
@@ -298,6 +304,25 @@ int conv_set_layout_irs(ConvState &c, DeviceCtx *ctx, size_t n_channels, const f
 // n_blocks of every stream's lay_K channels -> two ears, times gain; out of place (the caller checks), asynchronous on st
 int conv_launch_layout(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
                        float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st);
+// the table of layouts (host array irs[n_sets][n_channels][2][len], 1 <= len <= 512; n_sets == 0 frees it); zeroes the layout overlap;
+// the caller has drained the device
+int conv_set_layout_schedule_irs(ConvState &c, DeviceCtx *ctx, size_t n_sets, size_t n_channels, const float *irs, size_t len,
+                                 hipStream_t st);
+// rows of set indices into that table (device memory; validated by the caller): block t uses set tab[s * stream_stride + t / seg_blocks];
+// fade: the crossfade over the first block of a segment whose set differs from the one in front (prev: in front of the call's
+// first block, stream s reads prev[s * prev_stride]; nullptr: no boundary there)
+struct ConvLayoutRows {
+    const unsigned *tab = nullptr;
+    int seg_blocks = 1, stream_stride = 0;
+    const unsigned *prev = nullptr;
+    int prev_stride = 0;
+    bool fade = false;
+};
+// n_blocks of every stream's lays_K channels -> two ears, times gain.  rows == nullptr: set `one_set` throughout, served by
+// k_conv_p1_layout on that set's slice of the table; else one launch of k_conv_p1_layout_irs.  Out of place, asynchronous on st
+int conv_launch_layout_scheduled(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
+                                 float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st,
+                                 const ConvLayoutRows *rows, size_t one_set);
 // the handle's four responses become set `set` of the table, overlaps and history untouched (asynchronous on st)
 int conv_adopt_schedule_set(ConvState &c, size_t set, hipStream_t st);
 // the per-path overlaps from the lazy state with the CURRENT spectra, the lazy state kept valid beside them (tails_both)

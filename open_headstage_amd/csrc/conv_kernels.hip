@@ -1530,6 +1530,140 @@ __global__ __launch_bounds__(64 * kLayoutWaves, kLayoutWavesPerSimd) void k_conv
     }
 }
 
+// k_conv_p1_layout_irs (ohs_batch_process_layout_scheduled; kernels.h: ConvLayoutIrArgs): k_conv_p1_layout with the layout of every
+// block looked up in a table of layouts ([set][pair][1024] float4) by the stream's row of set indices, as k_conv_p1_irs looks up its
+// set -- one scalar load per block, segment lay_k and position lay_r two scalar counters (one division per wave, none per block) --,
+// and with the crossfade of k_conv_p1_irs_xf in the form that kernel could not afford: lay_prev is the previous segment's index (the
+// caller's prev in front of the call's first block, ~0 = none: no boundary), and the first block of a segment whose set differs from
+// it runs 2 P "pairs" instead of P.  Passes 0 .. P - 1 take the block's frames times g[n] = (512 - n) / 512 through the OLD set's P
+// tables, passes P .. 2 P - 1 the same frames times f[n] = n / 512 through the block's own; all 2 P products accumulate in the same
+// sixteen registers, then ONE inverse transform, and no tail waits anywhere: the frames leave as (w + overlap) * gain, the upper
+// half is the overlap the block leaves.  The accumulator already lives across forward transforms here, which is what the one-inverse
+// form needs and what four waves per SIMD could not hold (k_conv_p1_irs_xf's comment); at three it costs nothing more.  The ramps are
+// rebuilt per pass from the lane number (exact in f32: one multiplication per sample and channel); a fading block requests its frames
+// twice -- pairs 0 .. P - 1, then again 0 .. P - 1, the second time an L2 hit.  The test is wave-uniform, so every other block is
+// k_conv_p1_layout's block on its set, operation for operation; L.fade == 0 (RING_OUT) never fades.  The dry block in front of a chunk
+// takes the same path as any block: it reads the set (and the fade) of ITS block.  Workgroup shape, LDS plan, chunks, prefetch plan
+// and the address idiom are k_conv_p1_layout's.
+__global__ __launch_bounds__(64 * kLayoutWaves, kLayoutWavesPerSimd) void k_conv_p1_layout_irs(const ConvP1Args A, const ConvLayoutIrArgs L)
+{
+    const long long wg = p1_xcd_block(A);
+    if (wg < 0) return;
+    ohs_set_fp_mode(A.fp_mode);
+    extern __shared__ __attribute__((aligned(16))) float2 smem[];
+    float2 *tab = smem;
+    fill_twiddle_tables(tab, A.tw, threadIdx.x, 64 * kLayoutWaves);
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const unsigned ul = (unsigned)lane;
+    float2 *lds = smem + kTabComplex + wave * kWaveLdsComplex;
+    const long long gw = wg * kLayoutWaves + wave;
+    if (gw >= (long long)A.n_streams * A.chunks) return;
+    const int s = __builtin_amdgcn_readfirstlane((int)(gw / A.chunks));
+    const int ck = __builtin_amdgcn_readfirstlane((int)(gw % A.chunks));
+    const int b0 = __builtin_amdgcn_readfirstlane((int)((long long)ck * A.n_blocks / A.chunks));
+    const int b1 = __builtin_amdgcn_readfirstlane((int)((long long)(ck + 1) * A.n_blocks / A.chunks));
+    if (b0 >= b1) return;
+    const int t_first = ck > 0 ? b0 - 1 : b0;
+    const int P = L.n_pairs, K = L.n_channels;
+
+    const float *in_s = A.in + (size_t)s * A.in_stream_stride;
+    float *ql = A.out + (size_t)s * A.out_stream_stride + (size_t)t_first * kBlock;
+
+    const unsigned *lay_row = L.tab + (size_t)s * (size_t)L.stream;
+    int lay_k = __builtin_amdgcn_readfirstlane(t_first / L.seg);
+    int lay_r = __builtin_amdgcn_readfirstlane(t_first - lay_k * L.seg);
+    unsigned lay_prev = lay_k > 0 ? (unsigned)__builtin_amdgcn_readfirstlane((int)lay_row[lay_k - 1])
+                      : L.prev    ? (unsigned)__builtin_amdgcn_readfirstlane((int)L.prev[(size_t)s * (size_t)L.prev_stream])
+                                  : 0xffffffffu;
+
+    float2 tail[8];
+    if (ck == 0) {
+        const float2 *mt = A.merged_in + (size_t)s * (8 * 64);
+#pragma unroll
+        for (int a = 0; a < 8; ++a) tail[a] = mt[a * 64 + ul];
+    } else {
+#pragma unroll
+        for (int a = 0; a < 8; ++a) tail[a] = make_float2(0.0f, 0.0f);
+    }
+    float xa[8], xb[8];
+    auto request = [&](int t, int p) {
+        unsigned u = ul;
+        asm volatile("" : "+v"(u));
+        const float *pa = in_s + (size_t)(2 * p) * A.in_ch_stride + (size_t)t * kBlock + u;
+#pragma unroll
+        for (int a = 0; a < 8; ++a) xa[a] = OHS_P1_LD(&pa[64 * a]);
+        if (2 * p + 1 < K) {
+            const float *pb = pa + A.in_ch_stride;
+#pragma unroll
+            for (int a = 0; a < 8; ++a) xb[a] = OHS_P1_LD(&pb[64 * a]);
+        } else {
+#pragma unroll
+            for (int a = 0; a < 8; ++a) xb[a] = 0.0f;
+        }
+    };
+    request(t_first, 0);
+    const PairedPlan plan = paired_plan(lane);
+    for (int t = t_first; t < b1; ++t) {
+        const bool dry = t < b0;
+        const unsigned lay_cur = (unsigned)__builtin_amdgcn_readfirstlane((int)lay_row[lay_k]);
+        const bool fade = L.fade && lay_r == 0 && lay_prev != 0xffffffffu && lay_prev != lay_cur;
+        const int Q = fade ? 2 * P : P;
+        float2 w[16];
+        int p = 0;          // the pair of pass q: q, or q - P in the second half of a fading block
+        for (int q = 0; q < Q; ++q) {
+            const bool old_half = fade && q < P;
+            float2 v[16];
+            if (fade) {
+                float n = (float)lane;
+                asm volatile("" : "+v"(n));     // (the ramp values are not worth registers across the transforms)
+                const float sn = old_half ? -n : n, c0 = old_half ? (float)kBlock : 0.0f, c64 = old_half ? -64.0f : 64.0f;
+#pragma unroll
+                for (int a = 0; a < 8; ++a) {
+                    const float ramp = ((c0 + c64 * (float)a) + sn) * (1.0f / (float)kBlock);     // g, then f: exact
+                    v[a] = make_float2(xa[a] * ramp, xb[a] * ramp);
+                }
+            } else {
+#pragma unroll
+                for (int a = 0; a < 8; ++a) v[a] = make_float2(xa[a], xb[a]);
+            }
+#pragma unroll
+            for (int a = 0; a < 8; ++a) v[a + 8] = make_float2(0.0f, 0.0f);
+            if (q + 1 < Q) request(t, p + 1 < P ? p + 1 : 0);
+            wave_fft_fwd_paired(v, lds, tab, lane, plan);
+            unsigned u = ul;
+            asm volatile("" : "+v"(u));
+            const float4 *cdp = L.cd + ((size_t)(old_half ? lay_prev : lay_cur) * (size_t)P + (size_t)p) * kFft + u;
+            if (q == 0) p1_spectral_product_paired_global(v, w, cdp, lane);
+            else p1_spectral_product_paired_global_add(v, w, cdp, lane);
+            if (++p == P) p = 0;
+        }
+        // behind the launch's last block the prefetch re-reads that block (its own frames: in bounds; the values are never used)
+        request(t + 1 < A.n_blocks ? t + 1 : t, 0);
+        wave_fft_inv_paired(w, lds, tab, lane, plan);
+        if (!dry) {
+            unsigned u = ul;
+            asm volatile("" : "+v"(u));
+            float *pl = ql + u, *pr = pl + A.out_ch_stride;
+#pragma unroll
+            for (int a = 0; a < 8; ++a) {
+                OHS_P1_ST(&pl[64 * a], (w[a].x + tail[a].x) * A.gain);
+                OHS_P1_ST(&pr[64 * a], (w[a].y + tail[a].y) * A.gain);
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < 8; ++a) tail[a] = w[a + 8];
+        ql += kBlock;
+        lay_prev = lay_cur;
+        if (++lay_r == L.seg) { lay_r = 0; ++lay_k; }
+    }
+    if (b1 == A.n_blocks) {         // the overlap the call leaves behind
+        float2 *mo = A.merged_out + (size_t)s * (8 * 64);
+#pragma unroll
+        for (int a = 0; a < 8; ++a) mo[a * 64 + ul] = tail[a];
+    }
+}
+
 // pre-pass, two small kernels that read INPUT frames only -- which is why they run before the main kernel stores over
 // them (in place) -- one transform pair per wave:
 //   k_conv_p1_state  wave (s, speaker): the overlap the launch's last block leaves behind in the reference's per-path
@@ -1879,6 +2013,25 @@ hipError_t launch_conv_p1_layout(const ConvP1Args &a, const ConvLayoutArgs &l, h
     const long long waves = (long long)a.n_streams * a.chunks;
     const dim3 grid(xcd_grid((unsigned)((waves + kLayoutWaves - 1) / kLayoutWaves), a.xcd_n));
     hipLaunchKernelGGL(k_conv_p1_layout, grid, dim3(64 * kLayoutWaves), shmem, st, a, l);
+    return hipGetLastError();
+}
+
+// the scheduled layout kernel: launch_conv_p1_layout's checks and shape, plus the rows
+hipError_t launch_conv_p1_layout_irs(const ConvP1Args &a, const ConvLayoutIrArgs &l, hipStream_t st)
+{
+    if (a.n_blocks <= 0 || a.n_streams <= 0 || a.chunks > a.n_blocks) return hipErrorInvalidValue;
+    if (!(a.chunks == 1 || a.chunks == 2 || a.chunks == 4 || a.chunks == 8 || a.chunks == 16)) return hipErrorInvalidValue;
+    if (a.xcd_n < 1 || a.xcd_n > 8 || a.xcd_lo < 0 || a.xcd_lo + a.xcd_n > 8) return hipErrorInvalidValue;
+    if (!a.in || !a.out || !a.merged_in || !a.merged_out || a.merged_in == a.merged_out || !a.tw) return hipErrorInvalidValue;
+    if (!l.cd || l.n_channels < 1 || l.n_pairs != (l.n_channels + 1) / 2) return hipErrorInvalidValue;
+    if (!l.tab || l.seg < 1 || l.stream < 0 || l.prev_stream < 0) return hipErrorInvalidValue;
+    const size_t shmem = (kTabComplex + kLayoutWaves * kWaveLdsComplex) * sizeof(float2);
+    static std::atomic<unsigned long long> lds_ok{0};
+    hipError_t e = allow_large_lds(reinterpret_cast<const void *>(k_conv_p1_layout_irs), shmem, lds_ok);
+    if (e != hipSuccess) return e;
+    const long long waves = (long long)a.n_streams * a.chunks;
+    const dim3 grid(xcd_grid((unsigned)((waves + kLayoutWaves - 1) / kLayoutWaves), a.xcd_n));
+    hipLaunchKernelGGL(k_conv_p1_layout_irs, grid, dim3(64 * kLayoutWaves), shmem, st, a, l);
     return hipGetLastError();
 }
 

@@ -279,6 +279,24 @@ struct ConvLayoutArgs {
 int conv_layout_waves_per_cu();  // resident waves of k_conv_p1_layout per CU
 // a.chunks: 1, 2, 4, 8 or 16, <= a.n_blocks; every chunk but the first runs one dry block in front of its range
 hipError_t launch_conv_p1_layout(const ConvP1Args &a, const ConvLayoutArgs &l, hipStream_t st);
+// A layout per segment and stream out of a table of layouts (ohs_batch_process_layout_scheduled): k_conv_p1_layout_irs, the body of
+// k_conv_p1_layout with the P tables of every block looked up by the stream's row of set indices -- block t of the launch (= of the
+// call: one launch per call) uses set tab[s * stream + t / seg] --, and, with `fade`, a crossfade from the previous segment's set over
+// the first block of a segment whose set differs from it: 2 P forward transforms and products, one inverse.  A struct of its own, so
+// that ConvLayoutArgs and with it k_conv_p1_layout stay what they are.  Of ConvP1Args the kernel reads what k_conv_p1_layout reads.
+struct ConvLayoutIrArgs {
+    const float4 *cd;           // [set][pair][1024] (C[i], D[i]) in the paired layout (launch_irs_tables, (set, pair) as the "set")
+    int n_pairs;                // ceil(n_channels / 2)
+    int n_channels;             // odd: channel 2 n_pairs - 1 is not read (and its two responses in cd are zero)
+    const unsigned *tab;        // rows of set indices (device memory)
+    int stream;                 // stream s reads its row at tab + s * stream (0: one row for all streams)
+    int seg;                    // blocks per segment
+    const unsigned *prev;       // the set in front of the call's first block per stream (device memory), or nullptr: no boundary there
+    int prev_stream;            // stream s reads prev[s * prev_stream] (0: one entry for all streams)
+    int fade;                   // 1: OHS_LAYOUT_SWITCH_CROSSFADE; 0: RING_OUT, no block fades (prev is not read)
+};
+// a.chunks as for launch_conv_p1_layout; the host has checked every index against the table
+hipError_t launch_conv_p1_layout_irs(const ConvP1Args &a, const ConvLayoutIrArgs &l, hipStream_t st);
 // cd[set][2][1024] (launch_build_cd per set) -> dst[set][1024] in the block loop's layout
 hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st);
 // CD[0][..] = (A - jB)/2, CD[1][..] = (A + jB)/2 from four single-partition spectra

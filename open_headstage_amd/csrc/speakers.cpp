@@ -101,4 +101,37 @@ int ohs_sofa_layout_irs(const ohs_sofa *sofa, size_t n_channels, const float *az
     return OHS_OK;
 }
 
+// A table of layouts for ohs_batch_set_layout_schedule_irs, one per head yaw: set j is ohs_sofa_layout_irs with every speaker at
+// az[c] - yaw[j] (the head turns to the right by yaw, positive like the azimuth, so the room turns to the left around it), wrapped
+// into [-180, 180).  Two passes over that function: the lengths first, then every set at the longest.
+int ohs_sofa_layout_yaw_irs(const ohs_sofa *sofa, size_t n_channels, const float *az_deg, const float *el_deg, float radius_m, float fs,
+                            size_t n_yaws, const float *yaw_deg, float *out, size_t len, size_t *needed_len)
+{
+    if (!sofa || !az_deg || !el_deg || !yaw_deg || !needed_len) { ohsint_set_error("NULL argument"); return OHS_ERR_INVALID_ARG; }
+    if (n_channels == 0 || n_channels > 16) { ohsint_set_error("n_channels must be 1 .. 16"); return OHS_ERR_INVALID_ARG; }
+    if (n_yaws == 0 || n_yaws > 65536) { ohsint_set_error("n_yaws must be 1 .. 65536"); return OHS_ERR_INVALID_ARG; }
+    std::vector<float> az(n_yaws * n_channels);
+    size_t longest = 0;
+    for (size_t j = 0; j < n_yaws; ++j) {
+        float *a = &az[j * n_channels];
+        for (size_t c = 0; c < n_channels; ++c) {
+            const float d = az_deg[c] - yaw_deg[j];
+            a[c] = d - 360.0f * std::floor((d + 180.0f) / 360.0f);
+        }
+        size_t n = 0;
+        const int rc = ohs_sofa_layout_irs(sofa, n_channels, a, el_deg, radius_m, fs, nullptr, 0, &n);
+        if (rc) return rc;
+        longest = std::max(longest, n);
+    }
+    *needed_len = longest;
+    if (!out) return OHS_OK;
+    if (len < longest) { ohsint_set_error("len is smaller than the longest response"); return OHS_ERR_INVALID_ARG; }
+    for (size_t j = 0; j < n_yaws; ++j) {
+        size_t n = 0;
+        const int rc = ohs_sofa_layout_irs(sofa, n_channels, &az[j * n_channels], el_deg, radius_m, fs, out + j * n_channels * 2 * len, len, &n);
+        if (rc) return rc;
+    }
+    return OHS_OK;
+}
+
 }  // extern "C"

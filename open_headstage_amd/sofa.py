@@ -153,6 +153,24 @@ def layout_irs(sofa: MySofa, az, el, radius_m: float = 1.0, fs: float = 0.0, len
     return out
 
 
+def layout_yaw_irs(sofa: MySofa, az, el, yaws, radius_m: float = 1.0, fs: float = 0.0, length: int | None = None) -> np.ndarray:
+    """[n_yaws][K][2][len]: layout_irs per head yaw (degrees, positive to the right), every speaker at az[c] - yaws[j]; all sets
+    zero-padded to `length` (default: the longest response of any set) -- ohs_sofa_layout_yaw_irs, the array
+    BatchProcessor.set_layout_table takes."""
+    azf = np.ascontiguousarray(az, np.float32).ravel()
+    elf = np.ascontiguousarray(el, np.float32).ravel()
+    yf = np.ascontiguousarray(yaws, np.float32).ravel()
+    if azf.size != elf.size:
+        raise ValueError("az and el must have one entry per speaker")
+    n = C.c_size_t()
+    args = (sofa._h, azf.size, azf.ctypes.data_as(fp), elf.ctypes.data_as(fp), radius_m, fs, yf.size, yf.ctypes.data_as(fp))
+    check(lib().ohs_sofa_layout_yaw_irs(*args, None, 0, C.byref(n)))
+    ln = int(n.value) if length is None else int(length)
+    out = np.zeros((yf.size, azf.size, 2, max(ln, 1)), np.float32)
+    check(lib().ohs_sofa_layout_yaw_irs(*args, out.ctypes.data_as(fp), ln, C.byref(n)))
+    return out
+
+
 def load_into(target, irs) -> None:
     """get_hrtf_irs -> set_ir wiring: target is a ConvolutionEngine or a BatchProcessor."""
     for p, h in zip((ConvolutionPath.Lsl, ConvolutionPath.Lsr, ConvolutionPath.Rsl, ConvolutionPath.Rsr), irs):

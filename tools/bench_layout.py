@@ -14,6 +14,17 @@ Device time per repetition by HIP events on a stream of the tool's own, after `-
 min - max of `--reps` repetitions.  The two routes' outputs are compared once (relative RMS; they differ by f32 rounding).
 
     python tools/bench_layout.py [--reps 12] [--warmup 3] [--out profiles/layout_bench.json]
+
+--scheduled prices ohs_batch_process_layout_scheduled instead (head-tracked layouts: 72 sets, seg_blocks 2, every stream a row of
+its own with a new set in every segment), four routes alternating in one process:
+
+  sched_xf   one ohs_batch_process_layout_scheduled call, OHS_LAYOUT_SWITCH_CROSSFADE
+  composed   what the library offered before: ceil(K / 2) handles, each holding one pair's four responses of every set as its
+             set table, one ohs_batch_process_ir_crossfaded per handle at the same rows, then a torch sum
+  sched_ro   the same call under OHS_LAYOUT_SWITCH_RING_OUT
+  plain      ohs_batch_process_layout on set 0 (no schedule): what the walk through the table and the fades cost on top
+
+    python tools/bench_layout.py --scheduled [--out profiles/layout_sched_bench.json]
 """
 import argparse
 import json
@@ -105,6 +116,105 @@ def bench_one(a, name, K):
     return rec
 
 
+def bench_scheduled(a, name, K):
+    import numpy as np
+    import torch
+    import open_headstage_amd as ohs
+    from open_headstage_amd import synth
+
+    dev = torch.device("cuda:0")
+    S, nb, seg, n_sets = a.streams, a.blocks, a.seg_blocks, a.sets
+    frames = nb * 512
+    P = (K + 1) // 2
+    n_segs = -(-nb // seg)
+    base = synth.hrir_set(a.taps)
+    table = np.zeros((n_sets, K, 2, a.taps), np.float32)
+    for j in range(n_sets):
+        for c in range(K):
+            for e in range(2):
+                table[j, c, e] = np.roll(base[(2 * c + e + j) % 4], (5 * c + e + 3 * j) % 23) * np.float32(1.0 - 0.02 * c)
+        table[j] /= np.abs(table[j]).sum(axis=(0, 2), keepdims=True)
+    # every stream its own row, a new set in every segment
+    idx = np.zeros((S, n_segs), np.uint32)
+    for s in range(S):
+        idx[s] = (7 * s + np.arange(n_segs) * (1 + s % 5)) % n_sets
+    assert (idx[:, 1:] != idx[:, :-1]).all()
+
+    sched = ohs.BatchProcessor(S, num_bands=10)
+    sched.set_layout_table(table)
+    plain = ohs.BatchProcessor(S, num_bands=10)
+    plain.set_layout_irs(table[0])
+    pairs = []
+    zero = np.zeros((n_sets, a.taps), np.float32)
+    for p in range(P):
+        h = ohs.BatchProcessor(S, num_bands=10)
+        odd = 2 * p + 1 >= K
+        h.set_schedule_irs(np.stack([table[:, 2 * p, 0], table[:, 2 * p, 1], zero if odd else table[:, 2 * p + 1, 0],
+                                     zero if odd else table[:, 2 * p + 1, 1]], axis=1))
+        pairs.append(h)
+
+    Kp = 2 * P
+    x = torch.empty((S, Kp, frames), dtype=torch.float32, device=dev)
+    for c in range(Kp):
+        x[:, c] = synth.white_noise_torch(1000 * c, S, frames, dev)[:, 0] if c < K else 0.0
+    y = {n: torch.empty((S, 2, frames), dtype=torch.float32, device=dev) for n in ("sched_xf", "composed", "sched_ro", "plain")}
+    scratch = torch.empty((S, Kp, frames), dtype=torch.float32, device=dev)
+    stream = torch.cuda.Stream(dev)
+    hs = stream.cuda_stream
+
+    def sched_call(fade, out):
+        sched.process_layout_scheduled_ptr(x.data_ptr(), out.data_ptr(), nb, Kp * frames, frames, 2 * frames, frames, seg, idx, None,
+                                           fade, hs)
+
+    def composed():
+        for p, h in enumerate(pairs):
+            off = 4 * 2 * p * frames
+            h.process_ir_crossfaded_ptr(x.data_ptr() + off, scratch.data_ptr() + off, nb, Kp * frames, frames, seg, idx, None, hs)
+        if P == 1:
+            y["composed"].copy_(scratch[:, 0:2])
+        else:
+            torch.add(scratch[:, 0:2], scratch[:, 2:4], out=y["composed"])
+        for p in range(2, P):
+            y["composed"].add_(scratch[:, 2 * p:2 * p + 2])
+
+    routes = [("sched_xf", lambda: sched_call(True, y["sched_xf"])), ("composed", composed),
+              ("sched_ro", lambda: sched_call(False, y["sched_ro"])),
+              ("plain", lambda: plain.process_layout_ptr(x.data_ptr(), y["plain"].data_ptr(), nb, Kp * frames, frames, 2 * frames,
+                                                         frames, hs))]
+    ms = {n: [] for n, _ in routes}
+    launches = {}
+    torch.cuda.synchronize(dev)     # (the inputs were filled on torch's own stream; `stream` does not wait for it by itself)
+    with torch.cuda.stream(stream):
+        for _ in range(a.warmup):
+            for n, fn in routes:
+                fn()
+                if n.startswith("sched"):
+                    launches[n] = [int(sched.last_layout_scheduled())] + list(sched.last_layout_launch())
+        stream.synchronize()
+        d = (y["sched_xf"].double() - y["composed"].double())
+        rel = float(torch.sqrt((d * d).mean()) / torch.sqrt((y["composed"].double() ** 2).mean()))
+        for _ in range(a.reps):
+            for n, fn in routes:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                fn()
+                e1.record(stream)
+                stream.synchronize()
+                ms[n].append(e0.elapsed_time(e1))
+    rec = {"name": name, "channels": K, "pairs": P, "streams": S, "blocks": nb, "taps": a.taps, "eq": 0, "sets": n_sets,
+           "seg_blocks": seg, "reps": a.reps, "warmup": a.warmup, "scheduled_and_launch": launches,
+           "plain_launch": list(plain.last_layout_launch()), "sched_xf_vs_composed_relative_rms": rel}
+    for n in ms:
+        v = ms[n]
+        rec[n] = {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4),
+                  "all_ms": [round(t, 4) for t in v]}
+    rec["sched_xf_median_over_composed_min"] = round(rec["sched_xf"]["median_ms"] / rec["composed"]["min_ms"], 4)
+    rec["sched_xf_median_below_composed_min"] = rec["sched_xf"]["median_ms"] < rec["composed"]["min_ms"]
+    rec["sched_xf_median_over_plain_median"] = round(rec["sched_xf"]["median_ms"] / rec["plain"]["median_ms"], 4)
+    rec["sched_ro_median_over_plain_median"] = round(rec["sched_ro"]["median_ms"] / rec["plain"]["median_ms"], 4)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=256)
@@ -114,16 +224,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--layouts", type=str, default="5.1,7.1")
     ap.add_argument("--tag", type=str, default="")
+    ap.add_argument("--scheduled", action="store_true")         # ohs_batch_process_layout_scheduled and its routes
+    ap.add_argument("--sets", type=int, default=72)
+    ap.add_argument("--seg-blocks", type=int, default=2)
     ap.add_argument("--out", type=str, default="")
     a = ap.parse_args()
     assert a.reps >= 1 and a.warmup >= 1
     sys.path.insert(0, ROOT)
     from open_headstage_amd import build
     known = {"5.1": 6, "7.1": 8}
-    res = build.resources().get("k_conv_p1_layout", {})
-    out = {"tag": a.tag, "kernel": {"name": "k_conv_p1_layout", **res}, "results": []}
+    kernel = "k_conv_p1_layout_irs" if a.scheduled else "k_conv_p1_layout"
+    res = build.resources().get(kernel, {})
+    out = {"tag": a.tag, "kernel": {"name": kernel, **res}, "results": []}
     for name in a.layouts.split(","):
-        rec = bench_one(a, name, known[name] if name in known else int(name))
+        rec = (bench_scheduled if a.scheduled else bench_one)(a, name, known[name] if name in known else int(name))
         print(json.dumps(rec), flush=True)
         out["results"].append(rec)
     if a.out:
