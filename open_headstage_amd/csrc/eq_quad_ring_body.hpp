@@ -18,7 +18,15 @@
 // alpha wrote.  The slot carries the port (a group = 16 steps: two stores, two injects, one load, one wait), so the steady
 // state is 81 issue slots per 16 samples -- 5.06 per sample against 6.02 + 4.75 / 48.  The loop is generated from the model's
 // own instruction list (tools/gen_eq_quad_ring_asm.py -> eq_quad_ring_asm.inc), which also checks every DPP read's distance.
-// A slot with nothing to carry holds a v_nop.  FILL_SLOTS (experiments build, Tuning::eq_quad_fill) is the loop with a fill
+// Where the port's memory instructions issue is what the loop's time above 4 ticks per slot is made of: each of the three,
+// alone between VALU instructions, costs the wave about 8 ticks beyond its slot, one directly behind another about none
+// (without them the loop runs at 20.41 ticks per sample, with them at 21.91).  So the loop the
+// kernel runs (eq_quad_ring_cl_asm.inc, the model's port variant C2) parks step 8's value in a holding register (v20, a
+// plain v_mov in that step's slot) and issues store, store, load back to back in step 15's slot: 83 slots per 16 samples at
+// 21.44 ticks per sample.  Same ring, same lanes, same addresses, same bits; stores and the load only issue later than they
+// did, so in place a store still never passes the load of its sample.  kQuadLoopLone (experiments build,
+// Tuning::eq_quad_lone_port) is the loop of round 12 with the three alone in the slots of steps 8, 10 and 15.
+// A slot with nothing to carry holds a v_nop.  kQuadLoopFill (experiments build, Tuning::eq_quad_fill) is round 12's loop with a fill
 // instruction there, v_and_b32_dpp on v19 (a register nothing else touches), which keeps the vector unit for the four
 // cycles a step instruction takes instead of leaving them to a convolution wave of the same SIMD: a tie -- the loop runs at
 // the lone prototype's 21.9 ticks per sample with or without the convolution underneath.
@@ -34,6 +42,7 @@
 #include "kernels.h"
 #include "eq_ring64_body.hpp"   // kWaveRor1, ring64_rsrc, ring2_ld / ring2_st, dpp_mov
 #include "eq_quad_ring_asm.inc"
+#include "eq_quad_ring_cl_asm.inc"
 #include <type_traits>
 
 namespace ohs {
@@ -43,6 +52,9 @@ constexpr int kQuadK = EQ_QUAD_RING_K;  // groups per asm iteration = input regi
 constexpr int kQp0003 = 0xC0, kQp0033 = 0xF0, kQp0012 = 0x90, kQp0101 = 0x44;
 
 struct QuadRegs { float Z0, Z1, Zp, G, P; };
+// the asm run's loop: the port's memory instructions in one cluster per group (the product's), or -- experiments build --
+// round 12's loop with each of them alone in its slot, without or with the fill instruction in the slots that carry nothing
+enum { kQuadLoopCluster, kQuadLoopLone, kQuadLoopFill };
 
 // A DPP read for the C++ form of the step.  Every control of the step (wave_ror:1, the quad_perms) gives every lane a source
 // lane, so bound_ctrl changes no value; with it the compiler folds the move into the VOP2 instruction that consumes it --
@@ -54,13 +66,14 @@ __device__ __forceinline__ float quad_dpp(float src)
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(src), CTRL, 0xf, 0xf, true));
 }
 
-template <bool FILL_SLOTS = false>
+template <int LOOP = kQuadLoopCluster>
 __device__ __forceinline__ void eq_quad_ring_wave(const float *in, float *out, long long stream_stride, long long ch_stride,
                                                   long long n, int n_chains, int nb, const EqPassTable &tab,
                                                   float *__restrict__ state, long long chain)
 {
     constexpr int G = kQuadGroup, K = kQuadK;
     static_assert(K == 8, "the operand list below names x0 .. x7");
+    static_assert(EQ_QUAD_RING_CL_HOLD == 1, "the clobber list below names one holding register, v20");
     if (chain >= n_chains) return;
     const int lane = threadIdx.x & 63, q = lane >> 2, role = lane & 3;
     const int n32 = (int)n;
@@ -171,7 +184,7 @@ __device__ __forceinline__ void eq_quad_ring_wave(const float *in, float *out, l
         const unsigned inc_ld = conv ? 4u * G * K : 0u, inc_st = st_lane ? 4u * G * K : 0u;
         unsigned cnt = 0u - (unsigned)__builtin_amdgcn_readfirstlane(iters);
 #ifdef OHS_EXPERIMENTS
-        if constexpr (FILL_SLOTS) {
+        if constexpr (LOOP == kQuadLoopFill) {
             unsigned fill = 0u;     // the fill's own register: F & F, whatever it holds
             asm volatile(
                 "s_nop 4\n"
@@ -182,16 +195,26 @@ __device__ __forceinline__ void eq_quad_ring_wave(const float *in, float *out, l
                   [F] "+{v19}"(fill), [cnt] "+s"(cnt)
                 : [C1] "{v7}"(C1), [C2] "{v8}"(C2), [incl] "{v9}"(inc_ld), [incs] "{v10}"(inc_st), [rin] "s"(rin), [rout] "s"(rout)
                 : "memory", "scc", "vcc");
+        } else if constexpr (LOOP == kQuadLoopLone) {
+            asm volatile(
+                "s_nop 4\n"
+                EQ_QUAD_RING_LOOP
+                : [Z0] "+{v2}"(r.Z0), [Z1] "+{v3}"(r.Z1), [Zp] "+{v4}"(r.Zp), [Gr] "+{v5}"(r.G), [P] "+{v6}"(r.P),
+                  [vs] "+{v0}"(voff_st), [vl] "+{v1}"(voff_ld), [x0] "+{v11}"(xcur), [x1] "+{v12}"(xnext), [x2] "+{v13}"(x2),
+                  [x3] "+{v14}"(x3), [x4] "+{v15}"(x4), [x5] "+{v16}"(x5), [x6] "+{v17}"(x6), [x7] "+{v18}"(x7), [cnt] "+s"(cnt)
+                : [C1] "{v7}"(C1), [C2] "{v8}"(C2), [incl] "{v9}"(inc_ld), [incs] "{v10}"(inc_st), [rin] "s"(rin), [rout] "s"(rout)
+                : "memory", "scc", "vcc");
         } else
 #endif
+        // (v20: the holding register, written and read inside the loop only -- v19 is left to the fill)
         asm volatile(
             "s_nop 4\n"
-            EQ_QUAD_RING_LOOP
+            EQ_QUAD_RING_CL_LOOP
             : [Z0] "+{v2}"(r.Z0), [Z1] "+{v3}"(r.Z1), [Zp] "+{v4}"(r.Zp), [Gr] "+{v5}"(r.G), [P] "+{v6}"(r.P),
               [vs] "+{v0}"(voff_st), [vl] "+{v1}"(voff_ld), [x0] "+{v11}"(xcur), [x1] "+{v12}"(xnext), [x2] "+{v13}"(x2),
               [x3] "+{v14}"(x3), [x4] "+{v15}"(x4), [x5] "+{v16}"(x5), [x6] "+{v17}"(x6), [x7] "+{v18}"(x7), [cnt] "+s"(cnt)
             : [C1] "{v7}"(C1), [C2] "{v8}"(C2), [incl] "{v9}"(inc_ld), [incs] "{v10}"(inc_st), [rin] "s"(rin), [rout] "s"(rout)
-            : "memory", "scc", "vcc");
+            : "memory", "scc", "vcc", "v20");
         // (x0, x1 now hold the inputs of groups g1, g1 + 1: the run's last inject A took x0, group g1's inject B is next)
         g = g1;
 #pragma unroll 1

@@ -33,6 +33,9 @@ struct Tuning {
                                             // one band per quad of lanes (eq_quad_ring_body.hpp: what the library chooses)
     int eq_quad_fill = 0;                   // 1: the quad body's loop with a VOP2+DPP fill instruction in the slots that carry
                                             // nothing instead of v_nop (experiments build only; a tie: DESIGN.md 4.5, round 12)
+    int eq_quad_lone_port = 0;              // 1: the quad body's loop of round 12, the port's two stores and its load each alone in the
+                                            // slot of its step, instead of the loop with one memory cluster per group (experiments
+                                            // build only; the A/B and the "same bits" test of DESIGN.md 4.5, round 15)
     int eq_wg_waves = 0;                    // 0: 1 wave per workgroup below one wave per CU, else 4
     int eq_lds = 0;                         // LDS reservation per EQ workgroup, bytes
     // ohs_batch_process

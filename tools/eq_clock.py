@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Cycles and shader clock inside k_eq_ring (experiment build: OHS_BUILD_TAG=eqstamps OHS_EXTRA_DEFS=-DOHS_EQ_STAMPS): s_memtime
 (shader clock) against s_memrealtime (100 MHz) over every wave of EVERY EQ launch of one steady-state headline step, with
-and without the convolution running beside it, for the quad ring's loop with v_nop and with the fill instruction
-(Tuning::eq_quad_fill).  Per launch: shader-clock ticks per sample (independent of the clock), the clock, and how far the
-slowest wave ends behind the median one (a launch ends with its slowest wave).
+and without the convolution running beside it, for the quad ring's loops: the library's (one memory cluster per group), round
+12's with the port's memory instructions each alone in its slot (Tuning::eq_quad_lone_port; the only loop of a library from
+before round 15, "v_nop" there) and that one with the fill instruction (Tuning::eq_quad_fill).  Per launch: shader-clock ticks per sample (independent of the clock), the clock, and how far the
+slowest wave ends behind the median one (a launch ends with its slowest wave); per step the line through the six launches'
+median ticks over their samples: slope = the loop's ticks per sample, intercept = a launch's fixed ticks.
     OHS_LIB=open_headstage_amd/libohs_hip_eqstamps.so python tools/eq_clock.py [--json FILE] [streams ...]"""
 import ctypes as C
 import json
@@ -42,8 +44,14 @@ def launches(st):
     return out
 
 
-def run(S, conv_on, fill, sink):
-    assert L.ohs_debug_set_tuning(b"eq_quad_fill", str(int(fill)).encode()) == 0
+HAS_LONE = L.ohs_debug_set_tuning(b"eq_quad_lone_port", b"0") == 0
+LOOPS = ("cluster", "lone", "fill") if HAS_LONE else ("v_nop", "fill")
+
+
+def run(S, conv_on, loop, sink):
+    assert L.ohs_debug_set_tuning(b"eq_quad_fill", str(int(loop == "fill")).encode()) == 0
+    if HAS_LONE:
+        assert L.ohs_debug_set_tuning(b"eq_quad_lone_port", str(int(loop == "lone")).encode()) == 0
     bp = ohs.BatchProcessor(S, num_bands=10)
     irs = synth.hrir_set(512)
     for p in range(4):
@@ -70,10 +78,10 @@ def run(S, conv_on, fill, sink):
     assert 0 < count.value <= RECORDS, count.value
     st = np.frombuffer(buf, dtype=np.uint64).reshape(RECORDS, 6)[:count.value].astype(np.int64)
     st = st[st[:, 0] < 2 * S]       # (waves behind the last chain leave at once)
-    loop = "fill" if fill else "v_nop"
     print(f"streams {S}, loop {loop}, convolution {'on' if conv_on else 'muted (empty IRs: general path, no P = 1 kernel)'}: "
           f"{a.elapsed_time(b) / 4:.3f} ms per step, {count.value} wave records", flush=True)
     t0 = st[:, 2].min()
+    fit = []
     for k, l in enumerate(launches(st)):
         n = int(l[0, 1])
         ticks = (l[:, 5] - l[:, 4]) / n
@@ -88,11 +96,17 @@ def run(S, conv_on, fill, sink):
                "last_end_behind_median_us": round(float(end.max() - np.median(end)), 1),
                "end_spread_us": round(float(end.max() - end.min()), 1)}
         sink.append(rec)
+        fit.append((n, float(np.median(l[:, 5] - l[:, 4]))))
         print(f"  launch {k}: {n:7d} samples, {len(l):4d} waves, start {rec['start_us']:8.1f} us, span {rec['span_us']:7.1f} us; "
               f"ticks per sample median {rec['ticks_per_sample'][0]:.3f} (min {rec['ticks_per_sample'][1]:.3f}, max "
               f"{rec['ticks_per_sample'][2]:.3f}); clock {rec['ghz'][0]:.3f} GHz (min {rec['ghz'][1]:.3f}, max {rec['ghz'][2]:.3f}); "
               f"last wave ends {rec['last_end_behind_median_us']:.1f} us behind the median one, ends spread over {rec['end_spread_us']:.1f} us",
               flush=True)
+    if len(fit) >= 2:
+        slope, icpt = np.polyfit([f[0] for f in fit], [f[1] for f in fit], 1)
+        sink.append({"streams": S, "loop": loop, "conv_on": bool(conv_on), "fit_ticks_per_sample": round(float(slope), 3),
+                     "fit_ticks_per_launch": round(float(icpt))})
+        print(f"  fit over {len(fit)} launches: {slope:.3f} ticks per sample + {icpt:.0f} ticks per launch", flush=True)
     del bp, x, y
     torch.cuda.empty_cache()
 
@@ -107,8 +121,8 @@ if __name__ == "__main__":
     sink = []
     for S in [int(a) for a in args] or [256]:
         for conv_on in (True, False):
-            for fill in (0, 1):
-                run(S, conv_on, fill, sink)
+            for loop in LOOPS:
+                run(S, conv_on, loop, sink)
     if out:
         with open(out, "w") as f:
             for r in sink:

@@ -22,6 +22,12 @@ Pinned registers:
     v11 ..     x0 .. x(K-1): the inputs of the next K groups, reloaded in place K groups ahead
     v19        the fill's own register (EQ_QUAD_RING_LOOP_FILL only): no other instruction reads or writes it
     VCC  every lane but c, d of the conveyor quads (the inject is a v_cndmask with the quad_perm on x)
+
+The cluster variants of the port (the model's group_program(port=...): the two stores and the load of a group issue behind
+one another instead of each alone between VALU instructions) go to a second file, eq_quad_ring_cl_asm.inc, as
+EQ_QUAD_RING_CL_LOOP; eq_quad_ring_asm.inc stays what it was.  Their holding registers are v20 .. v22 (H0 .. H2: a store's
+value parked by a v_mov_b32 in VOP3 form, 8 bytes like everything else in the loop).  The offset of a store or a load is that
+of the step its value or its register belongs to, less the iteration's advance where it issues behind the advance of v0 / v1.
 """
 import os
 import sys
@@ -31,23 +37,28 @@ sys.path.insert(0, HERE)
 import model_eq_quad_ring as model      # noqa: E402
 
 FULL = "row_mask:0xf bank_mask:0xf"
-REG = {"Z0": "v2", "Z1": "v3", "Zp": "v4", "G": "v5", "P": "v6", "C1": "v7", "C2": "v8", "F": "v19"}
+REG = {"Z0": "v2", "Z1": "v3", "Zp": "v4", "G": "v5", "P": "v6", "C1": "v7", "C2": "v8", "F": "v19",
+       "H0": "v20", "H1": "v21", "H2": "v22"}
+CL_PORT = "C2"      # the variant eq_quad_ring_cl_asm.inc carries (the gate: DESIGN.md 4.5, round 15)
 INJECT_PERM = {"A": "[0,1,2,3]", "B": "[0,1,0,1]"}
 
 
-def loop_asm(K, fill=False):
+def loop_asm(K, fill=False, port=None):
     REG.update({f"x{k}": f"v{11 + k}" for k in range(K)})
     """One iteration = groups 0 .. K - 1 of the model's program as asm lines.  v0: store offsets (lanes a, d of the conveyor
     quads: the store of step 16 (g0 - 1) + 8, g0 = the iteration's first group), v1: load offsets (the conveyor's 16 lanes:
     group g0's inputs), v9 / v10: the iteration's advance of v1 / v0, 64 K bytes.  Other lanes hold 0xFFFFF000 (out of range) and advance by 0."""
     out = []
-    wait = model.wait_count(K)
+    wait = model.wait_count(K, port) if port else model.wait_count(K)
+    adv_ld = adv_st = False         # this iteration's advance of v1 / v0 has issued
+    s_adv_st = 15 if port == "C3" else 12   # (C3: behind the last cluster, whose parked stores are two groups old)
     for k in range(K):
         last = k == K - 1
-        for ins in model.group_program(k, K, fill):
+        s = 0
+        for ins in (model.group_program(k, K, fill, port=port) if port else model.group_program(k, K, fill)):
             op, step = ins[0], ins[1]
-            s = step - model.G * k
             if op == "alpha":
+                s = step - model.G * k      # the step that issues (a parked store carries the step of its value)
                 out.append(f"v_add_f32_dpp {REG[ins[2]]}, {REG['Zp']}, {REG['G']} wave_ror:1 {FULL}")
             elif op == "delta":
                 out.append(f"v_mul_f32_dpp {REG['Zp']}, {REG[ins[2]]}, {REG['C2']} quad_perm:[0,0,0,3] {FULL}")
@@ -57,13 +68,19 @@ def loop_asm(K, fill=False):
                 out.append(f"v_sub_f32_dpp {REG['G']}, {REG[ins[2]]}, {REG['P']} quad_perm:[0,0,1,2] {FULL}")
             elif op == "store":
                 # behind the advance of v0 (slot 12 of the last group) the offsets are those of the next iteration
-                off = 64 * (k + 1) + (28 if s == 15 else 0) - (64 * K if last and s == 15 else 0)
+                kd, sd = divmod(step - 1, model.G)
+                off = 64 * (kd + 1) + (28 if sd + 1 == 15 else 0) - (64 * K if adv_st else 0)
+                assert sd + 1 in (8, 15) and 0 <= off < 4096, ins
                 out.append(f"buffer_store_dword {REG[ins[2]]}, v0, %[rout], 0 offen offset:{off}")
             elif op == "inject":
                 # VCC = every lane but c, d of the conveyor quads: those take x (through the quad_perm), the others keep Zp
                 out.append(f"v_cndmask_b32_dpp {REG['Zp']}, {REG[ins[3]]}, {REG['Zp']}, vcc quad_perm:{INJECT_PERM[ins[2]]} {FULL}")
             elif op == "load":
-                out.append(f"buffer_load_dword {REG[ins[2]]}, v1, %[rin], 0 offen offset:{64 * (k + K)}")
+                off = 64 * ins[3] - (64 * K if adv_ld else 0)
+                assert 0 <= off < 4096, ins
+                out.append(f"buffer_load_dword {REG[ins[2]]}, v1, %[rin], 0 offen offset:{off}")
+            elif op == "hold":
+                out.append(f"v_mov_b32_e64 {REG[ins[2]]}, {REG[ins[3]]}")
             elif op == "wait":
                 out.append(f"s_waitcnt vmcnt({wait})")
             elif op == "nop4":
@@ -73,17 +90,19 @@ def loop_asm(K, fill=False):
             elif op == "nop":
                 if last and s == 11:
                     out.append("v_add_u32_e64 v1, v1, v9")
-                elif last and s == 12:
+                    adv_ld = True
+                elif last and s == s_adv_st:
                     out.append("v_add_u32_e64 v0, v0, v10")
+                    adv_st = True
                 else:
                     assert not fill, (k, s)
                     out.append("v_nop_e64")
     return out
 
 
-def gen_loop(K=model.K_DEFAULT, fill=False):
+def gen_loop(K=model.K_DEFAULT, fill=False, port=None):
     """the whole statement: VCC, the loop (%[cnt] counts up to 0), the wait for the last loads"""
-    return (["s_mov_b32 vcc_lo, -1", "s_mov_b32 vcc_hi, 0x3333ffff", ".p2align 5", "1:"] + loop_asm(K, fill) +
+    return (["s_mov_b32 vcc_lo, -1", "s_mov_b32 vcc_hi, 0x3333ffff", ".p2align 5", "1:"] + loop_asm(K, fill, port) +
             ["s_cbranch_scc0 1b", "s_waitcnt vmcnt(0)", "s_nop 1"])
 
 
@@ -98,9 +117,20 @@ def text(K=model.K_DEFAULT):
             "#ifdef OHS_EXPERIMENTS\n" + _macro("EQ_QUAD_RING_LOOP_FILL", gen_loop(K, fill=True)) + "#endif\n")
 
 
+def text_cl(K=model.K_DEFAULT, port=CL_PORT):
+    """eq_quad_ring_cl_asm.inc: the loop with the port's memory instructions in clusters"""
+    return ("// generated by tools/gen_eq_quad_ring_asm.py -- do not edit\n"
+            f"// the steady-state loop of eq_quad_ring_asm.inc with the port variant {port} of tools/model_eq_quad_ring.py:\n"
+            "// the group's stores and its load issue behind one another; holding registers from v20 on\n"
+            f"#define EQ_QUAD_RING_CL_HOLD {len({i[2] for g in range(K) for i in model.group_program(g, K, port=port) if i[0] == 'hold'})}\n"
+            + _macro("EQ_QUAD_RING_CL_LOOP", gen_loop(K, port=port)))
+
+
 if __name__ == "__main__":
     model.check_hazards(model.K_DEFAULT)
     model.check_hazards(model.K_DEFAULT, fill=True)
-    out = os.path.join(os.path.dirname(HERE), "open_headstage_amd", "csrc", "eq_quad_ring_asm.inc")
-    open(out, "w").write(text())
-    print("wrote", out)
+    model.check_hazards(model.K_DEFAULT, port=CL_PORT)
+    csrc = os.path.join(os.path.dirname(HERE), "open_headstage_amd", "csrc")
+    for name, t in (("eq_quad_ring_asm.inc", text()), ("eq_quad_ring_cl_asm.inc", text_cl())):
+        open(os.path.join(csrc, name), "w").write(t)
+        print("wrote", os.path.join(csrc, name))

@@ -38,6 +38,15 @@ input that does not exist is a zero).  Band k's state of the launch before goes 
 4k + 2, one step before its first sample's sums; it is taken out behind step n + 4k + 2, in which the band has filtered
 sample n - 1.  The ring runs on zeros until the last output has been stored.
 
+Where the port's memory instructions issue (group_program's `port`).  By default each of a group's two stores and its load
+stands alone in the slot of its step (8, 15; 10).  The cluster variants C1 / C2 / C3 issue them behind one another -- a
+vector-memory instruction alone between VALU instructions costs the wave about 8 ticks beyond its slot, one directly behind
+another next to nothing -- and change nothing else: a store waits in a holding register, the load
+issues up to 21 steps later, behind the inject B that consumed its register, with its deadline (the wait K - 1 groups on)
+unchanged.  In-place safety: stores only move LATER, and so does the load, which is requested K groups before its samples'
+outputs exist -- so a store never passes the load of the sample whose address it takes.  Ring(in_place=True) runs a launch
+on one array and refuses a load of an address that a store has written.
+
 hazards() walks the steady-state loop and gives, per DPP read, the distance in issue slots to the register's last VALU
 writer; check_hazards() fails below 2 (gfx9 / CDNA: two wait states between a VALU write and a DPP read of a VGPR).
 
@@ -85,28 +94,65 @@ def lane_constants(table):
     return c1, c2
 
 
-def group_program(g, K=K_DEFAULT, fill=False):
+PORTS = (None, "C1", "C2", "C3")    # where the port's three memory instructions issue (group_program)
+HOLD = ("H0", "H1", "H2")           # holding registers of the cluster variants: a parked store's value
+
+
+def _memory_slots(g, K, port):
+    """{s: instructions} of the slots of group g that carry the port's memory instructions, and of those the cluster
+    variants leave empty.  A parked store keeps the step its value belongs to: ("store", that step, holding register)."""
+    t = G * g
+    x, xb = f"x{g % K}", f"x{(g - 1) % K}"
+    if port is None:
+        return {8: [("store", t + 8, "Z0")], 10: [("load", t + 10, x, g + K)], 15: [("store", t + 15, "Z1")]}
+    if port == "C1":        # the load of the group before waits for this group's first store
+        return {8: [("store", t + 8, "Z0"), ("load", t + 8, xb, g - 1 + K)], 10: [], 15: [("store", t + 15, "Z1")]}
+    if port == "C2":        # one cluster per group: the first store's value waits in H0
+        return {8: [("hold", t + 8, "H0", "Z0")], 10: [],
+                15: [("store", t + 8, "H0"), ("store", t + 15, "Z1"), ("load", t + 15, x, g + K)]}
+    assert port == "C3" and K % 2 == 0, (port, K)
+    if g % 2 == 0:          # one cluster per two groups: the even group parks both of its values ...
+        return {8: [("hold", t + 8, "H0", "Z0")], 10: [], 15: [("hold", t + 15, "H1", "Z1")]}
+    return {8: [("hold", t + 8, "H2", "Z0")], 10: [],          # ... the odd one its first, and issues all six
+            15: [("store", t - 8, "H0"), ("store", t - 1, "H1"), ("store", t + 8, "H2"), ("store", t + 15, "Z1"),
+                 ("load", t + 15, xb, g - 1 + K), ("load", t + 15, x, g + K)] + ([("nop", t + 15)] if (g + 1) % K == 0 else [])}
+
+
+def group_program(g, K=K_DEFAULT, fill=False, port=None):
     """The instructions of group g (steps 16g + 1 .. 16g + 16) in issue order: (op, step, ...).  fill: a slot that carries
     nothing holds ("fill", step, "F") -- a VOP2+DPP instruction on a register F of its own, which keeps the vector unit for
     the step instruction's four cycles where a no-op lets a wave beside this one issue -- instead of ("nop", step).  (The
     experiments build's second loop; the product's has the no-ops: DESIGN.md 4.5, round 12.)  The two
-    slots of an iteration's last group that carry the loop's own offset advances (steps 11 and 12) stay ("nop", step)."""
+    slots of an iteration's last group that carry the loop's own offset advances (steps 11 and 12) stay ("nop", step).
+
+    port: where the two stores and the load issue.  None: each alone in the slot of its step (8, 10, 15).  The cluster
+    variants put them behind one another, because a vector-memory instruction that stands alone between VALU instructions
+    costs the wave about 12 cycles and one directly behind another about 4:
+        "C1"  the load waits for step 8's store (of the next group): a pair and a lone store, 82 slots per group
+        "C2"  step 8 parks Zc in the holding register H0 (("hold", step, "H0", Zc): a plain VALU move, no DPP, no hazard);
+              step 15 issues store H0, store Zc, load x back to back: 83 slots, one cluster per group
+        "C3"  groups in pairs (K even): the even group parks both values (H0, H1), the odd one its first (H2), and the odd
+              group's step 15 issues four stores and two loads: 167 slots per two groups; in an iteration's last group the
+              cluster is followed by the slot's ("nop", step): the store offsets' advance goes there, behind the stores
+    Nothing else moves: same ring, same lanes, same injects.  A load only moves LATER, to a slot behind the inject B (step 9
+    of its own or of the group before) that consumed its register, and its deadline -- the wait at step 14, K - 1 or K - 2
+    groups on -- stays; wait_count(K, port) is the wait's new vmcnt.  A store only moves LATER as well, so it never passes
+    the load of the sample whose place it takes (in place: an input is read K groups before it is injected, its output is
+    stored 64 samples behind that) -- tests/test_cpu_eq_quad_port_cluster.py runs the launch on one array.  No holding
+    register is live across the end of an iteration (K even), so the launch's C++ head and tail stay what they are."""
     prog = []
     own = (g + 1) % K == 0
+    mem = _memory_slots(g, K, port)
     for s in range(1, G + 1):
         step = G * g + s
         zc, zo = f"Z{step & 1}", f"Z{(step - 1) & 1}"
         prog += [("alpha", step, zc), ("delta", step, zo)]
-        if s == 8:
-            prog.append(("store", step, zc))
+        if mem.get(s):
+            prog += mem[s]
         elif s == 9:
             prog.append(("inject", step, "B", f"x{g % K}"))
-        elif s == 10:
-            prog.append(("load", step, f"x{g % K}", g + K))
         elif s == 14:
             prog += [("wait", step, f"x{(g + 1) % K}"), ("nop4", step)]
-        elif s == 15:
-            prog.append(("store", step, zc))
         elif s == 16:
             prog.append(("inject", step, "A", f"x{(g + 1) % K}"))
         elif fill and not (own and s in LOOP_OWN_SLOTS):
@@ -117,22 +163,32 @@ def group_program(g, K=K_DEFAULT, fill=False):
     return prog
 
 
-def wait_count(K=K_DEFAULT):
-    """vmcnt of a group's wait: the memory instructions issued behind the load it waits for (they retire in issue order)"""
-    prog = [i for g in range(0, K + 1) for i in group_program(g, K)]
-    at = max(j for j, i in enumerate(prog) if i[0] == "wait")
-    reg = prog[at][2]
-    ld = max(j for j, i in enumerate(prog[:at]) if i[0] == "load" and i[2] == reg)
-    return sum(1 for i in prog[ld + 1:at] if i[0] in ("load", "store"))
+def _program(g, K, fill=False, port=None):
+    """group_program with the arguments it had before `port` wherever the port is the default one"""
+    if port is not None:
+        return group_program(g, K, fill, port=port)
+    return group_program(g, K, True) if fill else group_program(g, K)
 
 
-def hazards(K=K_DEFAULT, extra=(), fill=False):
+def wait_count(K=K_DEFAULT, port=None):
+    """vmcnt of a group's wait: the memory instructions issued behind the load it waits for (they retire in issue order).
+    Where the groups of a pair differ (C3), the smaller count: it is right for one and waits a little longer in the other."""
+    prog = [i for g in range(0, 2 * K + 2) for i in _program(g, K, port=port)]
+    counts = []
+    for at in [j for j, i in enumerate(prog) if i[0] == "wait"][-2:]:
+        reg = prog[at][2]
+        ld = max(j for j, i in enumerate(prog[:at]) if i[0] == "load" and i[2] == reg)
+        counts.append(sum(1 for i in prog[ld + 1:at] if i[0] in ("load", "store")))
+    return min(counts)
+
+
+def hazards(K=K_DEFAULT, extra=(), fill=False, port=None):
     """(reader, step, register, distance) for every DPP read of the steady-state loop: distance = issue slots between the
     register's last VALU write and the read.  `extra`: instructions (op, dpp-read register, written register) put behind the
     last step of every K groups (the loop's own: offset advances, counter).  fill: the program with the fill instruction."""
     prog = []
     for g in range(2 * K, 4 * K):
-        prog += [i for i in (group_program(g, K, True) if fill else group_program(g, K)) if i[0] != "state"]
+        prog += [i for i in _program(g, K, fill, port) if i[0] != "state"]
         if (g + 1) % K == 0:
             prog += list(extra)
     last_write, out = {}, []
@@ -146,6 +202,7 @@ def hazards(K=K_DEFAULT, extra=(), fill=False):
         elif op == "inject": dpp_read, write = ins[3], "Zp"        # (x is written by a load: the wait covers it)
         elif op == "fill": dpp_read, write = ins[2], ins[2]
         elif op == "valu": dpp_read, write = ins[1], ins[2]
+        elif op == "hold": write = ins[2]                          # (a plain VALU read of Zc: no wait states needed)
         if dpp_read is not None and dpp_read in last_write and pos >= len(prog) // 2:     # (the second pass: all writers seen)
             out.append((op, ins[1], dpp_read, pos - last_write[dpp_read] - 1))
         if write is not None:
@@ -153,9 +210,9 @@ def hazards(K=K_DEFAULT, extra=(), fill=False):
     return out
 
 
-def check_hazards(K=K_DEFAULT, verbose=False, fill=False):
+def check_hazards(K=K_DEFAULT, verbose=False, fill=False, port=None):
     worst = {}
-    for op, step, reg, d in hazards(K, fill=fill):
+    for op, step, reg, d in hazards(K, fill=fill, port=port):
         key = (op, reg[:1] if reg.startswith("Z") and reg != "Zp" else reg)
         worst[key] = min(worst.get(key, 99), d)
     for (op, reg), d in sorted(worst.items()):
@@ -172,8 +229,8 @@ def _flush(v):
 class Ring:
     """the registers of one wave and the interpreter of group_program's instructions"""
 
-    def __init__(self, x, table, state=None, K=K_DEFAULT, mode=0):
-        self.x = np.asarray(x, F)
+    def __init__(self, x, table, state=None, K=K_DEFAULT, mode=0, in_place=False):
+        self.x = np.array(x, F)
         self.n = self.x.size
         tab = np.asarray(table, F).reshape(-1, 5)
         self.nb = tab.shape[0]
@@ -181,10 +238,12 @@ class Ring:
         self.K, self.mode = K, mode
         self.r = {k: np.zeros(LANES, F) for k in ["Z0", "Z1", "Zp", "G", "P"]}
         self.r["F"] = np.zeros(LANES, np.uint32)        # the fill's own register
+        self.r.update({h: np.zeros(LANES, F) for h in HOLD})
+        # in place the outputs go where the inputs are: load() then refuses an address that a store has written
+        self.y = self.x if in_place else np.zeros(self.n, F)
+        self.stored = np.zeros(self.n, np.int32)
         for g in range(-1, K - 1):
             self.r[f"x{g % K}"] = self.load(g)
-        self.y = np.zeros(self.n, F)
-        self.stored = np.zeros(self.n, np.int32)
         self.s_init = np.zeros((self.nb, 2), F) if state is None else np.asarray(state, F).reshape(self.nb, 2).copy()
         self.s_save = self.s_init.copy()
 
@@ -193,6 +252,7 @@ class Ring:
         ok = CONV & (i >= 0) & (i < self.n)
         v = np.zeros(LANES, F)
         v[ok] = self.x[i[ok]]
+        assert self.y is not self.x or not self.stored[i[ok]].any(), "an input is read after a store to its address"
         return v
 
     def op(self, f, a, b):
@@ -220,6 +280,8 @@ class Ring:
                 ok = STORE_LANES & (i >= 0) & (i < self.n)
                 self.y[i[ok]] = r[ins[2]][ok]
                 self.stored[i[ok]] += 1
+            elif o == "hold":
+                r[ins[2]] = r[ins[3]].copy()
             elif o == "inject":
                 r["Zp"] = np.where(INJECT_LANES, r[ins[3]][QP_INJECT[ins[2]]], r["Zp"]).astype(F)
             elif o == "load":
@@ -239,11 +301,13 @@ def n_groups(n):
     return (n + 62 + G - 1) // G
 
 
-def ring_eq(x, table, state=None, K=K_DEFAULT, mode=0, fill=False):
-    """One launch over x (float32 [n]) -> (y, new state [nb][2] = (s1, s2)); fill: the program with the fill instruction"""
-    ring = Ring(x, table, state, K, mode)
-    for g in range(-1, n_groups(ring.n)):
-        ring.run(group_program(g, K, True) if fill else group_program(g, K))
+def ring_eq(x, table, state=None, K=K_DEFAULT, mode=0, fill=False, port=None, in_place=False):
+    """One launch over x (float32 [n]) -> (y, new state [nb][2] = (s1, s2)); fill: the program with the fill instruction;
+    port: the whole launch in that variant's program (C3: to the end of a pair of groups); in_place: on one array"""
+    ring = Ring(x, table, state, K, mode, in_place)
+    last = n_groups(ring.n)
+    for g in range(-1, last + (last % 2 if port == "C3" else 0)):
+        ring.run(_program(g, K, fill, port))
     assert np.all(ring.stored == 1), "every output is stored exactly once"
     return ring.y, ring.s_save
 
@@ -365,9 +429,12 @@ def run_asm(lines, v, x, y, stored, n, iters):
                     y[i] = v[d][ok]
                     stored[i] += 1
                 else:
+                    assert y is not x or not stored[i].any(), "an input is read after a store to its address"
                     w = np.zeros(LANES, F)
                     w[ok] = x[i]
                     v[d] = w
+            elif op == "v_mov_b32_e64":         # a holding register of the cluster variants takes a value
+                v[int(t[1][1:])] = v[int(t[2][1:])].copy()
             elif op == "v_add_u32_e64":
                 d, a, b = (int(r[1:]) for r in t[1:4])
                 v[d] = (v[a] + v[b]).astype(np.uint32)
@@ -380,11 +447,13 @@ def run_asm(lines, v, x, y, stored, n, iters):
                 assert op in ("v_nop_e64", "s_waitcnt", "s_nop", "s_add_u32"), l
 
 
-def ring_eq_as_launched(x, table, state=None, lines=None, K=K_DEFAULT):
+def ring_eq_as_launched(x, table, state=None, lines=None, K=K_DEFAULT, port=None, in_place=False):
     """One launch with the structure of eq_quad_ring_wave: groups -1 .. g0 - 1 in the C++ form (inputs requested two groups
     ahead: xcur, xnext), whole iterations of K groups through run_asm on the generated text with the kernel's offsets, the
-    C++ form to the end.  -> (y, new state)"""
-    ring = Ring(x, table, state, K)
+    C++ form to the end.  -> (y, new state).  port: the variant `lines` were generated for (the C++ form is the default
+    program in any case: its holding registers start from whatever they hold and none is live behind an iteration);
+    in_place: inputs and outputs on one array, every load checked against the stores before it"""
+    ring = Ring(x, table, state, K, in_place=in_place)
     n = ring.n
     xcur, xnext = ring.load(-1), ring.load(0)
     g_hi = (n + 1) // G
@@ -421,6 +490,8 @@ def ring_eq_as_launched(x, table, state=None, lines=None, K=K_DEFAULT):
              11: xcur, 12: xnext}
         for k in range(2, K):
             v[11 + k] = xa[k]
+        if port is not None:                # (holding registers: never read before the loop has written them)
+            v.update({20 + k: np.full(LANES, np.nan, F) for k in range(len(HOLD))})
         run_asm(lines, v, ring.x, ring.y, ring.stored, n, iters)
         r["Z0"], r["Z1"], r["Zp"], r["G"], r["P"] = v[2], v[3], v[4], v[5], v[6]
         xcur, xnext = v[11], v[12]

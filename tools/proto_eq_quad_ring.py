@@ -14,6 +14,13 @@ per 16 samples = 5.06 per sample against the wave ring's 6.02 + port.  It builds
 Head and tail of a launch and the state hand-over are the product's business: every chain has 96 zeros in front of its first
 sample in both buffers (the ring starts from zero at group 5, one group before the first sample, exactly as the model starts
 at group -1), and its length is a multiple of 16 K.
+
+PROTO_VARIANT selects the loop, every one generated from the model's instruction list (tools/bin/proto_eq_quad_ring_<variant>):
+    cur (default)   the product's loop of round 12: each of a group's three memory instructions alone in its slot
+    nost / nold / nomem   attribution knock-outs: the stores / the load / all three replaced by v_nop -- the outputs are wrong
+                    by construction, so these skip the bit check and only time (what does the port cost the loop?)
+    C1 / C2 / C3    the cluster variants of the model's group_program(port=...): bit check and timing as for cur
+tools/ab_proto_eq_quad_port.sh runs them alternating in one call; profiles/r15_proto_eq_quad_port.txt is its table.
 """
 import os
 import subprocess
@@ -27,11 +34,17 @@ K = int(os.environ.get("PROTO_K", str(model.K_DEFAULT)))
 import gen_eq_quad_ring_asm as gen    # noqa: E402  (tools/ is on sys.path: this script's directory)
 
 loop_asm = gen.loop_asm
+VARIANT = os.environ.get("PROTO_VARIANT", "cur")
+KNOCK_OUT = {"nost": ("buffer_store_dword",), "nold": ("buffer_load_dword",), "nomem": ("buffer_store_dword", "buffer_load_dword")}
+assert VARIANT == "cur" or VARIANT in KNOCK_OUT or VARIANT in model.PORTS, VARIANT
 
 
 def main():
-    model.check_hazards(K)
-    body = gen.gen_loop(K)
+    port = VARIANT if VARIANT in model.PORTS else None
+    model.check_hazards(K, port=port)
+    body = gen.gen_loop(K, port=port)
+    # (a knock-out keeps the slot: v_nop is the 8-byte encoding the loop has wherever a slot carries nothing)
+    body = ["v_nop_e64" if l.startswith(KNOCK_OUT.get(VARIANT, ())) else l for l in body]
     slots = sum(1 for l in body if not l.startswith((".", "1:"))) - 4
     asm = "\n".join('        "' + l + '\\n"' for l in body)
     xdecl = "\n".join(f"    float x{k} = conv ? src[base + 16 * (G0 + {k}) + xs] : 0.0f;" for k in range(K))
@@ -44,6 +57,7 @@ def main():
 #include <vector>
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int NB = 10, K = %(K)d, G0 = 5, PAD = 16 * (G0 + 1);
+constexpr bool CHECK = %(check)d;       // (a knock-out variant's outputs are wrong by construction)
 // raw buffer resource over `bytes` bytes (stride 0, DATA_FORMAT 32)
 __device__ u32x4 rsrc(const void *p, unsigned bytes)
 {
@@ -86,7 +100,7 @@ __global__ __launch_bounds__(64) void k(const float *src, float *dst, long long 
         : [Z0] "+{v2}"(Z0), [Z1] "+{v3}"(Z1), [Zp] "+{v4}"(Zp), [Gr] "+{v5}"(Gr), [P] "+{v6}"(P), [vs] "+{v0}"(voff_st),
           [vl] "+{v1}"(voff_ld), %(xops)s, [cnt] "+s"(cnt)
         : [C1] "{v7}"(C1), [C2] "{v8}"(C2), [incl] "{v9}"(inc_ld), [incs] "{v10}"(inc_st), [rin] "s"(rin), [rout] "s"(rout)
-        : "memory", "scc", "vcc");
+        : "memory", "scc", "vcc", "v20", "v21", "v22");
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
     if (lane == 0 && ticks) ticks[blockIdx.x] = t1 - t0;
 }
@@ -138,11 +152,13 @@ int main()
         if (hipEventSynchronize(e1) != hipSuccess) { printf("kernel failed: %%s\n", hipGetErrorString(hipGetLastError())); return 1; }
         float ms; hipEventElapsedTime(&ms, e0, e1);
         if (rep) best = ms < best ? ms : best;
+        if (rep) printf("rep %%d: %%.4f ms\n", rep, ms);
     }
     std::vector<float> hy(hx.size());
     hipMemcpy(hy.data(), dy, hy.size() * 4, hipMemcpyDeviceToHost);
     int bad_total = 0;
     for (int ch : {0, 1, 511}) {
+        if (!CHECK) { printf("chain %%3d: not checked (knock-out variant)\n", ch); continue; }
         std::vector<float> y;
         host_cascade(c, &hx[(size_t)ch * stride + PAD], (size_t)n, y);
         long long bad = 0, untouched = 0;
@@ -157,7 +173,7 @@ int main()
         printf("chain %%3d: %%lld of %%lld samples differ from the host's DF2T cascade (%%lld never written, %%lld stray stores)\n", ch, bad, n, untouched, stray);
         bad_total += bad != 0 || stray != 0;
     }
-    printf("512 chains x %%lld samples, one chain per wave: %%.3f ms = %%.2f ns per sample  (%%d issue slots per %%d samples = %%.3f per sample)\n",
+    printf("variant %(variant)s: 512 chains x %%lld samples, one chain per wave: %%.3f ms = %%.2f ns per sample  (%%d issue slots per %%d samples = %%.3f per sample)\n",
            total, best, best * 1e6 / (double)total, %(slots)d, 16 * K, %(slots)d / (double)(16 * K));
     hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, 0, dx, dy, stride, iters, c, dt);
     hipDeviceSynchronize();
@@ -165,13 +181,14 @@ int main()
     printf("a lone wave: %%.3f s_memtime ticks per sample\n", (double)tk / (double)total);
     return bad_total ? 2 : 0;
 }
-''' % {"K": K, "asm": asm, "xdecl": xdecl, "xops": xops, "slots": slots}
-    path = "/tmp/proto_eq_quad_ring.hip"
+''' % {"K": K, "asm": asm, "xdecl": xdecl, "xops": xops, "slots": slots, "check": int(VARIANT not in KNOCK_OUT), "variant": VARIANT}
+    tag = ("" if VARIANT == "cur" else "_" + VARIANT) + ("" if K == model.K_DEFAULT else f"_k{K}")
+    path = f"/tmp/proto_eq_quad_ring{tag}.hip"
     open(path, "w").write(src)
     os.makedirs(os.path.join(HERE, "bin"), exist_ok=True)
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-w", "-ffp-contract=off", "--offload-arch=gfx950", "-o",
-                    os.path.join(HERE, "bin", "proto_eq_quad_ring" + ("" if K == model.K_DEFAULT else f"_k{K}")), path], check=True)
-    print(f"built tools/bin/proto_eq_quad_ring (K = {K}); {slots} issue slots per {16 * K} samples")
+                    os.path.join(HERE, "bin", "proto_eq_quad_ring" + tag), path], check=True)
+    print(f"built tools/bin/proto_eq_quad_ring{tag} (K = {K}, {VARIANT}); {slots} issue slots per {16 * K} samples")
 
 
 if __name__ == "__main__":
