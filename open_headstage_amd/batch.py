@@ -23,6 +23,71 @@ LAYOUT_7_1 = (("L", -30.0, 0.0), ("R", 30.0, 0.0), ("C", 0.0, 0.0), ("LFE", 0.0,
               ("Ls", -90.0, 0.0), ("Rs", 90.0, 0.0))
 
 
+def _stereo_io(proc, x, out, hip_stream):
+    """The tensor wrappers' checks of x / out [streams, 2, frames] -> (out, hip_stream, frames); out None: a fresh tensor, hip_stream
+    None: torch's current stream on x's device."""
+    import torch
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+        raise TypeError("x must be a contiguous float32 CUDA tensor [streams, 2, frames]")
+    S, ch, frames = x.shape
+    if S != proc.n_streams or ch != 2 or frames % BLOCK_SIZE:
+        raise ValueError(f"expected [{proc.n_streams}, 2, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
+    if x.device.index != proc.device:
+        raise ValueError("tensor is on a different device than the BatchProcessor")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must match x")
+    if hip_stream is None:
+        hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+    return out, hip_stream, frames
+
+
+def _layout_io(proc, x, K, out, hip_stream):
+    """The same for the layout calls: x [streams, >= K, frames], out [streams, 2, frames] -> (out, hip_stream, frames)"""
+    import torch
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+        raise TypeError("x must be a contiguous float32 CUDA tensor [streams, channels, frames]")
+    S, ch, frames = x.shape
+    if S != proc.n_streams or frames % BLOCK_SIZE or ch < K:
+        raise ValueError(f"expected [{proc.n_streams}, >= {K}, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
+    if x.device.index != proc.device:
+        raise ValueError("tensor is on a different device than the BatchProcessor")
+    if out is None:
+        out = torch.empty((S, 2, frames), dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (S, 2, frames) or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous [streams, 2, frames] tensor on x's device")
+    if hip_stream is None:
+        hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+    return out, hip_stream, frames
+
+
+def _index_rows(a, n_streams, n_segs, what, dtype):
+    """A schedule's rows -> (contiguous array, row stride for the C call): [>= n_segs] is one row for all streams (stride 0),
+    [n_streams][>= n_segs] a row per stream (stride = the row length)."""
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.ndim == 1:
+        if a.size < n_segs:
+            raise ValueError(f"{what} needs {n_segs} entries")
+        return a, 0
+    if a.ndim != 2 or a.shape[0] != n_streams or a.shape[1] < n_segs:
+        raise ValueError(f"{what}: expected [{n_streams}][>= {n_segs}] or [>= {n_segs}], got {a.shape}")
+    return a, int(a.shape[1])
+
+
+def _prev_rows(prev, n_streams, stride, what):
+    """The sets in front of a call's first block, beside rows of _index_rows' `stride`: one entry per row -> the uint32 array"""
+    pv = np.ascontiguousarray(prev, dtype=np.uint32).reshape(-1)
+    if pv.size != (n_streams if stride else 1):
+        raise ValueError(f"{what}: expected {n_streams if stride else 1} entries, got {pv.size}")
+    return pv
+
+
+def _n_segs(n_blocks, seg_blocks):
+    return -(-int(n_blocks) // int(seg_blocks)) if seg_blocks else 0
+
+
+
 class BatchProcessor:
     def __init__(self, n_streams: int, num_bands: int = 10, device: int = 0, library=None):
         """library: the CDLL the handle lives in (default: the product library; _ffi.experiments_lib() for plan
@@ -154,7 +219,7 @@ class BatchProcessor:
                               seg_blocks: int, table_idx=None, gains=None, hip_stream: int = 0) -> None:
         """ohs_batch_process_scheduled: segment k = blocks [k seg_blocks, (k + 1) seg_blocks) of the call is filtered with table
         table_idx[k] (set_schedule_tables) and leaves with gain gains[k]; None = the handle's table / gain throughout"""
-        n_segs = -(-int(n_blocks) // int(seg_blocks)) if seg_blocks else 0
+        n_segs = _n_segs(n_blocks, seg_blocks)
         t = g = None
         if table_idx is not None:
             t = np.ascontiguousarray(table_idx, dtype=np.uint32).ravel()
@@ -172,20 +237,7 @@ class BatchProcessor:
     def process_scheduled(self, x, seg_blocks: int, table_idx=None, gains=None, out=None, hip_stream: int | None = None):
         """process() with a schedule of EQ tables and gains, one entry per segment of seg_blocks * 512 frames: what the reference
         does when its host refreshes the bands and the master gain in front of every block.  x, out as in process()."""
-        import torch
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
-            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, 2, frames]")
-        S, ch, frames = x.shape
-        if S != self.n_streams or ch != 2 or frames % BLOCK_SIZE:
-            raise ValueError(f"expected [{self.n_streams}, 2, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
-        if x.device.index != self.device:
-            raise ValueError("tensor is on a different device than the BatchProcessor")
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
-            raise ValueError("out must match x")
-        if hip_stream is None:
-            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+        out, hip_stream, frames = _stereo_io(self, x, out, hip_stream)
         self.process_scheduled_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, 2 * frames, frames, seg_blocks,
                                    table_idx, gains, hip_stream)
         return out
@@ -195,22 +247,9 @@ class BatchProcessor:
         """ohs_batch_process_scheduled_streams: a schedule per stream.  table_idx [n_streams][n_segs] (or [n_segs]: one row for
         all streams), likewise gains; stream s filters segment k with table table_idx[s][k] and leaves with gains[s][k].  None =
         the handle's table(s) / gain throughout.  The handle's own table(s) and gain are unchanged by the call."""
-        n_segs = -(-int(n_blocks) // int(seg_blocks)) if seg_blocks else 0
-
-        def rows(a, dtype, what):
-            if a is None:
-                return None, 0
-            a = np.ascontiguousarray(a, dtype=dtype)
-            if a.ndim == 1:
-                if a.size < n_segs:
-                    raise ValueError(f"{what} needs {n_segs} entries")
-                return a, 0
-            if a.ndim != 2 or a.shape[0] != self.n_streams or a.shape[1] < n_segs:
-                raise ValueError(f"{what}: expected [{self.n_streams}][>= {n_segs}] or [>= {n_segs}], got {a.shape}")
-            return a, int(a.shape[1])
-
-        t, ts = rows(table_idx, np.uint32, "table_idx")
-        g, gs = rows(gains, np.float32, "gains")
+        n_segs = _n_segs(n_blocks, seg_blocks)
+        t, ts = (None, 0) if table_idx is None else _index_rows(table_idx, self.n_streams, n_segs, "table_idx", np.uint32)
+        g, gs = (None, 0) if gains is None else _index_rows(gains, self.n_streams, n_segs, "gains", np.float32)
         self._check(self._lib.ohs_batch_process_scheduled_streams(
             self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(stream_stride), int(channel_stride), int(seg_blocks),
             t.ctypes.data_as(C.POINTER(C.c_uint32)) if t is not None else None, ts,
@@ -219,20 +258,7 @@ class BatchProcessor:
     def process_scheduled_streams(self, x, seg_blocks: int, table_idx=None, gains=None, out=None, hip_stream: int | None = None):
         """process() with a schedule of EQ tables and gains per stream and segment of seg_blocks * 512 frames: every stream a
         plugin instance whose host refreshes its bands and its master gain in front of every block.  x, out as in process()."""
-        import torch
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
-            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, 2, frames]")
-        S, ch, frames = x.shape
-        if S != self.n_streams or ch != 2 or frames % BLOCK_SIZE:
-            raise ValueError(f"expected [{self.n_streams}, 2, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
-        if x.device.index != self.device:
-            raise ValueError("tensor is on a different device than the BatchProcessor")
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
-            raise ValueError("out must match x")
-        if hip_stream is None:
-            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+        out, hip_stream, frames = _stereo_io(self, x, out, hip_stream)
         self.process_scheduled_streams_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, 2 * frames, frames, seg_blocks,
                                            table_idx, gains, hip_stream)
         return out
@@ -282,18 +308,10 @@ class BatchProcessor:
         """ohs_batch_process_ir_scheduled: stream s convolves segment k = blocks [k seg_blocks, (k + 1) seg_blocks) of the call
         with set ir_idx[s][k] (set_schedule_irs); a 1-D ir_idx is one row for all streams.  mode: "ring_out" (the old response's
         tail rings out under the new one) or "cut" (the reference's set_ir: it is cut off), or the C constants 0 / 1."""
-        n_segs = -(-int(n_blocks) // int(seg_blocks)) if seg_blocks else 0
+        n_segs = _n_segs(n_blocks, seg_blocks)
         if ir_idx is None:
             raise ValueError("ir_idx is required")
-        a = np.ascontiguousarray(ir_idx, dtype=np.uint32)
-        if a.ndim == 1:
-            if a.size < n_segs:
-                raise ValueError(f"ir_idx needs {n_segs} entries")
-            stride = 0
-        elif a.ndim == 2 and a.shape[0] == self.n_streams and a.shape[1] >= n_segs:
-            stride = int(a.shape[1])
-        else:
-            raise ValueError(f"ir_idx: expected [{self.n_streams}][>= {n_segs}] or [>= {n_segs}], got {a.shape}")
+        a, stride = _index_rows(ir_idx, self.n_streams, n_segs, "ir_idx", np.uint32)
         m = self.IR_SWITCH[mode] if isinstance(mode, str) else int(mode)
         self._check(self._lib.ohs_batch_process_ir_scheduled(
             self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(stream_stride), int(channel_stride), int(seg_blocks),
@@ -301,20 +319,7 @@ class BatchProcessor:
 
     def process_ir_scheduled(self, x, seg_blocks: int, ir_idx, mode="ring_out", out=None, hip_stream: int | None = None):
         """process() with a schedule of HRIR sets per stream and segment of seg_blocks * 512 frames.  x, out as in process()."""
-        import torch
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
-            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, 2, frames]")
-        S, ch, frames = x.shape
-        if S != self.n_streams or ch != 2 or frames % BLOCK_SIZE:
-            raise ValueError(f"expected [{self.n_streams}, 2, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
-        if x.device.index != self.device:
-            raise ValueError("tensor is on a different device than the BatchProcessor")
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
-            raise ValueError("out must match x")
-        if hip_stream is None:
-            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+        out, hip_stream, frames = _stereo_io(self, x, out, hip_stream)
         self.process_ir_scheduled_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, 2 * frames, frames, seg_blocks,
                                       ir_idx, mode, hip_stream)
         return out
@@ -366,22 +371,8 @@ class BatchProcessor:
         """x: contiguous float32 device tensor [streams, K, frames], frames a multiple of 512 -> [streams, 2, frames]:
         gain * sum over channels of conv(h[c][ear], x[:, c]), then the handle's EQ on the two ears if it is enabled.
         K is the layout's channel count; x may hold MORE channels than that -- the surplus is never read."""
-        import torch
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
-            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, channels, frames]")
-        S, ch, frames = x.shape
-        K = self._layout_k
-        if S != self.n_streams or frames % BLOCK_SIZE or ch < K:
-            raise ValueError(f"expected [{self.n_streams}, >= {K}, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
-        if x.device.index != self.device:
-            raise ValueError("tensor is on a different device than the BatchProcessor")
-        if out is None:
-            out = torch.empty((S, 2, frames), dtype=x.dtype, device=x.device)
-        elif tuple(out.shape) != (S, 2, frames) or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
-            raise ValueError("out must be a contiguous [streams, 2, frames] tensor on x's device")
-        if hip_stream is None:
-            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
-        self.process_layout_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, ch * frames, frames, 2 * frames, frames,
+        out, hip_stream, frames = _layout_io(self, x, self._layout_k, out, hip_stream)
+        self.process_layout_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, x.shape[1] * frames, frames, 2 * frames, frames,
                                 hip_stream)
         return out
 
@@ -426,24 +417,12 @@ class BatchProcessor:
         """ohs_batch_process_layout_scheduled: process_layout_ptr with a set of the table per stream and segment of seg_blocks
         blocks.  idx: [n_segs] for all streams or [n_streams][n_segs]; prev: the set in front of the call's first block -- a scalar
         for a 1-D idx, [n_streams] for rows per stream --, or None: the call's start is no boundary (read when crossfade only)."""
-        n_segs = -(-int(n_blocks) // int(seg_blocks)) if seg_blocks else 0
+        n_segs = _n_segs(n_blocks, seg_blocks)
         if idx is None:
             raise ValueError("idx is required")
-        a = np.ascontiguousarray(idx, dtype=np.uint32)
-        if a.ndim == 1:
-            if a.size < n_segs:
-                raise ValueError(f"idx needs {n_segs} entries")
-            stride = 0
-        elif a.ndim == 2 and a.shape[0] == self.n_streams and a.shape[1] >= n_segs:
-            stride = int(a.shape[1])
-        else:
-            raise ValueError(f"idx: expected [{self.n_streams}][>= {n_segs}] or [>= {n_segs}], got {a.shape}")
-        pp = None
-        if prev is not None:
-            pv = np.ascontiguousarray(prev, dtype=np.uint32).reshape(-1)
-            if pv.size != (self.n_streams if stride else 1):
-                raise ValueError(f"prev: expected {self.n_streams if stride else 1} entries, got {pv.size}")
-            pp = pv.ctypes.data_as(C.POINTER(C.c_uint32))
+        a, stride = _index_rows(idx, self.n_streams, n_segs, "idx", np.uint32)
+        pv = None if prev is None else _prev_rows(prev, self.n_streams, stride, "prev")
+        pp = None if pv is None else pv.ctypes.data_as(C.POINTER(C.c_uint32))
         self._check(self._lib.ohs_batch_process_layout_scheduled(
             self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(in_stream_stride), int(in_channel_stride),
             int(out_stream_stride), int(out_channel_stride), int(seg_blocks), a.ctypes.data_as(C.POINTER(C.c_uint32)), stride, pp,
@@ -454,22 +433,8 @@ class BatchProcessor:
         """process_layout() with a set of the table per stream and segment of seg_blocks * 512 frames; crossfade: fade from the old
         set to the new one over the first block of every segment that changes the set (False: the old set's tail rings out).
         x, out as in process_layout(); K is the table's channel count."""
-        import torch
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
-            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, channels, frames]")
-        S, ch, frames = x.shape
-        K = self._table_k
-        if S != self.n_streams or frames % BLOCK_SIZE or ch < K:
-            raise ValueError(f"expected [{self.n_streams}, >= {K}, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
-        if x.device.index != self.device:
-            raise ValueError("tensor is on a different device than the BatchProcessor")
-        if out is None:
-            out = torch.empty((S, 2, frames), dtype=x.dtype, device=x.device)
-        elif tuple(out.shape) != (S, 2, frames) or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
-            raise ValueError("out must be a contiguous [streams, 2, frames] tensor on x's device")
-        if hip_stream is None:
-            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
-        self.process_layout_scheduled_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, ch * frames, frames, 2 * frames,
+        out, hip_stream, frames = _layout_io(self, x, self._table_k, out, hip_stream)
+        self.process_layout_scheduled_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, x.shape[1] * frames, frames, 2 * frames,
                                           frames, seg_blocks, idx, prev, crossfade, hip_stream)
         return out
 
@@ -484,24 +449,12 @@ class BatchProcessor:
         """ohs_batch_process_ir_crossfaded: process_ir_scheduled_ptr's rows, with a crossfade from the old set to the new one over
         the first block of every segment whose set differs from the one in front of it.  prev_idx: the set in front of the call's
         first block -- a scalar for a 1-D ir_idx, [n_streams] for rows per stream --, or None: the call's start is no boundary."""
-        n_segs = -(-int(n_blocks) // int(seg_blocks)) if seg_blocks else 0
+        n_segs = _n_segs(n_blocks, seg_blocks)
         if ir_idx is None:
             raise ValueError("ir_idx is required")
-        a = np.ascontiguousarray(ir_idx, dtype=np.uint32)
-        if a.ndim == 1:
-            if a.size < n_segs:
-                raise ValueError(f"ir_idx needs {n_segs} entries")
-            stride = 0
-        elif a.ndim == 2 and a.shape[0] == self.n_streams and a.shape[1] >= n_segs:
-            stride = int(a.shape[1])
-        else:
-            raise ValueError(f"ir_idx: expected [{self.n_streams}][>= {n_segs}] or [>= {n_segs}], got {a.shape}")
-        pp = None
-        if prev_idx is not None:
-            pv = np.ascontiguousarray(prev_idx, dtype=np.uint32).reshape(-1)
-            if pv.size != (self.n_streams if stride else 1):
-                raise ValueError(f"prev_idx: expected {self.n_streams if stride else 1} entries, got {pv.size}")
-            pp = pv.ctypes.data_as(C.POINTER(C.c_uint32))
+        a, stride = _index_rows(ir_idx, self.n_streams, n_segs, "ir_idx", np.uint32)
+        pv = None if prev_idx is None else _prev_rows(prev_idx, self.n_streams, stride, "prev_idx")
+        pp = None if pv is None else pv.ctypes.data_as(C.POINTER(C.c_uint32))
         self._check(self._lib.ohs_batch_process_ir_crossfaded(
             self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(stream_stride), int(channel_stride), int(seg_blocks),
             a.ctypes.data_as(C.POINTER(C.c_uint32)), stride, pp, C.c_void_p(hip_stream) if hip_stream else None))
@@ -509,20 +462,7 @@ class BatchProcessor:
     def process_ir_crossfaded(self, x, seg_blocks: int, ir_idx, prev_idx=None, out=None, hip_stream: int | None = None):
         """process() with a schedule of HRIR sets per stream and segment of seg_blocks * 512 frames, crossfaded over the first
         block of every segment that changes the set.  x, out as in process()."""
-        import torch
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
-            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, 2, frames]")
-        S, ch, frames = x.shape
-        if S != self.n_streams or ch != 2 or frames % BLOCK_SIZE:
-            raise ValueError(f"expected [{self.n_streams}, 2, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
-        if x.device.index != self.device:
-            raise ValueError("tensor is on a different device than the BatchProcessor")
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
-            raise ValueError("out must match x")
-        if hip_stream is None:
-            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+        out, hip_stream, frames = _stereo_io(self, x, out, hip_stream)
         self.process_ir_crossfaded_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, 2 * frames, frames, seg_blocks,
                                        ir_idx, prev_idx, hip_stream)
         return out
@@ -537,20 +477,7 @@ class BatchProcessor:
     def process(self, x, out=None, hip_stream: int | None = None, deferred: bool = False):
         """x, out: torch.float32 CUDA tensors [n_streams, 2, frames], frames % 512 == 0.
         deferred=True: `out` is complete on the stream only after join() / sync() (ohs_batch_process_deferred)."""
-        import torch
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
-            raise TypeError("x must be a contiguous float32 CUDA tensor [streams, 2, frames]")
-        S, ch, frames = x.shape
-        if S != self.n_streams or ch != 2 or frames % BLOCK_SIZE:
-            raise ValueError(f"expected [{self.n_streams}, 2, k*{BLOCK_SIZE}], got {tuple(x.shape)}")
-        if x.device.index != self.device:
-            raise ValueError("tensor is on a different device than the BatchProcessor")
-        if out is None:
-            out = torch.empty_like(x)
-        elif out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
-            raise ValueError("out must match x")
-        if hip_stream is None:
-            hip_stream = torch.cuda.current_stream(x.device).cuda_stream
+        out, hip_stream, frames = _stereo_io(self, x, out, hip_stream)
         self.process_ptr(x.data_ptr(), out.data_ptr(), frames // BLOCK_SIZE, 2 * frames, frames,
                          hip_stream, deferred)
         return out

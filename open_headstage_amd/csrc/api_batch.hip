@@ -2,10 +2,14 @@
 // many-stream job of BASELINE.json's north_star): EQ || convolution over time chunks on two streams, the deferred form,
 // the PCIe-fed host pipeline, per-kernel profiling, fail-closed error handling.
 #include "api_internal.h"
+#include "sched_rows.h"
 
 using namespace ohs;
 using namespace ohs_api;
 using ohs_host::rbj;
+using ohs_host::sched_row_constant;
+using ohs_host::sched_rows_equal;
+using ohs_host::sched_segments;
 
 extern "C" {
 
@@ -242,6 +246,36 @@ int ohs_batch_reset(ohs_batch *b)
     return OHS_OK;
 }
 
+// ---- what the processing entry points share -----------------------------------------------------------------------
+// [S][2][frames] fits its strides: the channels inside a stream's stride, or the streams inside a channel's
+static bool batch_strides_ok(size_t S, size_t ss, size_t cs, size_t frames)
+{
+    return cs >= frames && (S <= 1 || ss >= 2 * frames || ss >= cs + frames);
+}
+
+static int batch_refuse_failed(const ohs_batch *b)
+{
+    return fail(OHS_ERR_HIP, "this batch failed in the middle of an earlier call (" + b->fail_msg +
+                                 "): its per-stream state is half-advanced; ohs_batch_reset starts it afresh");
+}
+
+// A HIP call failed (rc, its message in g_err) with part of a processing call queued: some of the work has advanced the per-stream
+// state, the rest has not.  Every later processing call is refused until ohs_batch_reset.
+static int batch_mark_failed(ohs_batch *b, int rc)
+{
+    const std::string why = g_err;
+    b->failed = true;
+    b->fail_msg = why;
+    return fail(rc, why);
+}
+
+// the handle's EQ table becomes schedule table t (what the setters do)
+static void batch_adopt_table(ohs_batch *b, size_t t)
+{
+    for (size_t band = 0; band < b->eq.nb; ++band)
+        eq_set_shared_band(b->eq, band, &b->eq.sched_coeffs[(t * b->eq.nb + band) * 5], b->eq.sched_en[t * b->eq.nb + band]);
+}
+
 static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
                               size_t stream_stride, size_t channel_stride, void *hip_stream, bool deferred,
                               const BatchSchedule *sc, const ConvIrs *irs);
@@ -253,14 +287,11 @@ static int batch_process_impl(ohs_batch *b, const float *d_in, float *d_out, siz
                               const BatchSchedule *sc = nullptr, const ConvIrs *irs = nullptr)
 {
     if (!b || !d_in || !d_out) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
-    if (b->failed)
-        return fail(OHS_ERR_HIP, "this batch failed in the middle of an earlier call (" + b->fail_msg +
-                                     "): its per-stream state is half-advanced; ohs_batch_reset starts it afresh");
+    if (b->failed) return batch_refuse_failed(b);
     const size_t spans_before = b->spans.size();
     const int rc = batch_process_body(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, deferred, sc, irs);
     if (rc == OHS_OK || rc == OHS_ERR_INVALID_ARG) return rc;      // (argument errors are found before anything is queued)
-    // A HIP call failed with part of the work queued.  Keep the message, then leave nothing dangling:
-    const std::string why = g_err;
+    // A HIP call failed with part of the work queued.  Leave nothing dangling (none of this touches the message):
     //  * the caller's stream must not run ahead of what this call put on the second stream
     hipStream_t st = (hipStream_t)hip_stream;
     hipEvent_t ev = nullptr;
@@ -281,9 +312,7 @@ static int batch_process_impl(ohs_batch *b, const float *d_in, float *d_out, siz
         if (sp.b) hipEventDestroy(sp.b);
     }
     //  * some time chunks have advanced the per-stream state, others have not
-    b->failed = true;
-    b->fail_msg = why;
-    return fail(rc, why);
+    return batch_mark_failed(b, rc);
 }
 
 static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
@@ -292,8 +321,7 @@ static int batch_process_body(ohs_batch *b, const float *d_in, float *d_out, siz
 {
     if (n_blocks == 0) return OHS_OK;
     if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
-    const size_t frames = n_blocks * BS;
-    if (channel_stride < frames || (b->conv.S > 1 && stream_stride < 2 * frames && stream_stride < channel_stride + frames))
+    if (!batch_strides_ok(b->conv.S, stream_stride, channel_stride, n_blocks * BS))
         return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)hip_stream;
@@ -504,6 +532,70 @@ int ohs_batch_last_eq_form(const ohs_batch *b, int *form, int *scheduled)
     return OHS_OK;
 }
 
+// ---- the staging slots of the scheduled calls ---------------------------------------------------------------------
+// A scheduled call's rows travel through the next of the handle's kSchedSlots staging slots (pinned host memory: the caller's
+// arrays are free on return, the copy to the device is asynchronous).  The lease closes the slot on every path out of the call
+// that took it: `done` recorded behind whatever the call queued on its stream, waited for before the slot is filled again.
+struct SchedLease {
+    ohs_batch::SchedSlot *slot = nullptr;
+    hipStream_t st = nullptr;
+    SchedLease() = default;
+    SchedLease(const SchedLease &) = delete;
+    SchedLease &operator=(const SchedLease &) = delete;
+    ~SchedLease()
+    {
+        if (!slot) return;
+        if (hipEventRecord(slot->done, st) == hipSuccess) slot->in_use = true;
+        else hipStreamSynchronize(st);
+    }
+};
+
+// the next slot, free of its last user and with room for n_entries 32-bit entries
+static int sched_lease(ohs_batch *b, size_t n_entries, hipStream_t st, SchedLease &lease)
+{
+    ohs_batch::SchedSlot &slot = b->sched_slot[b->sched_next];
+    b->sched_next = (b->sched_next + 1) % ohs_batch::kSchedSlots;
+    if (slot.in_use) HIP_TRY(hipEventSynchronize(slot.done));
+    slot.in_use = false;
+    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    lease.slot = &slot; lease.st = st;
+    if (slot.cap < n_entries) {
+        if (slot.h) hipHostFree(slot.h);
+        if (slot.d) {
+            DeviceWideSection dws;
+            hipFree(slot.d);
+        }
+        slot.h = nullptr; slot.d = nullptr; slot.cap = 0;
+        const size_t cap = std::max<size_t>(2048, n_entries + n_entries / 2);
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&slot.h), cap * sizeof(unsigned), hipHostMallocDefault));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&slot.d), cap * sizeof(unsigned)));
+        slot.cap = cap;
+    }
+    return OHS_OK;
+}
+
+// `rows` rows of n 32-bit entries (table indices, gains), read `stride` entries apart; src NULL: nothing
+struct SchedRows {
+    const void *src;
+    size_t stride, rows, n;
+    size_t entries() const { return src ? rows * n : 0; }
+};
+
+// Two arrays of rows into a slot, each packed n apart whatever the caller's stride and the second right behind the first, and ONE
+// copy to the device on st.  -> lease.slot->d: the first array, the second first.entries() behind it.
+static int sched_stage(ohs_batch *b, const SchedRows &first, const SchedRows &second, hipStream_t st, SchedLease &lease)
+{
+    const size_t n_first = first.entries(), n_all = n_first + second.entries();
+    const int rc = sched_lease(b, n_all, st, lease);
+    if (rc) return rc;
+    unsigned *h = lease.slot->h;
+    for (const SchedRows *a : {&first, &second})
+        for (size_t r = 0; a->src && r < a->rows; ++r, h += a->n)
+            std::memcpy(h, static_cast<const unsigned *>(a->src) + r * a->stride, a->n * sizeof(unsigned));
+    HIP_TRY(hipMemcpyAsync(lease.slot->d, lease.slot->h, n_all * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    return OHS_OK;
+}
+
 int ohs_batch_process_scheduled(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
                                 size_t channel_stride, size_t seg_blocks, const unsigned *table_idx, const float *gain,
                                 void *hip_stream)
@@ -516,71 +608,34 @@ int ohs_batch_process_scheduled(ohs_batch *b, const float *d_in, float *d_out, s
                                          "(ohs_batch_share_eq_table goes back to the one shared table)");
     if (table_idx && b->eq.sched_n == 0)
         return fail(OHS_ERR_INVALID_ARG, "table_idx given, but no tables uploaded (ohs_batch_set_schedule_tables)");
-    seg_blocks = std::min(seg_blocks, std::max<size_t>(n_blocks, 1));
-    const size_t n_segs = (n_blocks + seg_blocks - 1) / seg_blocks;
+    const size_t n_segs = sched_segments(n_blocks, &seg_blocks);
     if (table_idx)
         for (size_t k = 0; k < n_segs; ++k)
             if (table_idx[k] >= b->eq.sched_n) return fail(OHS_ERR_INVALID_ARG, "table_idx entry out of range");
     if (b->failed || n_blocks == 0)     // (the plain call's answers)
         return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
-    {
-        const size_t frames = n_blocks * BS;
-        if (channel_stride < frames || (b->conv.S > 1 && stream_stride < 2 * frames && stream_stride < channel_stride + frames))
-            return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
-    }
-    // the handle's table / gain become those of segment k (what the setters do)
-    auto adopt_table = [&](unsigned t) {
-        for (size_t band = 0; band < b->eq.nb; ++band)
-            eq_set_shared_band(b->eq, band, &b->eq.sched_coeffs[((size_t)t * b->eq.nb + band) * 5], b->eq.sched_en[(size_t)t * b->eq.nb + band]);
-    };
+    if (!batch_strides_ok(b->conv.S, stream_stride, channel_stride, n_blocks * BS))
+        return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
     // A constant schedule is the plain call: same launches, same bits.
-    bool tabs_vary = false, gains_vary = false;
-    for (size_t k = 1; k < n_segs; ++k) {
-        tabs_vary = tabs_vary || (table_idx && table_idx[k] != table_idx[0]);
-        gains_vary = gains_vary || (gain && std::memcmp(&gain[k], &gain[0], sizeof(float)) != 0);
-    }
-    if (table_idx && !tabs_vary) { adopt_table(table_idx[0]); table_idx = nullptr; }
-    if (gain && !gains_vary) { b->gain = gain[0]; gain = nullptr; }
+    if (table_idx && sched_row_constant(table_idx, n_segs)) { batch_adopt_table(b, table_idx[0]); table_idx = nullptr; }
+    if (gain && sched_row_constant(gain, n_segs)) { b->gain = gain[0]; gain = nullptr; }
     if (!table_idx && !gain)
         return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
 
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    // the schedule's staging slot: free once the call that used it last has completed
-    ohs_batch::SchedSlot &slot = b->sched_slot[b->sched_next];
-    b->sched_next = (b->sched_next + 1) % ohs_batch::kSchedSlots;
-    if (slot.in_use) HIP_TRY(hipEventSynchronize(slot.done));
-    slot.in_use = false;
-    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
-    if (slot.cap < n_segs) {
-        if (slot.h) hipHostFree(slot.h);
-        if (slot.d) {
-            DeviceWideSection dws;
-            hipFree(slot.d);
-        }
-        slot.h = nullptr; slot.d = nullptr; slot.cap = 0;
-        const size_t cap = std::max<size_t>(1024, n_segs + n_segs / 2);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&slot.h), 2 * cap * sizeof(unsigned), hipHostMallocDefault));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&slot.d), 2 * cap * sizeof(unsigned)));
-        slot.cap = cap;
-    }
+    const SchedRows tab_row{table_idx, 0, 1, n_segs}, gain_row{gain, 0, 1, n_segs};
+    SchedLease lease;
+    int rc = sched_stage(b, tab_row, gain_row, st, lease);
+    if (rc) return rc;
     BatchSchedule sc;
     sc.seg_blocks = seg_blocks; sc.n_segs = n_segs; sc.tab = table_idx; sc.gain = gain;
-    if (table_idx) {
-        std::memcpy(slot.h, table_idx, n_segs * sizeof(unsigned));
-        HIP_TRY(hipMemcpyAsync(slot.d, slot.h, n_segs * sizeof(unsigned), hipMemcpyHostToDevice, st));
-        sc.d_tab = slot.d;
-    }
-    if (gain) {
-        std::memcpy(slot.h + slot.cap, gain, n_segs * sizeof(float));
-        HIP_TRY(hipMemcpyAsync(slot.d + slot.cap, slot.h + slot.cap, n_segs * sizeof(float), hipMemcpyHostToDevice, st));
-        sc.d_gain = reinterpret_cast<const float *>(slot.d + slot.cap);
-    }
-    const int rc = batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false, &sc);
-    if (hipEventRecord(slot.done, st) == hipSuccess) slot.in_use = true;
-    else hipStreamSynchronize(st);
+    if (table_idx) sc.d_tab = lease.slot->d;
+    if (gain) sc.d_gain = reinterpret_cast<const float *>(lease.slot->d + tab_row.entries());
+    rc = batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false, &sc);
     if (rc) return rc;
-    if (table_idx) adopt_table(table_idx[n_segs - 1]);
+    // the handle's table / gain are the last segment's now (what the setters do)
+    if (table_idx) batch_adopt_table(b, table_idx[n_segs - 1]);
     if (gain) b->gain = gain[n_segs - 1];
     return OHS_OK;
 }
@@ -597,8 +652,7 @@ int ohs_batch_process_scheduled_streams(ohs_batch *b, const float *d_in, float *
                                          "tables take their place (ohs_batch_share_eq_table), or pass table_idx = NULL");
     if (table_idx && b->eq.sched_n == 0)
         return fail(OHS_ERR_INVALID_ARG, "table_idx given, but no tables uploaded (ohs_batch_set_schedule_tables)");
-    seg_blocks = std::min(seg_blocks, std::max<size_t>(n_blocks, 1));
-    const size_t n_segs = (n_blocks + seg_blocks - 1) / seg_blocks, S = b->conv.S;
+    const size_t n_segs = sched_segments(n_blocks, &seg_blocks), S = b->conv.S;
     if ((table_idx && idx_stride != 0 && idx_stride < n_segs) || (gain && gain_stride != 0 && gain_stride < n_segs))
         return fail(OHS_ERR_INVALID_ARG, "a row stride is 0 (one row for all streams) or >= the number of segments");
     if (S * n_segs > (size_t)0x7fffffff) return fail(OHS_ERR_INVALID_ARG, "schedule too large");
@@ -612,20 +666,11 @@ int ohs_batch_process_scheduled_streams(ohs_batch *b, const float *d_in, float *
     }
     if (b->failed || n_blocks == 0)     // (the plain call's answers)
         return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
-    {
-        const size_t frames = n_blocks * BS;
-        if (channel_stride < frames || (S > 1 && stream_stride < 2 * frames && stream_stride < channel_stride + frames))
-            return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
-    }
+    if (!batch_strides_ok(S, stream_stride, channel_stride, n_blocks * BS))
+        return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
     // rows that are all the same are one row
-    auto rows_equal = [&](const void *base, size_t stride) {
-        const unsigned *p = static_cast<const unsigned *>(base);      // (gains compare as bits)
-        for (size_t s = 1; s < S; ++s)
-            if (std::memcmp(p + s * stride, p, n_segs * sizeof(unsigned)) != 0) return false;
-        return true;
-    };
-    if (idx_stride && rows_equal(table_idx, idx_stride)) idx_stride = 0;
-    if (gain_stride && rows_equal(gain, gain_stride)) gain_stride = 0;
+    if (idx_stride && sched_rows_equal(table_idx, idx_stride, S, n_segs)) idx_stride = 0;
+    if (gain_stride && sched_rows_equal(gain, gain_stride, S, n_segs)) gain_stride = 0;
     // The schedule governs this call only: what the handle holds is put back behind it, whatever the call returns.
     struct Restore {
         ohs_batch *b;
@@ -642,66 +687,26 @@ int ohs_batch_process_scheduled_streams(ohs_batch *b, const float *d_in, float *
     if (!idx_stride && !gain_stride && !b->eq.per_stream)
         return ohs_batch_process_scheduled(b, d_in, d_out, n_blocks, stream_stride, channel_stride, seg_blocks, table_idx, gain, hip_stream);
     // a constant row of its own kind is the plain call's table / gain
-    auto adopt_table = [&](unsigned t) {
-        for (size_t band = 0; band < b->eq.nb; ++band)
-            eq_set_shared_band(b->eq, band, &b->eq.sched_coeffs[((size_t)t * b->eq.nb + band) * 5], b->eq.sched_en[(size_t)t * b->eq.nb + band]);
-    };
-    if (table_idx && !idx_stride) {
-        bool vary = false;
-        for (size_t k = 1; k < n_segs; ++k) vary = vary || table_idx[k] != table_idx[0];
-        if (!vary) { adopt_table(table_idx[0]); table_idx = nullptr; }
-    }
-    if (gain && !gain_stride) {
-        bool vary = false;
-        for (size_t k = 1; k < n_segs; ++k) vary = vary || std::memcmp(&gain[k], &gain[0], sizeof(float)) != 0;
-        if (!vary) { b->gain = gain[0]; gain = nullptr; }
-    }
+    if (table_idx && !idx_stride && sched_row_constant(table_idx, n_segs)) { batch_adopt_table(b, table_idx[0]); table_idx = nullptr; }
+    if (gain && !gain_stride && sched_row_constant(gain, n_segs)) { b->gain = gain[0]; gain = nullptr; }
     if (!table_idx && !gain)
         return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
 
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    // the schedule's staging slot (as ohs_batch_process_scheduled's), here with a row per stream: streams x n_segs entries per array
-    ohs_batch::SchedSlot &slot = b->sched_slot[b->sched_next];
-    b->sched_next = (b->sched_next + 1) % ohs_batch::kSchedSlots;
-    if (slot.in_use) HIP_TRY(hipEventSynchronize(slot.done));
-    slot.in_use = false;
-    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
-    // (the slot holds 2 * cap entries: here the index rows, packed n_segs apart whatever the caller's stride, and right behind them
-    // the gain rows -- ONE copy to the device)
-    const size_t n_tab = table_idx ? (idx_stride ? S : 1) * n_segs : 0, n_gain = gain ? (gain_stride ? S : 1) * n_segs : 0;
-    if (2 * slot.cap < n_tab + n_gain) {
-        if (slot.h) hipHostFree(slot.h);
-        if (slot.d) {
-            DeviceWideSection dws;
-            hipFree(slot.d);
-        }
-        slot.h = nullptr; slot.d = nullptr; slot.cap = 0;
-        const size_t cap = std::max<size_t>(1024, (n_tab + n_gain) / 2 + (n_tab + n_gain) / 4 + 1);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&slot.h), 2 * cap * sizeof(unsigned), hipHostMallocDefault));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&slot.d), 2 * cap * sizeof(unsigned)));
-        slot.cap = cap;
-    }
-    auto pack = [&](const void *src, size_t stride, unsigned *h) {
-        const size_t rows = stride ? S : 1;
-        for (size_t s = 0; s < rows; ++s) std::memcpy(h + s * n_segs, static_cast<const unsigned *>(src) + s * stride, n_segs * sizeof(unsigned));
-    };
+    // a row per stream, or one for all: up to streams x n_segs entries per array
+    const SchedRows tab_rows{table_idx, idx_stride, idx_stride ? S : 1, n_segs}, gain_rows{gain, gain_stride, gain_stride ? S : 1, n_segs};
+    SchedLease lease;
+    const int rc = sched_stage(b, tab_rows, gain_rows, st, lease);
+    if (rc) return rc;
     sc.tab = nullptr; sc.tab_stride = 0;
-    if (table_idx) {
-        pack(table_idx, idx_stride, slot.h);
-        sc.tab = slot.h; sc.d_tab = slot.d; sc.tab_stride = idx_stride ? n_segs : 0;
-    }
+    if (table_idx) { sc.tab = lease.slot->h; sc.d_tab = lease.slot->d; sc.tab_stride = idx_stride ? n_segs : 0; }
     if (gain) {
-        pack(gain, gain_stride, slot.h + n_tab);
-        sc.gain = reinterpret_cast<const float *>(slot.h + n_tab);
-        sc.d_gain = reinterpret_cast<const float *>(slot.d + n_tab);
+        sc.gain = reinterpret_cast<const float *>(lease.slot->h + tab_rows.entries());
+        sc.d_gain = reinterpret_cast<const float *>(lease.slot->d + tab_rows.entries());
         sc.gain_stride = gain_stride ? n_segs : 0;
     }
-    HIP_TRY(hipMemcpyAsync(slot.d, slot.h, (n_tab + n_gain) * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    const int rc = batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false, &sc);
-    if (hipEventRecord(slot.done, st) == hipSuccess) slot.in_use = true;
-    else hipStreamSynchronize(st);
-    return rc;
+    return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false, &sc);
 }
 
 // ---- a schedule of HRIR sets inside one call -------------------------------------------------------------------
@@ -724,46 +729,6 @@ int ohs_batch_last_conv_ir_scheduled(const ohs_batch *b, int *scheduled)
     return OHS_OK;
 }
 
-// Rows of set indices (and prev_idx behind them) into the next staging slot (ohs_batch_process_scheduled's slots) and one copy to the
-// device on st: n_rows_src rows of n_segs entries, read idx_stride apart and packed n_segs apart, then n_prev entries of prev.  The
-// slot is free once the call that used it last has completed; *out is set as soon as the slot is taken, so that the caller can
-// close it with stage_rows_done whatever happens afterwards.
-static int stage_rows(ohs_batch *b, const unsigned *idx, size_t idx_stride, size_t n_rows_src, size_t n_segs, const unsigned *prev,
-                      size_t n_prev, hipStream_t st, ohs_batch::SchedSlot **out)
-{
-    const size_t n_rows = n_rows_src * n_segs, n_tab = n_rows + n_prev;
-    ohs_batch::SchedSlot &slot = b->sched_slot[b->sched_next];
-    b->sched_next = (b->sched_next + 1) % ohs_batch::kSchedSlots;
-    if (slot.in_use) HIP_TRY(hipEventSynchronize(slot.done));
-    slot.in_use = false;
-    if (!slot.done) HIP_TRY(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
-    *out = &slot;
-    if (2 * slot.cap < n_tab) {
-        if (slot.h) hipHostFree(slot.h);
-        if (slot.d) {
-            DeviceWideSection dws;
-            hipFree(slot.d);
-        }
-        slot.h = nullptr; slot.d = nullptr; slot.cap = 0;
-        const size_t cap = std::max<size_t>(1024, n_tab / 2 + n_tab / 4 + 1);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&slot.h), 2 * cap * sizeof(unsigned), hipHostMallocDefault));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&slot.d), 2 * cap * sizeof(unsigned)));
-        slot.cap = cap;
-    }
-    for (size_t r = 0; r < n_rows_src; ++r) std::memcpy(slot.h + r * n_segs, idx + r * idx_stride, n_segs * sizeof(unsigned));
-    if (n_prev) std::memcpy(slot.h + n_rows, prev, n_prev * sizeof(unsigned));
-    HIP_TRY(hipMemcpyAsync(slot.d, slot.h, n_tab * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    return OHS_OK;
-}
-
-// behind the launches that read the slot
-static void stage_rows_done(ohs_batch::SchedSlot *slot, hipStream_t st)
-{
-    if (!slot) return;
-    if (hipEventRecord(slot->done, st) == hipSuccess) slot->in_use = true;
-    else hipStreamSynchronize(st);
-}
-
 // ohs_batch_process_ir_scheduled (crossfade false) and ohs_batch_process_ir_crossfaded (crossfade true; switch_mode RING_OUT, prev_idx
 // optional) share the validation pass, the staging slot and the state rules
 static int batch_process_irs(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
@@ -781,51 +746,27 @@ static int batch_process_irs(ohs_batch *b, const float *d_in, float *d_out, size
         return fail(OHS_ERR_INVALID_ARG, "the handle holds a response longer than one partition (512 taps): not supported in a schedule");
     if (c.pt_active) return fail(OHS_ERR_INVALID_ARG, "the handle has pending tails of a longer response: not supported in a schedule");
     if (!c.lazy_ok) return fail(OHS_ERR_INVALID_ARG, "the handle does not keep the lazy state the scheduled kernel leaves");
-    seg_blocks = std::min(seg_blocks, std::max<size_t>(n_blocks, 1));
-    const size_t n_segs = (n_blocks + seg_blocks - 1) / seg_blocks, S = c.S;
+    const size_t n_segs = sched_segments(n_blocks, &seg_blocks), S = c.S;
     if (idx_stride != 0 && idx_stride < n_segs)
         return fail(OHS_ERR_INVALID_ARG, "idx_stride is 0 (one row for all streams) or >= the number of segments");
     if (S * n_segs > (size_t)0x7fffffff) return fail(OHS_ERR_INVALID_ARG, "schedule too large");
-    // one pass over the rows: the range check, whether anything varies along a row, whether the rows differ
-    const size_t rows = idx_stride ? S : 1;
-    bool vary = false, rows_differ = false;
-    for (size_t r = 0; r < rows; ++r) {
-        const unsigned *row = ir_idx + r * idx_stride;
-        for (size_t k = 0; k < n_segs; ++k) {
-            if (row[k] >= c.irs_n) return fail(OHS_ERR_INVALID_ARG, "ir_idx entry out of range");
-            vary = vary || row[k] != row[0];
-            rows_differ = rows_differ || row[k] != ir_idx[k];
-        }
-    }
-    // the crossfaded call: where a fade begins -- at a change along a row, or at the call's start against prev_idx -- and whether
-    // the call's last block is such a block in any stream (its per-path overlaps are then the sum of both halves of the fade)
-    bool boundary = false, faded_end = false, prev_differ = false;
-    if (crossfade) {
-        const bool last_is_first = n_blocks > 0 && (n_blocks - 1) % seg_blocks == 0;
-        for (size_t r = 0; r < rows; ++r) {
-            const unsigned *row = ir_idx + r * idx_stride;
-            if (prev_idx) {
-                if (prev_idx[r] >= c.irs_n) return fail(OHS_ERR_INVALID_ARG, "prev_idx entry out of range");
-                prev_differ = prev_differ || prev_idx[r] != prev_idx[0];
-                boundary = boundary || prev_idx[r] != row[0];
-                faded_end = faded_end || (last_is_first && n_segs == 1 && prev_idx[r] != row[0]);
-            }
-            faded_end = faded_end || (last_is_first && n_segs > 1 && row[n_segs - 1] != row[n_segs - 2]);
-        }
-        boundary = boundary || vary;
-        crossfade = boundary;       // (a call without any boundary takes the RING_OUT paths below: their launches, their bits)
-    }
+    // one pass over the rows (and prev_idx, which the crossfaded call alone reads)
+    if (!crossfade) prev_idx = nullptr;
+    const ohs_host::SchedRowScan rs = ohs_host::sched_scan_rows(ir_idx, idx_stride, idx_stride ? S : 1, n_segs, (unsigned)c.irs_n, prev_idx,
+                                                                n_blocks, seg_blocks);
+    if (rs.idx_bad) return fail(OHS_ERR_INVALID_ARG, "ir_idx entry out of range");
+    if (rs.prev_bad) return fail(OHS_ERR_INVALID_ARG, "prev_idx entry out of range");
+    // The crossfaded call: a fade begins at a change along a row, or at the call's start against prev_idx.  A call without any such
+    // boundary takes the RING_OUT paths below: their launches, their bits.
+    crossfade = crossfade && (rs.vary || rs.prev_boundary);
     if (b->failed || n_blocks == 0)     // (the plain call's answers)
         return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
-    {
-        const size_t frames = n_blocks * BS;
-        if (channel_stride < frames || (S > 1 && stream_stride < 2 * frames && stream_stride < channel_stride + frames))
-            return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
-    }
+    if (!batch_strides_ok(S, stream_stride, channel_stride, n_blocks * BS))
+        return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)hip_stream;
     const bool cut = switch_mode == OHS_IR_SWITCH_CUT, shared = idx_stride == 0;
-    if (shared && !vary && !crossfade) {
+    if (shared && !rs.vary && !crossfade) {
         // One set throughout, for all streams: the plain kernel on that set's table -- the plain call's launches and bits.  The overlaps
         // at rest belong to the responses that go: under RING_OUT they are computed now (and ring out), under CUT the call's start is a
         // boundary and they are zero, as after four set_ir.
@@ -840,24 +781,26 @@ static int batch_process_irs(ohs_batch *b, const float *d_in, float *d_out, size
         if (rca) return rca;
         return batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false);
     }
-    // the rows' staging slot (ohs_batch_process_scheduled's): rows packed n_segs apart; equal rows travel as one
-    // (the crossfaded call's prev_idx travels behind the rows)
-    const size_t n_rows = (rows_differ ? S : 1) * n_segs, n_prev = (crossfade && prev_idx) ? (prev_differ ? S : 1) : 0;
-    ohs_batch::SchedSlot *slot = nullptr;
+    // the rows' staging slot: equal rows travel as one; the crossfaded call's prev_idx travels behind the rows.  The slot is closed
+    // right behind the call's launches.
+    const size_t n_rows_src = rs.rows_differ ? S : 1, n_rows = n_rows_src * n_segs;
+    const size_t n_prev = (crossfade && prev_idx) ? (rs.prev_differ ? S : 1) : 0;
+    int rc;
     {
-        const int rcs = stage_rows(b, ir_idx, idx_stride, rows_differ ? S : 1, n_segs, prev_idx, n_prev, st, &slot);
-        if (rcs) return rcs;
+        SchedLease lease;
+        rc = sched_stage(b, {ir_idx, idx_stride, n_rows_src, n_segs}, {prev_idx, 0, 1, n_prev}, st, lease);
+        if (rc) return rc;
+        ConvIrs ci;
+        ci.tab = lease.slot->d; ci.seg_blocks = (int)seg_blocks; ci.stream_stride = rs.rows_differ ? (int)n_segs : 0;
+        ci.call_blocks = (int)n_blocks; ci.cut = cut;
+        ci.per_stream_state = !shared;      // (a shared row is adopted below: the handle's spectra rebuild the overlaps when asked)
+        if (crossfade) {
+            // faded_end: the call's last block is a fade in some stream, its per-path overlaps the sum of both halves of the fade
+            ci.xfade = true; ci.faded_end = rs.faded_end;
+            if (n_prev) { ci.prev = lease.slot->d + n_rows; ci.prev_stride = rs.prev_differ ? 1 : 0; }
+        }
+        rc = batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false, nullptr, &ci);
     }
-    ConvIrs ci;
-    ci.tab = slot->d; ci.seg_blocks = (int)seg_blocks; ci.stream_stride = rows_differ ? (int)n_segs : 0; ci.call_blocks = (int)n_blocks;
-    ci.cut = cut;
-    ci.per_stream_state = !shared;      // (a shared row is adopted below: the handle's spectra rebuild the overlaps when asked)
-    if (crossfade) {
-        ci.xfade = true; ci.faded_end = faded_end;
-        if (n_prev) { ci.prev = slot->d + n_rows; ci.prev_stride = prev_differ ? 1 : 0; }
-    }
-    const int rc = batch_process_impl(b, d_in, d_out, n_blocks, stream_stride, channel_stride, hip_stream, false, nullptr, &ci);
-    stage_rows_done(slot, st);
     if (rc) return rc;
     // one row for all streams: the handle's responses ARE the last segment's now (what ohs_batch_process_scheduled does with its table)
     if (shared) return conv_adopt_schedule_set(c, ir_idx[n_segs - 1], st);
@@ -910,6 +853,24 @@ static bool layout_strides_ok(size_t n_outer, size_t outer, size_t n_inner, size
     return outer >= (n_inner - 1) * inner + frames || inner >= (n_outer - 1) * outer + frames;
 }
 
+// The layout calls' regions, in [S][K][frames] and out [S][2][frames]: each fits its strides, and -- out of place only -- the two, first
+// to last frame touched, do not meet.  false: refused, the message set.
+static bool layout_regions_ok(size_t S, size_t K, size_t frames, const float *d_in, size_t in_ss, size_t in_cs, const float *d_out,
+                              size_t out_ss, size_t out_cs)
+{
+    if (!layout_strides_ok(S, in_ss, K, in_cs, frames) || !layout_strides_ok(S, out_ss, 2, out_cs, frames)) {
+        fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
+        return false;
+    }
+    const float *in_end = d_in + (S - 1) * in_ss + (K - 1) * in_cs + frames;
+    const float *out_end = d_out + (S - 1) * out_ss + out_cs + frames;
+    if (!(in_end <= d_out || out_end <= d_in)) {
+        fail(OHS_ERR_INVALID_ARG, "input and output regions overlap (the layout call is out of place only)");
+        return false;
+    }
+    return true;
+}
+
 int ohs_batch_process_layout(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
                              size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride, void *hip_stream)
 {
@@ -917,20 +878,11 @@ int ohs_batch_process_layout(ohs_batch *b, const float *d_in, float *d_out, size
     ConvState &c = b->conv;
     if (c.lay_K == 0 || !c.d_lay_cd) return fail(OHS_ERR_INVALID_ARG, "no layout uploaded (ohs_batch_set_layout_irs)");
     if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
-    if (b->failed)
-        return fail(OHS_ERR_HIP, "this batch failed in the middle of an earlier call (" + b->fail_msg +
-                                     "): its per-stream state is half-advanced; ohs_batch_reset starts it afresh");
+    if (b->failed) return batch_refuse_failed(b);
     if (n_blocks == 0) return OHS_OK;
     const size_t frames = n_blocks * BS, S = c.S, K = c.lay_K;
-    if (!layout_strides_ok(S, in_stream_stride, K, in_channel_stride, frames) ||
-        !layout_strides_ok(S, out_stream_stride, 2, out_channel_stride, frames))
-        return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
-    {   // out of place only: the two regions, first to last frame touched, must not meet
-        const float *in_end = d_in + (S - 1) * in_stream_stride + (K - 1) * in_channel_stride + frames;
-        const float *out_end = d_out + (S - 1) * out_stream_stride + out_channel_stride + frames;
-        if (!(in_end <= d_out || out_end <= d_in))
-            return fail(OHS_ERR_INVALID_ARG, "input and output regions overlap (the layout call is out of place only)");
-    }
+    if (!layout_regions_ok(S, K, frames, d_in, in_stream_stride, in_channel_stride, d_out, out_stream_stride, out_channel_stride))
+        return OHS_ERR_INVALID_ARG;
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)hip_stream;
     auto body = [&]() -> int {
@@ -947,10 +899,7 @@ int ohs_batch_process_layout(ohs_batch *b, const float *d_in, float *d_out, size
     };
     const int rc = body();
     if (rc == OHS_OK || rc == OHS_ERR_INVALID_ARG) return rc;
-    const std::string why = g_err;
-    b->failed = true;
-    b->fail_msg = why;
-    return fail(rc, why);
+    return batch_mark_failed(b, rc);
 }
 
 // ---- head-tracked speaker layouts: a table of layouts walked per stream and segment ----------------------------------
@@ -988,47 +937,26 @@ int ohs_batch_process_layout_scheduled(ohs_batch *b, const float *d_in, float *d
     ConvState &c = b->conv;
     if (c.lays_n == 0 || !c.d_lays_cd) return fail(OHS_ERR_INVALID_ARG, "no table uploaded (ohs_batch_set_layout_schedule_irs)");
     if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
-    if (b->failed)
-        return fail(OHS_ERR_HIP, "this batch failed in the middle of an earlier call (" + b->fail_msg +
-                                     "): its per-stream state is half-advanced; ohs_batch_reset starts it afresh");
+    if (b->failed) return batch_refuse_failed(b);
     if (n_blocks == 0) return OHS_OK;
-    seg_blocks = std::min(seg_blocks, n_blocks);
-    const size_t frames = n_blocks * BS, S = c.S, K = c.lays_K, n_segs = (n_blocks + seg_blocks - 1) / seg_blocks;
+    const size_t n_segs = sched_segments(n_blocks, &seg_blocks), frames = n_blocks * BS, S = c.S, K = c.lays_K;
     if (idx_stride != 0 && idx_stride < n_segs)
         return fail(OHS_ERR_INVALID_ARG, "idx_stride is 0 (one row for all streams) or >= the number of segments");
     if (S * n_segs > (size_t)0x7fffffff) return fail(OHS_ERR_INVALID_ARG, "schedule too large");
     const bool fade = switch_mode == OHS_LAYOUT_SWITCH_CROSSFADE, shared = idx_stride == 0;
     if (!fade) prev_idx = nullptr;      // (read under CROSSFADE only)
-    // one pass over the rows: the range check, whether anything varies along a row, whether the rows differ; prev_idx beside them
-    const size_t rows = shared ? 1 : S;
-    bool vary = false, rows_differ = false, prev_differ = false, prev_boundary = false;
-    for (size_t r = 0; r < rows; ++r) {
-        const unsigned *row = set_idx + r * idx_stride;
-        for (size_t k = 0; k < n_segs; ++k) {
-            if (row[k] >= c.lays_n) return fail(OHS_ERR_INVALID_ARG, "set_idx entry out of range");
-            vary = vary || row[k] != row[0];
-            rows_differ = rows_differ || row[k] != set_idx[k];
-        }
-        if (prev_idx) {
-            if (prev_idx[r] >= c.lays_n) return fail(OHS_ERR_INVALID_ARG, "prev_idx entry out of range");
-            prev_differ = prev_differ || prev_idx[r] != prev_idx[0];
-            prev_boundary = prev_boundary || prev_idx[r] != row[0];
-        }
-    }
-    if (!layout_strides_ok(S, in_stream_stride, K, in_channel_stride, frames) ||
-        !layout_strides_ok(S, out_stream_stride, 2, out_channel_stride, frames))
-        return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
-    {   // out of place only: the two regions, first to last frame touched, must not meet
-        const float *in_end = d_in + (S - 1) * in_stream_stride + (K - 1) * in_channel_stride + frames;
-        const float *out_end = d_out + (S - 1) * out_stream_stride + out_channel_stride + frames;
-        if (!(in_end <= d_out || out_end <= d_in))
-            return fail(OHS_ERR_INVALID_ARG, "input and output regions overlap (the layout call is out of place only)");
-    }
+    // one pass over the rows, prev_idx beside them
+    const ohs_host::SchedRowScan rs = ohs_host::sched_scan_rows(set_idx, idx_stride, shared ? 1 : S, n_segs, (unsigned)c.lays_n, prev_idx,
+                                                                n_blocks, seg_blocks);
+    if (rs.idx_bad) return fail(OHS_ERR_INVALID_ARG, "set_idx entry out of range");
+    if (rs.prev_bad) return fail(OHS_ERR_INVALID_ARG, "prev_idx entry out of range");
+    if (!layout_regions_ok(S, K, frames, d_in, in_stream_stride, in_channel_stride, d_out, out_stream_stride, out_channel_stride))
+        return OHS_ERR_INVALID_ARG;
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)hip_stream;
     // one set throughout, for all streams, and no boundary at the call's start: k_conv_p1_layout on that set's slice of the table
-    const bool plain = shared && !vary && !prev_boundary;
-    ohs_batch::SchedSlot *slot = nullptr;
+    const bool plain = shared && !rs.vary && !rs.prev_boundary;
+    SchedLease lease;
     auto body = [&]() -> int {
         if (b->join_pending) {      // (a deferred call's last convolutions: the EQ state and d_out may be theirs)
             HIP_TRY(hipStreamWaitEvent(st, b->chunk_done[(size_t)b->chunk_done_n - 1], 0));
@@ -1037,12 +965,12 @@ int ohs_batch_process_layout_scheduled(ohs_batch *b, const float *d_in, float *d
         ConvLayoutRows lr;
         if (!plain) {
             // the rows' staging slot (the IR-scheduled calls'): rows packed n_segs apart, equal rows travel as one; prev_idx behind them
-            const size_t n_rows = (rows_differ ? S : 1) * n_segs, n_prev = prev_idx ? (prev_differ ? S : 1) : 0;
-            const int rcs = stage_rows(b, set_idx, idx_stride, rows_differ ? S : 1, n_segs, prev_idx, n_prev, st, &slot);
+            const size_t n_rows_src = rs.rows_differ ? S : 1, n_prev = prev_idx ? (rs.prev_differ ? S : 1) : 0;
+            const int rcs = sched_stage(b, {set_idx, idx_stride, n_rows_src, n_segs}, {prev_idx, 0, 1, n_prev}, st, lease);
             if (rcs) return rcs;
-            lr.tab = slot->d; lr.seg_blocks = (int)seg_blocks; lr.stream_stride = rows_differ ? (int)n_segs : 0;
+            lr.tab = lease.slot->d; lr.seg_blocks = (int)seg_blocks; lr.stream_stride = rs.rows_differ ? (int)n_segs : 0;
             lr.fade = fade;
-            if (n_prev) { lr.prev = slot->d + n_rows; lr.prev_stride = prev_differ ? 1 : 0; }
+            if (n_prev) { lr.prev = lease.slot->d + n_rows_src * n_segs; lr.prev_stride = rs.prev_differ ? 1 : 0; }
         }
         int rc = conv_launch_layout_scheduled(c, b->ctx, d_in, (long long)in_stream_stride, (long long)in_channel_stride, d_out,
                                               (long long)out_stream_stride, (long long)out_channel_stride, (int)n_blocks, b->gain, st,
@@ -1053,12 +981,8 @@ int ohs_batch_process_layout_scheduled(ohs_batch *b, const float *d_in, float *d
         return rc;
     };
     const int rc = body();
-    stage_rows_done(slot, st);
     if (rc == OHS_OK || rc == OHS_ERR_INVALID_ARG) return rc;
-    const std::string why = g_err;
-    b->failed = true;
-    b->fail_msg = why;
-    return fail(rc, why);
+    return batch_mark_failed(b, rc);
 }
 
 int ohs_batch_process_deferred(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
@@ -1079,8 +1003,8 @@ int ohs_batch_process_host(ohs_batch *b, const float *h_in, float *h_out, size_t
     if (!b || !h_in || !h_out) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
     if (n_blocks == 0) return OHS_OK;
     if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
-    const size_t frames = n_blocks * BS, S = b->conv.S;
-    if (channel_stride < frames || (S > 1 && stream_stride < 2 * frames && stream_stride < channel_stride + frames))
+    const size_t S = b->conv.S;
+    if (!batch_strides_ok(S, stream_stride, channel_stride, n_blocks * BS))
         return fail(OHS_ERR_INVALID_ARG, "strides smaller than the processed region");
     HIP_TRY(hipSetDevice(b->device));
     if (chunk_blocks == 0) {
@@ -1218,12 +1142,7 @@ int ohs_batch_process_host(ohs_batch *b, const float *h_in, float *h_out, size_t
     // Fail closed (ohs_batch_reset's contract): a copy, an event or a wait that failed with chunks already processed leaves
     // the per-stream state advanced for some chunks only -- exactly like a failure inside ohs_batch_process, which has
     // marked the handle itself.  (Argument errors were found before the loop: nothing was queued.)
-    if (rc && rc != OHS_ERR_INVALID_ARG && !b->failed) {
-        const std::string why = g_err;
-        b->failed = true;
-        b->fail_msg = why;
-        return fail(rc, why);
-    }
+    if (rc && rc != OHS_ERR_INVALID_ARG && !b->failed) return batch_mark_failed(b, rc);
     if (rc) return rc;
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
         b->failed = true;

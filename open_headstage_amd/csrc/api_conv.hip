@@ -754,6 +754,29 @@ static void layout_overlap_release_if_unused(ConvState &c)
     c.d_lay_ov = nullptr; c.d_lay_ov_alt = nullptr;
 }
 
+// One upload for the single layout and the table of layouts alike: `units` sets of four responses (rows, as layout_build_tables reads
+// them) into a fresh *d_cd, the layout overlap zeroed.  The caller has freed the old *d_cd; on an error nothing is left behind.
+template <class Rows>
+static int layout_upload(ConvState &c, DeviceCtx *ctx, size_t units, size_t len, Rows rows, float4 **d_cd, hipStream_t st)
+{
+    auto body = [&]() -> int {
+        HIP_TRY(hipMalloc(d_cd, units * (size_t)NF * sizeof(float4)));
+        const int rco = layout_overlap_zeroed(c, st);
+        if (rco) return rco;
+        const int rct = layout_build_tables(ctx, units, len, rows, *d_cd, st);
+        if (rct) return rct;
+        HIP_TRY(hipStreamSynchronize(st));
+        return OHS_OK;
+    };
+    const int rc = body();
+    if (rc) {
+        if (*d_cd) hipFree(*d_cd);
+        *d_cd = nullptr;
+        layout_overlap_release_if_unused(c);
+    }
+    return rc;
+}
+
 // The speaker layout of ohs_batch_process_layout.  irs[c][e] is row 2 c + e, so the four rows of pair p -- channel 2 p to both ears,
 // channel 2 p + 1 to both ears -- are the four paths Lsl, Lsr, Rsl, Rsr of a "set": the spectra by k_ir_spectrum, (C, D) by k_build_cd,
 // the block loop's layout by k_irs_tables, exactly as conv_set_schedule_irs builds a set (K = 2: the bits of a plain call on a handle
@@ -771,25 +794,10 @@ int conv_set_layout_irs(ConvState &c, DeviceCtx *ctx, size_t n_channels, const f
         }
         return OHS_OK;
     }
-    const size_t P = (n_channels + 1) / 2;
     // (unit p = pair p: rows irs[2 p][0], irs[2 p][1], irs[2 p + 1][0], irs[2 p + 1][1]; an odd last channel has a zero partner)
     auto rows = [&](size_t p, size_t r) -> const float * { return 4 * p + r < 2 * n_channels ? irs + (4 * p + r) * len : nullptr; };
-    auto body = [&]() -> int {
-        HIP_TRY(hipMalloc(&c.d_lay_cd, P * (size_t)NF * sizeof(float4)));
-        const int rco = layout_overlap_zeroed(c, st);
-        if (rco) return rco;
-        const int rct = layout_build_tables(ctx, P, len, rows, c.d_lay_cd, st);
-        if (rct) return rct;
-        HIP_TRY(hipStreamSynchronize(st));
-        return OHS_OK;
-    };
-    const int rc = body();
-    if (rc) {
-        if (c.d_lay_cd) hipFree(c.d_lay_cd);
-        c.d_lay_cd = nullptr;
-        layout_overlap_release_if_unused(c);
-        return rc;
-    }
+    const int rc = layout_upload(c, ctx, (n_channels + 1) / 2, len, rows, &c.d_lay_cd, st);
+    if (rc) return rc;
     c.lay_K = n_channels; c.lay_len = len;
     return OHS_OK;
 }
@@ -806,38 +814,23 @@ int conv_set_layout_schedule_irs(ConvState &c, DeviceCtx *ctx, size_t n_sets, si
         layout_overlap_release_if_unused(c);
         return OHS_OK;
     }
-    const size_t P = (n_channels + 1) / 2, units = n_sets * P;
+    const size_t P = (n_channels + 1) / 2;
     auto rows = [&](size_t u, size_t r) -> const float * {      // (unit u = set u / P, pair u % P)
         const size_t j = u / P, q = 4 * (u % P) + r;
         return q < 2 * n_channels ? irs + (j * 2 * n_channels + q) * len : nullptr;
     };
-    auto body = [&]() -> int {
-        HIP_TRY(hipMalloc(&c.d_lays_cd, units * (size_t)NF * sizeof(float4)));
-        const int rco = layout_overlap_zeroed(c, st);
-        if (rco) return rco;
-        const int rct = layout_build_tables(ctx, units, len, rows, c.d_lays_cd, st);
-        if (rct) return rct;
-        HIP_TRY(hipStreamSynchronize(st));
-        return OHS_OK;
-    };
-    const int rc = body();
-    if (rc) {
-        if (c.d_lays_cd) hipFree(c.d_lays_cd);
-        c.d_lays_cd = nullptr;
-        layout_overlap_release_if_unused(c);
-        return rc;
-    }
+    const int rc = layout_upload(c, ctx, n_sets * P, len, rows, &c.d_lays_cd, st);
+    if (rc) return rc;
     c.lays_n = n_sets; c.lays_K = n_channels; c.lays_len = len;
     return OHS_OK;
 }
 
-// Chunks per stream: conv_p1_chunks' rule for this kernel's resident waves, capped to 1 / 2 / 4 / 8 / 16 as conv_choose_plan caps
-// k_conv_p1_irs (every chunk but the first pays a dry block; there is no pre-pass)
-int conv_launch_layout(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
-                       float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st)
+// What the two layout kernels share of a launch: the chunks per stream -- conv_p1_chunks' rule for this kernel's resident waves, capped
+// to 1 / 2 / 4 / 8 / 16 as conv_choose_plan caps k_conv_p1_irs (every chunk but the first pays a dry block; there is no pre-pass) --
+// and the arguments around the layout's own.  n_blocks > 0.
+static ConvP1Args layout_launch_args(const ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out,
+                                     long long out_ss, long long out_cs, int n_blocks, float gain)
 {
-    if (!c.d_lay_cd || c.lay_K == 0) return fail(OHS_ERR_INVALID_ARG, "no layout uploaded (ohs_batch_set_layout_irs)");
-    if (n_blocks <= 0) return OHS_OK;
     const long long want = conv_p1_chunks(ctx, c.S, n_blocks, 0, 8, conv_layout_waves_per_cu());
     int K = 16;
     while (K > want || K > n_blocks) K >>= 1;
@@ -851,12 +844,21 @@ int conv_launch_layout(ConvState &c, DeviceCtx *ctx, const float *in, long long 
     for (int g = 0; g < 4; ++g) a.weights[g] = 1;
     a.merged_in = c.d_lay_ov; a.merged_out = c.d_lay_ov_alt;
     a.gain_seg = 1;
+    return a;
+}
+
+int conv_launch_layout(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
+                       float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st)
+{
+    if (!c.d_lay_cd || c.lay_K == 0) return fail(OHS_ERR_INVALID_ARG, "no layout uploaded (ohs_batch_set_layout_irs)");
+    if (n_blocks <= 0) return OHS_OK;
+    const ConvP1Args a = layout_launch_args(c, ctx, in, in_ss, in_cs, out, out_ss, out_cs, n_blocks, gain);
     ConvLayoutArgs l;
     l.cd = c.d_lay_cd; l.n_channels = (int)c.lay_K; l.n_pairs = (int)((c.lay_K + 1) / 2);
     const hipError_t e = launch_conv_p1_layout(a, l, st);
     if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_layout launch: ") + hipGetErrorString(e));
     std::swap(c.d_lay_ov, c.d_lay_ov_alt);
-    c.last_lay_pairs = l.n_pairs; c.last_lay_ranges = K; c.last_lay_scheduled = false;
+    c.last_lay_pairs = l.n_pairs; c.last_lay_ranges = a.chunks; c.last_lay_scheduled = false;
     return OHS_OK;
 }
 
@@ -868,19 +870,7 @@ int conv_launch_layout_scheduled(ConvState &c, DeviceCtx *ctx, const float *in, 
     if (!c.d_lays_cd || c.lays_n == 0) return fail(OHS_ERR_INVALID_ARG, "no table uploaded (ohs_batch_set_layout_schedule_irs)");
     if (!rows && one_set >= c.lays_n) return fail(OHS_ERR_INVALID_ARG, "set index out of range");
     if (n_blocks <= 0) return OHS_OK;
-    const long long want = conv_p1_chunks(ctx, c.S, n_blocks, 0, 8, conv_layout_waves_per_cu());
-    int K = 16;
-    while (K > want || K > n_blocks) K >>= 1;
-    ConvP1Args a{};
-    a.in = in; a.out = out;
-    a.in_stream_stride = in_ss; a.in_ch_stride = in_cs;
-    a.out_stream_stride = out_ss; a.out_ch_stride = out_cs;
-    a.n_blocks = n_blocks; a.n_streams = (int)c.S; a.chunks = K;
-    a.tw = ctx->d_tw; a.gain = gain; a.fp_mode = c.fp_mode;
-    a.xcd_lo = 0; a.xcd_n = 8;
-    for (int g = 0; g < 4; ++g) a.weights[g] = 1;
-    a.merged_in = c.d_lay_ov; a.merged_out = c.d_lay_ov_alt;
-    a.gain_seg = 1;
+    const ConvP1Args a = layout_launch_args(c, ctx, in, in_ss, in_cs, out, out_ss, out_cs, n_blocks, gain);
     const int P = (int)((c.lays_K + 1) / 2);
     hipError_t e;
     if (!rows) {
@@ -896,7 +886,7 @@ int conv_launch_layout_scheduled(ConvState &c, DeviceCtx *ctx, const float *in, 
     }
     if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_layout_irs launch: ") + hipGetErrorString(e));
     std::swap(c.d_lay_ov, c.d_lay_ov_alt);
-    c.last_lay_pairs = P; c.last_lay_ranges = K; c.last_lay_scheduled = rows != nullptr;
+    c.last_lay_pairs = P; c.last_lay_ranges = a.chunks; c.last_lay_scheduled = rows != nullptr;
     return OHS_OK;
 }
 

@@ -535,11 +535,10 @@ struct ohs_batch {
     hipStream_t st_h2d = nullptr, st_comp = nullptr, st_d2h = nullptr;
     hipEvent_t ev_h2d[kHostSlots] = {nullptr, nullptr, nullptr}, ev_comp[kHostSlots] = {nullptr, nullptr, nullptr},
                ev_d2h[kHostSlots] = {nullptr, nullptr, nullptr};
-    // ohs_batch_process_scheduled: the call's schedule travels through one of kSchedSlots staging slots -- pinned host memory
-    // (the caller's arrays are free on return, the copy to the device is asynchronous) and its device copy, [cap] table indices
-    // then [cap] gains; `done` is recorded behind the call that used the slot and waited for before the slot is filled again
-    // (ohs_batch_process_scheduled_streams: a row per stream, packed n_segs apart -- up to streams x n_segs entries per array; it
-    // uses the slot's 2 * cap entries as one array, the gain rows right behind the index rows, and copies them in one go)
+    // The scheduled calls: a call's rows (table indices, gains, set indices, prev_idx) travel through one of kSchedSlots staging
+    // slots -- pinned host memory and its device copy, `cap` 32-bit entries each, the call's arrays packed one behind the other
+    // and copied in one go; `done` is recorded behind the call that used the slot and waited for before the slot is filled
+    // again (api_batch.hip: SchedLease)
     static constexpr int kSchedSlots = 4;
     struct SchedSlot {
         unsigned *h = nullptr, *d = nullptr;

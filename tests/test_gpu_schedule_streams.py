@@ -493,3 +493,67 @@ def test_argument_errors_leave_the_handle_usable(oracle):
     torch.cuda.synchronize()
     ref = _Reference(oracle, _ffi.lib(), irs, coeffs, en)
     _same_bits(y.cpu().numpy(), ref.call(x.cpu().numpy(), 2, idx, gains), "after the refused calls")
+
+
+# ---- 11. the staging slots under mixed traffic ----------------------------------------------------------------------------------
+def test_mixed_scheduled_calls_share_the_staging_slots():
+    """One handle, no host synchronisation: three rounds of {per-stream EQ + gain schedule, crossfaded IR schedule with rows per
+    stream and prev_idx, crossfaded layout schedule with rows per stream and prev_idx}, seg_blocks 1, 64 / 128 / 384 blocks.  Nine
+    calls are more than two turns of the four staging slots, and the last round's EQ call stages 3 x 384 x 2 = 2304 entries -- more
+    than a fresh slot's 2048 --, so a slot earlier calls used is regrown while others are in flight.  The yardstick: the same calls
+    with a sync() behind each, the six stereo calls on one handle and the three layout calls on another (the two states are
+    independent: test_gpu_layout_schedule.py's test_scheduled_layout_and_stereo_calls_do_not_touch_each_other).  Bit for bit."""
+    import torch
+    from open_headstage_amd import _ffi, synth
+    from tests.test_cpu_ir_schedule import make_sets
+    from tests.test_cpu_layout import make_input
+    from tests.test_cpu_layout_schedule import make_table
+    streams, K, n_choices, rounds = 3, 3, 4, [64, 128, 384]
+    coeffs, en = _tables(n_choices)
+    sets, table, irs = make_sets(n_choices), make_table(n_choices, K), synth.hrir_set(512)
+    total = sum(rounds) * 512
+    x_eq = torch.from_numpy(synth.white_noise(range(900, 900 + streams), total)).cuda()
+    x_ir = torch.from_numpy(synth.white_noise(range(920, 920 + streams), total)).cuda()
+    x_lay = torch.from_numpy(make_input(streams, K, sum(rounds), seed=6000)).cuda()
+    rng = np.random.default_rng(2718)
+    calls, pos = [], 0
+    for nb in rounds:
+        sl = slice(pos * 512, (pos + nb) * 512)
+        rows = lambda: rng.integers(0, n_choices, (streams, nb)).astype(np.uint32)      # noqa: E731
+        prev = lambda: rng.integers(0, n_choices, streams).astype(np.uint32)            # noqa: E731
+        calls.append(("eq", x_eq[:, :, sl].contiguous(), rows(), rng.uniform(0.3, 0.9, (streams, nb)).astype(np.float32)))
+        calls.append(("ir", x_ir[:, :, sl].contiguous(), rows(), prev()))
+        calls.append(("layout", x_lay[:, :, sl].contiguous(), rows(), prev()))
+        pos += nb
+    assert calls[6][2].size + calls[6][3].size == 2304
+
+    def handle():
+        bp = _batch(_ffi.lib(), irs, streams=streams)
+        bp.set_schedule_tables(coeffs, en)
+        bp.set_schedule_irs(sets)
+        bp.set_layout_table(table)
+        bp.set_eq_enabled(True)         # (the handle's own table has no band enabled: the EQ state is the EQ-scheduled calls' alone)
+        return bp
+
+    def run(bp, kinds, sync):
+        out = []
+        for kind, x, idx, extra in calls:
+            if kind not in kinds:
+                continue
+            if kind == "eq":
+                out.append(bp.process_scheduled_streams(x, 1, idx, extra))
+            elif kind == "ir":
+                out.append(bp.process_ir_crossfaded(x, 1, idx, extra))
+            else:
+                out.append(bp.process_layout_scheduled(x, idx, 1, extra, True))
+            if sync:
+                bp.sync()
+        torch.cuda.synchronize()
+        return out
+
+    mixed = run(handle(), ("eq", "ir", "layout"), False)
+    stereo = iter(run(handle(), ("eq", "ir"), True))
+    layout = iter(run(handle(), ("layout",), True))
+    for i, (y, (kind, _, _, _)) in enumerate(zip(mixed, calls)):
+        want = next(layout if kind == "layout" else stereo)
+        assert torch.equal(y.view(torch.int32), want.view(torch.int32)), f"call {i} ({kind}, {y.shape[2] // 512} blocks)"
