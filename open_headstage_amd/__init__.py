@@ -9,10 +9,12 @@ contains no CPU compute path.
 from .dsp import (BLOCK_SIZE, FFT_SIZE, NUM_EQ_BANDS, BandConfig, BiquadFilter, ConvolutionEngine, ConvolutionPath,
                   FilterType, StereoParametricEQ, biquad_coefficients, process_chain)
 from .batch import LAYOUT_5_1, LAYOUT_7_1, BatchProcessor, NodeBatchProcessor
+from .session import HeadTrack, SessionRenderer, nearest_set, plan_calls, render_files, yaw_rows
 from .autoeq import BandSetting, apply_bands, parse_autoeq_csv, parse_autoeq_csv_text
 from ._ffi import OhsError
 
 __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter", "ConvolutionEngine",
            "ConvolutionPath", "FilterType", "StereoParametricEQ", "biquad_coefficients",
            "process_chain", "BatchProcessor", "NodeBatchProcessor", "OhsError", "BandSetting", "apply_bands",
-           "parse_autoeq_csv", "parse_autoeq_csv_text", "LAYOUT_5_1", "LAYOUT_7_1"]
+           "parse_autoeq_csv", "parse_autoeq_csv_text", "LAYOUT_5_1", "LAYOUT_7_1", "SessionRenderer",
+           "HeadTrack", "nearest_set", "yaw_rows", "plan_calls", "render_files"]
