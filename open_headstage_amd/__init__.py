@@ -10,6 +10,7 @@ from .dsp import (BLOCK_SIZE, FFT_SIZE, NUM_EQ_BANDS, BandConfig, BiquadFilter, 
                   FilterType, StereoParametricEQ, biquad_coefficients, process_chain)
 from .batch import LAYOUT_5_1, LAYOUT_7_1, BatchProcessor, NodeBatchProcessor
 from .session import HeadTrack, SessionRenderer, nearest_set, plan_calls, render_files, yaw_rows
+from .pcm import WavReader, pcm_decode_device, pcm_encode_device
 from .autoeq import BandSetting, apply_bands, parse_autoeq_csv, parse_autoeq_csv_text
 from ._ffi import OhsError
 
@@ -17,4 +18,5 @@ __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter
            "ConvolutionPath", "FilterType", "StereoParametricEQ", "biquad_coefficients",
            "process_chain", "BatchProcessor", "NodeBatchProcessor", "OhsError", "BandSetting", "apply_bands",
            "parse_autoeq_csv", "parse_autoeq_csv_text", "LAYOUT_5_1", "LAYOUT_7_1", "SessionRenderer",
-           "HeadTrack", "nearest_set", "yaw_rows", "plan_calls", "render_files"]
+           "HeadTrack", "nearest_set", "yaw_rows", "plan_calls", "render_files", "WavReader", "pcm_decode_device",
+           "pcm_encode_device"]

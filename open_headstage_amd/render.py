@@ -1,10 +1,10 @@
 """python -m open_headstage_amd.render: WAV stems, a SOFA file and head-tracker logs -> binaural WAVs.
 
     python -m open_headstage_amd.render --sofa F --layout 5.1|7.1|stereo --yaw-step 5 [--track T.csv ...] [--late late.wav]
-                                        -o OUTDIR IN.wav ...
+                                        [--out-bits 16|24|32] -o OUTDIR IN.wav ...
 
 One input file per stream (PCM 16 / 24 / 32, all of one rate; 6, 8 or 2 channels in WAV order), one output file of the same name in
-OUTDIR.  --track: `time_s,yaw_deg` lines, yaw positive to the right; one file for all streams or one per input; none: the head
+OUTDIR, of its input's sample width or of --out-bits.  --track: `time_s,yaw_deg` lines, yaw positive to the right; one file for all streams or one per input; none: the head
 looks ahead.  --late: a four-channel WAV [Lsl, Lsr, Rsl, Rsr] holding the static late part of the room's response from tap 512 on
 (stereo only).  The table holds one set per --yaw-step degrees around the circle."""
 from __future__ import annotations
@@ -27,14 +27,13 @@ def _parser():
     p.add_argument("--chunk-blocks", type=int, default=64, help="blocks per pipeline chunk (default 64)")
     p.add_argument("--no-crossfade", action="store_true", help="let the old set ring out instead of fading")
     p.add_argument("--no-ring-out", action="store_true", help="cut every output at its input's length")
+    p.add_argument("--out-bits", type=int, choices=[16, 24, 32], help="bits per sample of the outputs (default: the inputs' width)")
     p.add_argument("--device", type=int, default=0)
     return p
 
 
 def main(argv=None) -> int:
     a = _parser().parse_args(argv)
-    import wave
-
     import numpy as np
 
     from . import session
@@ -45,8 +44,8 @@ def main(argv=None) -> int:
         raise SystemExit("--yaw-step: between 0 and 360 degrees")
     if a.track and len(a.track) not in (1, len(a.inputs)):
         raise SystemExit("--track: one log for all streams, or one per input")
-    with wave.open(a.inputs[0], "rb") as w:
-        fs = float(w.getframerate())
+    with session.WavReader(a.inputs[0]) as w:
+        fs = float(w.rate)
     grid = np.arange(-180.0, 180.0, a.yaw_step)
     kw = dict(seg_blocks=a.seg_blocks, chunk_blocks=a.chunk_blocks, crossfade=not a.no_crossfade, fs=fs, device=a.device)
     sofa = MySofa(a.sofa)
@@ -68,7 +67,7 @@ def main(argv=None) -> int:
     outs = [os.path.join(a.outdir, os.path.basename(p)) for p in a.inputs]
     if len(set(outs)) != len(outs):
         raise SystemExit("two inputs share a file name: their outputs would collide")
-    n = session.render_files(a.inputs, outs, r, tracks, ring_out=not a.no_ring_out)
+    n = session.render_files(a.inputs, outs, r, tracks, ring_out=not a.no_ring_out, out_bits=a.out_bits)
     for p, k in zip(outs, n):
         print(f"{p}: {k} frames")
     return 0

@@ -11,20 +11,25 @@ sum of the late part.
   streams so that they overlap (measured: tools/bench_session.py); two pinned staging pairs and two device
   pairs of `chunk_blocks` blocks are allocated at construction, so neither device
   nor pinned memory grows with the session.
+  `render_pcm` is the same pipeline with integer PCM over the link: the codec of pcm.py runs on the compute stream in front of and
+  behind the kernels.
 * `render_files`, PCM and tracker-CSV helpers: one WAV per stream, read and written chunk by chunk.
 """
 from __future__ import annotations
 
 import math
+import queue
+import threading
 import wave
 
 import numpy as np
 
 from .batch import LAYOUT_5_1, LAYOUT_7_1, BatchProcessor
 from .dsp import BLOCK_SIZE
+from .pcm import PCM_BITS, WavReader, pcm_decode_device, pcm_dtype, pcm_encode_device, pcm_shape
 
 __all__ = ["HeadTrack", "nearest_set", "yaw_rows", "plan_calls", "call_rows", "SessionRenderer", "render_files", "pcm_decode",
-           "pcm_encode", "read_track_csv"]
+           "pcm_encode", "read_track_csv", "pcm_decode_device", "pcm_encode_device", "WavReader"]
 
 
 # ---- 1. head tracks to table rows --------------------------------------------------------------------------------------------------
@@ -175,6 +180,8 @@ class SessionRenderer:
         self._last = None           # every stream's last set [n_streams], None at the session's start
         self._finished = False
         self._broken = False        # a render() failed behind its first queued chunk: the handles' state is ahead of _pos
+        self._pcm = None            # render_pcm's device buffers, allocated by its first call
+        self._bytes_in = self._bytes_out = 0
 
     # -- constructors ---------------------------------------------------------------------
     @classmethod
@@ -305,6 +312,7 @@ class SessionRenderer:
         for sl in self._slots:
             sl.pending = None
         self._pos, self._last, self._finished, self._broken = 0, None, False, False
+        self._bytes_in = self._bytes_out = 0
 
     def _rows_of_call(self, yaw, rows, n_blocks, n_given):
         """the validated session rows of this call, [n_segs] or [n_streams][n_segs]: n_given segments must be there, the segments
@@ -350,17 +358,113 @@ class SessionRenderer:
         if not is_np and not isinstance(x, torch.Tensor):
             x = np.asarray(x, np.float32)
             is_np = True
+        self._check_session(yaw, rows)
+        if x.ndim != 3 or x.shape[0] != self.n_streams or x.shape[1] != self.channels:
+            raise ValueError(f"expected x [{self.n_streams}][{self.channels}][frames], got {tuple(x.shape)}")
+        if (x.dtype != np.float32) if is_np else (x.dtype != torch.float32 or x.is_cuda):
+            raise TypeError("x must be float32 host audio")
+        frames = int(x.shape[2])
+        out_frames, n_blocks, sess_rows, last = self._plan_call(frames, yaw, rows, prev, final, ring_out)
+        if out is None:
+            out = np.empty((self.n_streams, 2, out_frames), np.float32) if is_np else torch.empty((self.n_streams, 2, out_frames), dtype=torch.float32)
+        elif tuple(out.shape) != (self.n_streams, 2, out_frames) or isinstance(out, np.ndarray) != is_np \
+                or (out.dtype != np.float32 if is_np else (out.dtype != torch.float32 or out.is_cuda)):
+            raise ValueError(f"out: a float32 host array [{self.n_streams}][2][{out_frames}] of x's kind")
+        if n_blocks == 0:
+            return out
+        xt = torch.from_numpy(x) if is_np else x
+        ot = torch.from_numpy(out) if is_np else out
+        self._run(xt, ot, frames, out_frames, n_blocks, sess_rows, last, final, None)
+        return out
+
+    def render_pcm(self, x, yaw=None, rows=None, prev=None, final=False, ring_out=False, out=None, out_bits=None):
+        """render() on integer PCM, with integers over the link.  x: HOST PCM in WAV frame order, numpy or a torch host tensor:
+        int16 [n_streams][frames][K or 2] (16-bit), int32 of that shape (32-bit) or uint8 [n_streams][frames][K or 2][3] (24-bit,
+        packed, little-endian) -> [n_streams][out_frames][2] of the same kind, of the out_bits kind (16, 24 or 32) when given, or
+        `out` when given and of exactly that kind and shape.  Blocking.
+
+        Bit for bit, per stream, pcm_encode(render(pcm_decode(x)), out_bits) with the same yaw / rows / prev / final / ring_out:
+        everything render() documents holds, and the two may alternate within one session -- position, last set and the handles'
+        state are shared.  Decode is int / 2^(bits - 1); encode is round-half-even, clip, no dither.
+
+        The pipeline is render()'s: the chunk's frames are copied as PCM bytes into the slot's pinned staging buffer (the float one,
+        viewed as bytes: PCM is never wider), copy-in lands them in a device PCM buffer, pcm_decode_device writes the slot's float
+        input on the compute stream in front of the kernels (frames behind the input's end are zeroed there and never cross the
+        link), pcm_encode_device writes the device PCM output behind them, copy-out moves those bytes and the drain copies them
+        into the result.  A pinned tensor whose chunk slice is contiguous (a call of one chunk) is copied to the device as it is.
+
+        Memory: the first render_pcm() allocates, once and for the widest format, two device PCM pairs and the codec's scratch
+        (an int32 word per input sample for 24-bit input; a float64 and an int32 word per output sample):
+        (12 C + 40) S chunk_blocks 512 bytes on top of render()'s (8 C + 16) S chunk_blocks 512, (20 C + 56) S chunk_blocks 512
+        in all; no pinned memory is added.  A renderer that only calls render() allocates what it always did."""
+        torch = self._torch
+        is_np = isinstance(x, np.ndarray)
+        if not is_np and not isinstance(x, torch.Tensor):
+            x = np.asarray(x)
+            is_np = True
+        self._check_session(yaw, rows)
+        bits = self._pcm_kind(x, is_np, "x", self.channels)
+        frames = int(x.shape[1])
+        if out_bits is None:
+            out_bits = bits
+        elif out_bits not in PCM_BITS:
+            raise ValueError(f"out_bits {out_bits!r}: 16, 24 or 32")
+        out_frames, n_blocks, sess_rows, last = self._plan_call(frames, yaw, rows, prev, final, ring_out)
+        shape = pcm_shape(out_bits, self.n_streams, out_frames, 2)
+        if out is None:
+            out = np.empty(shape, pcm_dtype(np, out_bits)) if is_np else torch.empty(shape, dtype=pcm_dtype(torch, out_bits))
+        elif isinstance(out, np.ndarray) != is_np or not (is_np or isinstance(out, torch.Tensor)) or tuple(out.shape) != shape \
+                or self._pcm_kind(out, is_np, "out", 2) != out_bits:
+            raise ValueError(f"out: {out_bits}-bit host PCM {shape} of x's kind")
+        if n_blocks == 0:
+            return out
+        if self._pcm is None:
+            with torch.cuda.stream(self._s_comp):       # the stream that decodes: the fill of word_in is ordered in front of it
+                self._pcm = _PcmBuffers(torch, self.n_streams, self.channels, self.chunk_blocks * BLOCK_SIZE, self._dev)
+        xt = torch.from_numpy(x) if is_np else x
+        ot = torch.from_numpy(out) if is_np else out
+        self._run(xt, ot, frames, out_frames, n_blocks, sess_rows, last, final, (bits, out_bits))
+        return out
+
+    @property
+    def link_bytes(self):
+        """(bytes_in, bytes_out) queued over the link since construction or reset(), by render() and render_pcm() alike: what the
+        copies really carry.  render() moves every chunk whole, zero padding and ring-out included, four bytes per sample;
+        render_pcm() moves the frames the input holds in and the frames that are kept out.  So on calls of whole blocks without
+        ring-out the 16-bit figures are exactly half of render()'s and the 24-bit ones three quarters; on a ragged or ring-out
+        call render_pcm() moves less than that."""
+        return self._bytes_in, self._bytes_out
+
+    def _pcm_kind(self, a, is_np, what, channels):
+        """the sample width of host PCM `a`, [n_streams][frames][channels] int16 / int32 or [...][3] uint8"""
+        torch = self._torch
+        if (np.issubdtype(a.dtype, np.floating) if is_np else a.dtype.is_floating_point):
+            raise TypeError(f"{what}: integer PCM; float audio is render()'s")
+        if not is_np and a.is_cuda:
+            raise TypeError(f"{what} must be host PCM")
+        i16, i32, u8 = (np.int16, np.int32, np.uint8) if is_np else (torch.int16, torch.int32, torch.uint8)
+        if a.ndim == 3 and a.dtype in (i16, i32):
+            bits = 16 if a.dtype == i16 else 32
+        elif a.ndim == 4 and a.dtype == u8 and a.shape[3] == 3:
+            bits = 24
+        else:
+            raise ValueError(f"{what}: int16 or int32 [n_streams][frames][channels], or uint8 [n_streams][frames][channels][3]; "
+                             f"got {a.dtype} {tuple(a.shape)}")
+        if a.shape[0] != self.n_streams or a.shape[2] != channels:
+            raise ValueError(f"expected {what} [{self.n_streams}][frames][{channels}], got {tuple(a.shape)}")
+        return bits
+
+    def _check_session(self, yaw, rows):
         if self._finished:
             raise ValueError("the session ended with a final call: reset() starts the next one")
         if self._broken:
             raise RuntimeError("an earlier render() failed midway, the handles' state is undefined: reset() starts a new session")
         if (yaw is None) == (rows is None):
             raise ValueError("give either yaw or rows")
-        if x.ndim != 3 or x.shape[0] != self.n_streams or x.shape[1] != self.channels:
-            raise ValueError(f"expected x [{self.n_streams}][{self.channels}][frames], got {tuple(x.shape)}")
-        if (x.dtype != np.float32) if is_np else (x.dtype != torch.float32 or x.is_cuda):
-            raise TypeError("x must be float32 host audio")
-        frames = int(x.shape[2])
+
+    def _plan_call(self, frames, yaw, rows, prev, final, ring_out):
+        """the checks of a call of `frames` frames that do not depend on the samples' format -> (out_frames, n_blocks, the session
+        rows of the call, every stream's set in front of it or None)"""
         if ring_out and not final:
             raise ValueError("ring_out belongs to the final call")
         if not final and frames % (self.seg_blocks * BLOCK_SIZE):
@@ -376,18 +480,13 @@ class SessionRenderer:
             if pv.size not in (1, self.n_streams) or pv.min() < 0 or pv.max() >= self.yaw_grid.size:
                 raise ValueError(f"prev: one index or {self.n_streams}, each below {self.yaw_grid.size}")
             last = np.broadcast_to(pv.astype(np.uint32), (self.n_streams,)).copy()
-        if out is None:
-            out = np.empty((self.n_streams, 2, out_frames), np.float32) if is_np else torch.empty((self.n_streams, 2, out_frames), dtype=torch.float32)
-        elif tuple(out.shape) != (self.n_streams, 2, out_frames) or isinstance(out, np.ndarray) != is_np \
-                or (out.dtype != np.float32 if is_np else (out.dtype != torch.float32 or out.is_cuda)):
-            raise ValueError(f"out: a float32 host array [{self.n_streams}][2][{out_frames}] of x's kind")
-        if n_blocks == 0:
-            return out
+        return out_frames, n_blocks, sess_rows, last
+
+    def _run(self, xt, ot, frames, out_frames, n_blocks, sess_rows, last, final, fmt):
+        """queue the planned calls of one render() / render_pcm() (fmt: None or (bits in, bits out)), drain, advance the session"""
         # one row for all streams stays one row (the kernels' cheapest case) while every stream has the same set in front of it
         if sess_rows.ndim == 1 and last is not None and (last != last[0]).any():
             sess_rows = np.ascontiguousarray(np.broadcast_to(sess_rows, (self.n_streams, sess_rows.size)))
-        xt = torch.from_numpy(x) if is_np else x
-        ot = torch.from_numpy(out) if is_np else out
         first_seg = self._pos // self.seg_blocks
         try:
             for start, n, g, _ in plan_calls(self._pos, n_blocks, self.seg_blocks, self.chunk_blocks):
@@ -396,7 +495,7 @@ class SessionRenderer:
                     pv = sess_rows[..., (start - 1) // self.seg_blocks - first_seg]
                 else:
                     pv = None if last is None else (last if sess_rows.ndim == 2 else last[0])
-                self._chunk(xt, ot, (start - self._pos) * BLOCK_SIZE, n, g, idx, pv, frames, out_frames)
+                self._chunk(xt, ot, (start - self._pos) * BLOCK_SIZE, n, g, idx, pv, frames, out_frames, fmt)
             self._drain_all(ot)
         except BaseException:
             self._broken = True                         # overlaps and EQ state are ahead of _pos and _last
@@ -407,38 +506,37 @@ class SessionRenderer:
         self._pos += n_blocks
         self._last = np.broadcast_to(sess_rows[..., -1], (self.n_streams,)).astype(np.uint32)
         self._finished = bool(final)
-        return out
 
     # -- the pipeline -----------------------------------------------------------------------
-    def _chunk(self, xt, ot, f0, n_blocks, g, idx, prev, in_frames, out_frames):
+    def _chunk(self, xt, ot, f0, n_blocks, g, idx, prev, in_frames, out_frames, fmt):
         """queue one planned call: frames [f0, f0 + n_blocks 512) of this render() call"""
         torch = self._torch
         S, C = self.n_streams, self.channels
         n = n_blocks * BLOCK_SIZE
-        sl = self._slots[self._turn % 2]
+        turn = self._turn % 2
+        sl = self._slots[turn]
         self._turn += 1
         have = max(0, min(n, in_frames - f0))          # frames of x in this chunk; the rest is padding and ring-out
-        src = xt[:, :, f0:f0 + have]
+        keep = max(0, min(n, out_frames - f0))
         d_in = sl.d_in[:S * C * n].view(S, C, n)
-        direct = have == n and src.is_contiguous() and src.is_pinned()
-        if not direct:
-            sl.ev_in.synchronize()                      # the copy that last read h_in is done
-            h_in = sl.h_in[:S * C * n].view(S, C, n)
-            h_in[:, :, :have].copy_(src)
-            if have < n:
-                h_in[:, :, have:].zero_()
-            src = h_in
         in_place = sl.d_out is None
-        with torch.cuda.stream(self._s_in):
-            self._s_in.wait_event(sl.ev_comp)           # the kernels that last read d_in are done
-            if in_place:
-                self._s_in.wait_event(sl.ev_out)        # ... and so is the copy-out of what they left there
-            d_in.copy_(src, non_blocking=True)
-            sl.ev_in.record(self._s_in)
         d_res = d_in if in_place else sl.d_out[:S * 2 * n].view(S, 2, n)
+        if fmt is None:
+            self._copy_in(sl, xt[:, :, f0:f0 + have], d_in, have, in_place)
+        else:
+            pb = self._pcm
+            w_out = fmt[1] // 8
+            raw = self._copy_in_pcm(sl, turn, xt[:, f0:f0 + have], have, fmt[0])
         with torch.cuda.stream(self._s_comp):
             self._s_comp.wait_event(sl.ev_in)
-            self._s_comp.wait_event(sl.ev_out)          # the copy-out that last read d_out is done
+            self._s_comp.wait_event(sl.ev_out)          # the copy-out that last read d_out (the device PCM output) is done
+            if fmt is not None:
+                if have:
+                    word = pb.word_in[:S * have * C].view(S, have, C) if fmt[0] == 24 else None
+                    pcm_decode_device(raw, fmt[0], d_in[:, :, :have], word)
+                if have < n:
+                    d_in[:, :, have:].zero_()
+                pb.ev_dec[turn].record(self._s_comp)
             hs = self._s_comp.cuda_stream
             if self.mode == "layout":
                 self.batch.process_layout_scheduled_ptr(d_in.data_ptr(), d_res.data_ptr(), n_blocks, C * n, n, 2 * n, n, g, idx,
@@ -452,33 +550,98 @@ class SessionRenderer:
                     self.batch.process_ir_scheduled_ptr(d_in.data_ptr(), d_in.data_ptr(), n_blocks, 2 * n, n, g, idx, "ring_out", hs)
                 if self.late_batch is not None:
                     d_res.add_(d_in)
+            if fmt is not None and keep:
+                d_pcm = pb.d_out[turn][:S * keep * 2 * w_out].view(pcm_dtype(torch, fmt[1])).view(pcm_shape(fmt[1], S, keep, 2))
+                pcm_encode_device(d_res[:, :, :keep], fmt[1], d_pcm, pb.f64[:S * 2 * keep].view(S, 2, keep),
+                                  pb.word_out[:S * keep * 2].view(S, keep, 2) if fmt[1] == 24 else None)
             sl.ev_comp.record(self._s_comp)
         self._drain(sl, ot)                             # h_out still holds the chunk two turns back
-        keep = max(0, min(n, out_frames - f0))
         with torch.cuda.stream(self._s_out):
             self._s_out.wait_event(sl.ev_comp)
-            sl.h_out[:S * 2 * n].copy_(d_res.reshape(-1), non_blocking=True)
+            if fmt is None:
+                sl.h_out[:S * 2 * n].copy_(d_res.reshape(-1), non_blocking=True)
+                self._bytes_out += 4 * S * 2 * n
+            elif keep:
+                nb = S * keep * 2 * w_out
+                sl.h_out.view(torch.uint8)[:nb].copy_(pb.d_out[turn][:nb], non_blocking=True)
+                self._bytes_out += nb
             sl.ev_out.record(self._s_out)
-        sl.pending = (f0, n, keep)
+        sl.pending = (f0, n, keep, None if fmt is None else fmt[1])
+
+    def _copy_in(self, sl, src, d_in, have, in_place):
+        """float audio: the chunk's slice of x, zero-padded to the chunk, into the slot's device input"""
+        S, C, n = d_in.shape
+        direct = have == n and src.is_contiguous() and src.is_pinned()
+        if not direct:
+            sl.ev_in.synchronize()                      # the copy that last read h_in is done
+            h_in = sl.h_in[:S * C * n].view(S, C, n)
+            h_in[:, :, :have].copy_(src)
+            if have < n:
+                h_in[:, :, have:].zero_()
+            src = h_in
+        with self._torch.cuda.stream(self._s_in):
+            self._s_in.wait_event(sl.ev_comp)           # the kernels that last read d_in are done
+            if in_place:
+                self._s_in.wait_event(sl.ev_out)        # ... and so is the copy-out of what they left there
+            d_in.copy_(src, non_blocking=True)
+            sl.ev_in.record(self._s_in)
+        self._bytes_in += 4 * S * C * n
+
+    def _copy_in_pcm(self, sl, turn, src, have, bits):
+        """PCM: the `have` frames of x in this chunk, as they are, into the slot's device PCM input -> that input's view"""
+        torch = self._torch
+        S, C = self.n_streams, self.channels
+        nb = S * have * C * (bits // 8)
+        raw = self._pcm.d_in[turn][:nb].view(pcm_dtype(torch, bits)).view(pcm_shape(bits, S, have, C))
+        if have and not (src.is_contiguous() and src.is_pinned()):
+            sl.ev_in.synchronize()                      # the copy that last read h_in is done
+            h_in = sl.h_in.view(torch.uint8)[:nb].view(raw.dtype).view(raw.shape)
+            h_in.copy_(src)
+            src = h_in
+        with torch.cuda.stream(self._s_in):
+            if have:
+                self._s_in.wait_event(self._pcm.ev_dec[turn])       # the decode that last read the device PCM input is done
+                raw.copy_(src, non_blocking=True)
+            sl.ev_in.record(self._s_in)
+        self._bytes_in += nb
+        return raw
 
     def _drain(self, sl, ot):
         if sl.pending is None:
             return
-        f0, n, keep = sl.pending
+        f0, n, keep, bits = sl.pending
         sl.pending = None
         sl.ev_out.synchronize()
-        if keep:
-            ot[:, :, f0:f0 + keep].copy_(sl.h_out[:self.n_streams * 2 * n].view(self.n_streams, 2, n)[:, :, :keep])
+        S = self.n_streams
+        if not keep:
+            return
+        if bits is None:
+            ot[:, :, f0:f0 + keep].copy_(sl.h_out[:S * 2 * n].view(S, 2, n)[:, :, :keep])
+        else:
+            ot[:, f0:f0 + keep].copy_(sl.h_out.view(self._torch.uint8)[:S * keep * 2 * (bits // 8)].view(ot.dtype)
+                                      .view(pcm_shape(bits, S, keep, 2)))
 
     def _drain_all(self, ot):
         for k in (self._turn, self._turn + 1):          # the older chunk first
             self._drain(self._slots[k % 2], ot)
 
 
+class _PcmBuffers:
+    """what render_pcm adds to the two slots, sized for 32-bit samples: a device PCM pair and a decode event per slot; one int32
+    word per input sample (24-bit decode; its low bytes stay zero), one float64 and one int32 word per output sample (encode).
+    The scratch is touched on the compute stream only, so one copy serves both slots.  Built with the compute stream current:
+    the zero fill of word_in is then in front of the first decode in stream order."""
+
+    def __init__(self, torch, S, C, chunk, device):
+        self.d_in = [torch.empty(4 * S * C * chunk, dtype=torch.uint8, device=device) for _ in range(2)]
+        self.d_out = [torch.empty(4 * S * 2 * chunk, dtype=torch.uint8, device=device) for _ in range(2)]
+        self.ev_dec = [torch.cuda.Event(), torch.cuda.Event()]
+        self.word_in = torch.zeros(S * C * chunk, dtype=torch.int32, device=device)
+        self.f64 = torch.empty(S * 2 * chunk, dtype=torch.float64, device=device)
+        self.word_out = torch.empty(S * 2 * chunk, dtype=torch.int32, device=device)
+
+
 # ---- 4. files ----------------------------------------------------------------------------------------------------------------------
-PCM_BITS = (16, 24, 32)
-
-
 def pcm_decode(data: bytes, bits: int, channels: int) -> np.ndarray:
     """little-endian signed PCM frames -> float32 [channels][frames], value = int / 2^(bits - 1)"""
     if bits not in PCM_BITS:
@@ -509,9 +672,8 @@ def pcm_encode(x, bits: int) -> bytes:
 
 def read_wav(path):
     """a whole PCM WAV -> (float32 [channels][frames], rate, bits)"""
-    with wave.open(str(path), "rb") as w:
-        bits, ch = 8 * w.getsampwidth(), w.getnchannels()
-        return pcm_decode(w.readframes(w.getnframes()), bits, ch), w.getframerate(), bits
+    with WavReader(path) as w:
+        return pcm_decode(w.readframes(w.frames), w.bits, w.channels), w.rate, w.bits
 
 
 def write_wav(path, x, rate, bits=16):
@@ -547,44 +709,56 @@ def read_track_csv(path) -> HeadTrack:
 CALL_CHUNKS = 4     # chunks per render() call of render_files
 
 
-def render_files(inputs, outputs, renderer, tracks=None, ring_out=True):
-    """One PCM WAV per stream (16 / 24 / 32-bit integer; stdlib `wave`) through `renderer`, from the session's start (it is reset
-    first).  All files have the renderer's rate and channel count; lengths may differ: shorter files are padded with silence (a
-    track holds its last value behind its log) and each output is trimmed to its own length, plus the reach when ring_out.  The
-    outputs are two-channel files of the inputs' sample width.  tracks: None (yaw 0), one HeadTrack, or one per stream.
+def render_files(inputs, outputs, renderer, tracks=None, ring_out=True, out_bits=None, pcm=None):
+    """One PCM WAV per stream (16 / 24 / 32-bit integer; format tag 1 or WAVE_FORMAT_EXTENSIBLE: pcm.WavReader) through `renderer`,
+    from the session's start (it is reset first).  All files have the renderer's rate and channel count; lengths may differ:
+    shorter files are padded with silence (a track holds its last value behind its log) and each output is trimmed to its own
+    length, plus the reach when ring_out.  The outputs are two-channel files (stdlib `wave`) of out_bits (16, 24 or 32) per sample;
+    None: of their input's sample width.  tracks: None (yaw 0), one HeadTrack, or one per stream.
 
     Decode is int / 2^(bits - 1); encode is round-half-even, clip, NO dither (pcm_encode).  Files are read and written
-    CALL_CHUNKS * chunk_blocks blocks at a time: host memory does not hold a session either.  -> frames written per output."""
+    CALL_CHUNKS * chunk_blocks blocks at a time: host memory does not hold a session either.  -> frames written per output.
+
+    pcm: None -- where all inputs share one sample width, the file bytes go as they are through render_pcm (the codec runs on the
+    device, a reader thread fetches the next call's frames and a writer thread writes the previous call's output while the
+    current call renders; at most two calls' worth of PCM per direction is held); inputs of mixed widths take the float path.
+    False: the float path, always: pcm_decode and pcm_encode on the host around render().  True: the PCM path; mixed widths are
+    a ValueError.  Both paths write the same bytes."""
     S = renderer.n_streams
     if len(inputs) != S or len(outputs) != S:
         raise ValueError(f"one input and one output per stream: {S}")
+    if out_bits is not None and out_bits not in PCM_BITS:
+        raise ValueError(f"out_bits {out_bits!r}: 16, 24 or 32")
     if tracks is None:
         tracks = HeadTrack([0.0], [0.0])
     ins, outs = [], []
     try:
         for p in inputs:
-            w = wave.open(str(p), "rb")
+            w = WavReader(p)
             ins.append(w)
-            if w.getframerate() != renderer.fs:
-                raise ValueError(f"{p}: rate {w.getframerate()}, the renderer runs at {renderer.fs:g}")
-            if w.getnchannels() != renderer.channels:
-                raise ValueError(f"{p}: {w.getnchannels()} channels, the renderer takes {renderer.channels}")
-            if 8 * w.getsampwidth() not in PCM_BITS or w.getcomptype() != "NONE":
-                raise ValueError(f"{p}: 16, 24 or 32-bit integer PCM only")
-        lens = [w.getnframes() for w in ins]
+            if w.rate != renderer.fs:
+                raise ValueError(f"{p}: rate {w.rate}, the renderer runs at {renderer.fs:g}")
+            if w.channels != renderer.channels:
+                raise ValueError(f"{p}: {w.channels} channels, the renderer takes {renderer.channels}")
+        lens = [w.frames for w in ins]
         total = max(lens)
         if total == 0:
             raise ValueError("the inputs are empty")
+        one_width = len({w.bits for w in ins}) == 1
+        if pcm and not one_width:
+            raise ValueError("pcm=True: the inputs hold samples of different widths")
         reach = renderer.reach if ring_out else 0
         for p, w in zip(outputs, ins):
             o = wave.open(str(p), "wb")
             outs.append(o)
             o.setnchannels(2)
-            o.setsampwidth(w.getsampwidth())
-            o.setframerate(w.getframerate())
+            o.setsampwidth((out_bits or w.bits) // 8)
+            o.setframerate(w.rate)
         renderer.reset()
         seg = renderer.seg_blocks
         call_frames = max(1, CALL_CHUNKS * renderer.chunk_blocks // seg) * seg * BLOCK_SIZE
+        if one_width and (pcm or pcm is None):
+            return _render_files_pcm(ins, outs, renderer, tracks, ring_out, lens, reach, call_frames, out_bits or ins[0].bits)
         x = np.zeros((S, renderer.channels, call_frames), np.float32)
         pos, written = 0, [0] * S
         while pos < total:
@@ -593,7 +767,7 @@ def render_files(inputs, outputs, renderer, tracks=None, ring_out=True):
             for s, w in enumerate(ins):
                 have = max(0, min(n, lens[s] - pos))
                 if have:
-                    x[s, :, :have] = pcm_decode(w.readframes(have), 8 * w.getsampwidth(), renderer.channels)
+                    x[s, :, :have] = pcm_decode(w.readframes(have), w.bits, renderer.channels)
                 x[s, :, have:n] = 0.0
             y = renderer.render(x[:, :, :n], yaw=tracks, final=final, ring_out=final and ring_out)
             for s, o in enumerate(outs):
@@ -606,3 +780,74 @@ def render_files(inputs, outputs, renderer, tracks=None, ring_out=True):
     finally:
         for w in ins + outs:
             w.close()
+
+
+def _render_files_pcm(ins, outs, renderer, tracks, ring_out, lens, reach, call_frames, out_bits):
+    """render_files through render_pcm.  Two host PCM arrays per direction go round: the reader thread fills one with the next
+    call's frames while the other renders; the writer thread empties one while the next call fills the other."""
+    S, C, bits, total = renderer.n_streams, renderer.channels, ins[0].bits, max(lens)
+    xs = [np.zeros(pcm_shape(bits, S, call_frames, C), pcm_dtype(np, bits)) for _ in range(2)]
+    ys = [np.empty(pcm_shape(out_bits, S, call_frames + reach, 2), pcm_dtype(np, out_bits)) for _ in range(2)]
+    calls = [(pos, min(call_frames, total - pos)) for pos in range(0, total, call_frames)]
+    free_x, full_x, free_y, full_y = (queue.Queue() for _ in range(4))
+    for i in range(2):
+        free_x.put(i)
+        free_y.put(i)
+    errors, written = [], [0] * S
+
+    def reader():
+        try:
+            for pos, n in calls:
+                i = free_x.get()
+                if i is None:
+                    return
+                for s, w in enumerate(ins):
+                    have = max(0, min(n, lens[s] - pos))
+                    if have and w.readinto(xs[i][s, :have], have) != have:
+                        raise ValueError(f"stream {s}: the file holds fewer frames than its header names")
+                    xs[i][s, have:n] = 0
+                full_x.put(i)
+        except BaseException as e:
+            errors.append(e)
+            full_x.put(None)
+
+    def writer():
+        failed = False
+        while True:
+            job = full_y.get()
+            if job is None:
+                return
+            i, pos, frames = job
+            try:
+                for s, o in enumerate(outs):
+                    k = max(0, min(frames, lens[s] + reach - pos))
+                    if k and not failed:
+                        o.writeframes(ys[i][s, :k])
+                        written[s] += k
+            except BaseException as e:              # keep handing the arrays back, so that the renderer never waits for ever
+                failed = True
+                errors.append(e)
+            free_y.put(i)
+
+    threads = [threading.Thread(target=reader, name="render_files reader"), threading.Thread(target=writer, name="render_files writer")]
+    for t in threads:
+        t.start()
+    try:
+        for pos, n in calls:
+            i = full_x.get()
+            if i is None or errors:
+                break
+            j = free_y.get()
+            final = pos + n == total
+            y = renderer.render_pcm(xs[i][:, :n], yaw=tracks, final=final, ring_out=final and ring_out,
+                                    out=ys[j][:, :n + (reach if final else 0)], out_bits=out_bits)
+            free_x.put(i)
+            full_y.put((j, pos, y.shape[1]))
+    finally:
+        free_x.put(None)
+        full_y.put(None)
+        for t in threads:
+            t.join()
+    if errors:
+        raise errors[0]
+    return written
