@@ -47,7 +47,9 @@ def _signals(synth, S, first_id, frames):
                                          (1024, [128, 7, 150])])
 def test_block_8192_kernel_matches_the_oracle_and_f64(oracle, taps, blocks):
     """long calls take the block-8192 kernel, short ones in between the block-2048 plan: each continues from the input history the
-    other leaves; call lengths that end inside an 8192-frame block (zeros behind the call, nothing stored there)"""
+    other leaves; call lengths that end inside an 8192-frame block (zeros behind the call, nothing stored there: that no word is
+    stored behind, between or in front of the chains is checked by tests/test_gpu_conv_guard_bands.py::test_block_8192, on
+    sentinel-filled gaps around every chain)"""
     import torch
     import open_headstage_amd as ohs
     from open_headstage_amd import synth

@@ -15,6 +15,7 @@ import os
 import numpy as np
 import pytest
 
+from tests.guard_bands import SENT_OUT
 from tests.util import assert_parity
 
 pytestmark = pytest.mark.gpu
@@ -207,10 +208,18 @@ def test_fuzz_batch(ohs, synth, oracle, seed):
             buf = torch.full((S * ss_,), float("nan"), device="cuda")
             view = torch.as_strided(buf, (S, 2, n), (ss_, cs_, 1))
             view.copy_(xt)
-            obuf = torch.zeros_like(buf)
+            obuf = torch.full((S * ss_,), int(SENT_OUT) - (1 << 32), dtype=torch.int32, device="cuda").view(torch.float32)
             bp.process_ptr(buf.data_ptr(), obuf.data_ptr(), nblk, ss_, cs_,
                            torch.cuda.current_stream().cuda_stream)
             y = torch.as_strided(obuf, (S, 2, n), (ss_, cs_, 1)).cpu().numpy()
+            # the output's padding (behind every chain) still holds the sentinel: nothing was stored outside the chains
+            pad = np.ones(S * ss_, bool)
+            for s_ in range(S):
+                for c_ in range(2):
+                    pad[s_ * ss_ + c_ * cs_:s_ * ss_ + c_ * cs_ + n] = False
+            words = obuf.cpu().numpy().view(np.uint32)
+            hit = np.flatnonzero(pad & (words != SENT_OUT))
+            assert hit.size == 0, (seed, call, nblk, S, ss_, cs_, bp.last_conv_plan(), hit.size, [int(v) for v in hit[:6]])
         o = np.empty_like(y)
         for s in range(S):
             l, r = x[s, 0, pos:pos + n].copy(), x[s, 1, pos:pos + n].copy()
