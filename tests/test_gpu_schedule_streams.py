@@ -502,7 +502,9 @@ def test_mixed_scheduled_calls_share_the_staging_slots():
     calls are more than two turns of the four staging slots, and the last round's EQ call stages 3 x 384 x 2 = 2304 entries -- more
     than a fresh slot's 2048 --, so a slot earlier calls used is regrown while others are in flight.  The yardstick: the same calls
     with a sync() behind each, the six stereo calls on one handle and the three layout calls on another (the two states are
-    independent: test_gpu_layout_schedule.py's test_scheduled_layout_and_stereo_calls_do_not_touch_each_other).  Bit for bit."""
+    independent: test_gpu_layout_schedule.py's test_scheduled_layout_and_stereo_calls_do_not_touch_each_other).  Bit for bit.
+    (The handle's own table has no band enabled here; the EQ state that layout and stereo calls SHARE is checked against the oracle in
+    tests/test_gpu_fuzz_call_kinds.py.)"""
     import torch
     from open_headstage_amd import _ffi, synth
     from tests.test_cpu_ir_schedule import make_sets
