@@ -380,7 +380,32 @@ int  ohs_batch_set_gain(ohs_batch *b, float gain);
  *      convolution hides under the EQ either way, and the block-512 bits stay as recorded).  Longer responses: plan 2 for every
  *      call -- block 2048's blocks sit on the stream's absolute grid, so calls of any length continue one another, and the
  *      block-8192 kernel starts from the same state at rest (the streams' last input frames).
- * The single-stream engine is always served by the reference blocking. */
+ * The single-stream engine is always served by the reference blocking.
+ *
+ * Special values.  The convolution is linear and every product and sum is rounded on its own: a stream whose input is
+ * multiplied by 2^k leaves multiplied by 2^k bit for bit (nothing overflowing or becoming subnormal), and no stream's samples
+ * enter another stream's arithmetic at any level (tests/test_gpu_special_values.py holds every family and call kind to both).
+ * A non-finite INPUT sample (NaN, +Inf, -Inf) in block b of one stream -- blocks of 512 frames, counted over the stream's
+ * calls -- makes the reference's output of that stream non-finite in the blocks [b, b + Pmax], Pmax the partitions of 512 taps
+ * of the stream's longest path: its history holds the block for Pmax blocks and the overlap carries it one more
+ * (convolution.rs:258-284; a muted path is one partition of zeros there and answers 0 x NaN = NaN like any other).  Here:
+ *   - no other stream changes by a bit, ever;
+ *   - the stream is non-finite wherever the reference is, from the sample on, and differs from a clean run only inside
+ *     [b - back, b + Pmax + fwd], never in front of the call that holds b; behind that window it is bit-identical to a clean
+ *     run again (the state has drained; padded table rows and ring slots are skipped, never multiplied by their zeros), and
+ *     ohs_batch_reset clears whatever is left, as a new handle;
+ *   - back and fwd belong to the family that serves the calls -- a transform that spans F blocks is non-finite as a whole:
+ *       block 512 (one partition, time-parallel, sequential), the single-stream engine:   F = 1    back 0    fwd 0
+ *       hop 1536 (the sample's hop; the next one when its window reads the sample back):    F = 3    back 2    fwd 2
+ *       block 2048 (the 2048-frame block of the stream's grid with the sample, and the
+ *         ceil(Pmax / 4) blocks behind it):                             F = 4    back 3    fwd 4 ceil(Pmax / 4) + 3 - Pmax  (<= 6)
+ *       block 8192 (likewise, 8192-frame blocks counted from the call's start):
+ *                                                                       F = 16   back 15   fwd 16 ceil(Pmax / 16) + 15 - Pmax  (<= 30)
+ *     (1300 taps under block 2048: fwd 4; 8192 taps under block 8192: fwd 15.)  A per-path ohs_batch_set_ir behind such a
+ *     block carries the other paths' past on as pending tails, computed from the input history that holds the sample: the
+ *     same window holds for them, and no other stream sees them.
+ * With the EQ on, the recurrence keeps a non-finite sample for good (as the reference's does): see ohs_eq_process_block for
+ * where the stream's output becomes non-finite; every other stream stays bit-identical. */
 int  ohs_batch_set_conv_plan(ohs_batch *b, int plan);
 /* What served the handle's most recent convolution launch (of the last time chunk, when a call is cut into several): the
  * kernel family and the number of independent ranges a stream's frames were cut into for it (one-partition plans: time

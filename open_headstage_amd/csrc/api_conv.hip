@@ -310,6 +310,7 @@ static int conv_lb_prepare(ConvState &c, DeviceCtx *ctx, hipStream_t st, ConvLbA
     }
     std::memset(&a, 0, sizeof(a));
     a.tw = ctx->d_tw; a.tw4096 = ctx->d_tw4096; a.fp_mode = c.fp_mode; a.P2pad = P2pad;
+    a.P2 = std::min(P2pad, (conv_max_p(c) + 3) / 4);        // (the real partitions of 2048 taps: the padding is never multiplied)
 #ifdef OHS_EXPERIMENTS
     a.debug_skip = tuning().lb_skip;
 #endif
@@ -1287,7 +1288,7 @@ static int conv_run_tp(ConvState &c, DeviceCtx *ctx, const ConvCall &k, const Co
         a.in = k.in + done * BS; a.out = k.out + done * BS;
         a.in_stream_stride = k.in_ss; a.in_ch_stride = k.in_cs;
         a.out_stream_stride = k.out_ss; a.out_ch_stride = k.out_cs;
-        a.n_streams = (int)c.S; a.seg_blocks = seg; a.n_mac = seg; a.Ppad = Ppad;
+        a.n_streams = (int)c.S; a.seg_blocks = seg; a.n_mac = seg; a.Ppad = Ppad; a.Pmax = Pmax;
         a.CD = c.d_cdm; a.hist = c.d_hist; a.cap = c.cap; a.cnt = c.cnt + (unsigned long long)done;
         a.W = c.d_W; a.W1 = c.d_W1; a.tails = c.d_tails; a.tails_out = c.d_tails_alt;
         a.pairs = ctx->d_pairs; a.n_pairs = ctx->n_pairs;

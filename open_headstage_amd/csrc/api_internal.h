@@ -63,7 +63,8 @@ struct DeviceCtx {
 };
 int get_ctx(int device, DeviceCtx **out);
 
-// the MAC reads up to Ppad - 1 blocks back (zero C/D beyond the real partition count)
+// the MAC's register windows read up to Ppad - 1 blocks back (C/D are zero beyond the real partition count, and those
+// partitions are skipped, never multiplied: ConvTpArgs::Pmax)
 inline int Ppad_for_ring(int Pmax) { return (Pmax + 15) / 16 * 16; }
 
 inline int next_pow2(int v)

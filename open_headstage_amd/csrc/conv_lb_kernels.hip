@@ -260,7 +260,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_lb_mac_inverse(const ConvLbArgs
 #else
     constexpr int dskip = 0;
 #endif
-    for (int i0 = 0; i0 < ((dskip & 1) ? 0 : A.P2pad); i0 += PI) {
+    // Partitions P2 .. P2pad - 1 are padding (zero tables).  They are SKIPPED, not multiplied: a non-finite window spectrum in the ring
+    // times zero is NaN, and one bad input sample would answer for P2pad blocks of 2048 frames instead of P2.  Whole windows of PI real
+    // partitions run the register tile; the rest of them below the loop.
+    const int p2_whole = A.P2 / PI * PI;
+    for (int i0 = 0; i0 < ((dskip & 1) ? 0 : p2_whole); i0 += PI) {
         const __amdgpu_buffer_rsrc_t r_cd = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<float4 *>(A.cd) + (size_t)i0 * 2 * kLbPairs, 0, PI * 2 * (kLbPairs * 16), 0x00020000);
         // window of blocks t - i, t in [0, TB), i in [i0, i0 + PI): w = t - (i - i0) + PI - 1 in [0, PI + TB - 1)
@@ -326,6 +330,42 @@ __global__ __launch_bounds__(256, 2) void k_conv_lb_mac_inverse(const ConvLbArgs
                 products(p, o);
                 __builtin_amdgcn_sched_barrier(0);
             }
+        }
+    }
+    // The real partitions behind the last whole window, fewer than PI, one at a time: block t's window spectrum of partition i and
+    // the partition's two table rows per pair group (per accumulator the same partitions in the same order as the tile above).
+#pragma unroll 1
+    for (int i = ((dskip & 1) ? A.P2 : p2_whole); i < A.P2; ++i) {
+        const __amdgpu_buffer_rsrc_t r_cd = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float4 *>(A.cd) + (size_t)i * 2 * kLbPairs, 0, 2 * (kLbPairs * 16), 0x00020000);
+        int so[TB];
+        {
+            int sl = (int)((A.ring_base + tb0 - i) % A.ring_cap);      // block t's window of partition i: ring slot of window tb0 + t - i
+#pragma unroll
+            for (int t = 0; t < TB; ++t) {
+                so[t] = __builtin_amdgcn_readfirstlane(sl * (kLbPairs * 16));
+                sl = sl + 1 == A.ring_cap ? 0 : sl + 1;
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            lb_v4f zw[TB], cc[2];
+#pragma unroll
+            for (int t = 0; t < TB; ++t)
+                zw[t] = __builtin_bit_cast(lb_v4f, __builtin_amdgcn_raw_buffer_load_b128(r_ring, voff, so[t] + p * 4096, 0));
+#pragma unroll
+            for (int comp = 0; comp < 2; ++comp)
+                cc[comp] = __builtin_bit_cast(lb_v4f, __builtin_amdgcn_raw_buffer_load_b128(r_cd, voff, comp * (kLbPairs * 16) + p * 4096, 0));
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int comp = 0; comp < 2; ++comp)
+#pragma unroll
+                for (int t = 0; t < TB; ++t) {
+                    lb_v2f z = comp ? zw[t].hi : zw[t].lo, m = comp ? zw[t].lo : zw[t].hi;
+                    if (p == 0) m = special ? z : m;
+                    lb_cmac(acc[p][t][comp], z, cc[comp].lo, m, cc[comp].hi);
+                }
+            __builtin_amdgcn_sched_barrier(0);
         }
     }
     __syncthreads();            // (the twiddle tables are in place)
@@ -505,7 +545,7 @@ hipError_t launch_conv_lb_mac_inverse(const ConvLbArgs &a, hipStream_t st, int *
 {
     if (a.n_big <= 0) return hipSuccess;
     // the oldest window a tile reads is block 0's partition P2pad - 1; a tile's unused blocks read slots that alias others
-    if (!lb_args_ok(a) || !a.out || !a.cd || a.P2pad < 4 || (a.P2pad & 3) || a.n_big + a.P2pad - 1 > a.ring_cap ||
+    if (!lb_args_ok(a) || !a.out || !a.cd || a.P2pad < 4 || (a.P2pad & 3) || a.P2 < 1 || a.P2 > a.P2pad || a.n_big + a.P2pad - 1 > a.ring_cap ||
         a.ring_base - (a.P2pad - 1) - 8 < 0)
         return hipErrorInvalidValue;
     // output blocks per workgroup: 4, or as many as the call has (1 or 2: the short calls)

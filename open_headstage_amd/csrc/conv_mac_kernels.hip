@@ -89,7 +89,13 @@ __global__ __launch_bounds__(256) void k_conv_tp_mac(const ConvTpArgs A)
 #pragma unroll
     for (int t = 0; t < kTB; ++t) acc[t] = (v2f){0.f, 0.f};
 
-    for (int i0 = 0; i0 < A.Ppad; i0 += kPI) {
+    // Partitions Pmax .. Ppad - 1 are padding (zero C / D).  They are SKIPPED, not multiplied: a non-finite spectrum in the ring times
+    // zero is NaN, and one bad input sample would answer for Ppad blocks instead of Pmax.  The test is wave-uniform; every partition's
+    // C / D are requested one partition ahead of the test (the tables are allocated to Ppad: the loads stay inside them), so that no
+    // load waits behind a branch.  The 32-block tile sits at the register limit of two waves per SIMD and carries no test:
+    // launch_conv_tp_mac gives it whole windows of real partitions only.
+    const v2f *cd = reinterpret_cast<const v2f *>(A.CD);
+    for (int i0 = 0; i0 < A.Pmax; i0 += kPI) {
         // window of blocks u = t - i, t in [0,TB), i in [i0, i0+PI): w = (t - i) + i0 + PI - 1 in [0, TB+PI-1)
         v2f zw[kTB + kPI - 1], zm[kTB + kPI - 1];
 #pragma unroll
@@ -99,12 +105,29 @@ __global__ __launch_bounds__(256) void k_conv_tp_mac(const ConvTpArgs A)
             zw[w] = hs[b];
             zm[w] = hs[mb];
         }
+        if constexpr (kTB >= 32) {
 #pragma unroll
-        for (int ii = 0; ii < kPI; ++ii) {
-            const v2f c = reinterpret_cast<const v2f *>(A.CD)[((size_t)(i0 + ii) * 2 + 0) * kFft + b];
-            const v2f d = reinterpret_cast<const v2f *>(A.CD)[((size_t)(i0 + ii) * 2 + 1) * kFft + b];
+            for (int ii = 0; ii < kPI; ++ii) {
+                const v2f c = cd[((size_t)(i0 + ii) * 2 + 0) * kFft + b];
+                const v2f d = cd[((size_t)(i0 + ii) * 2 + 1) * kFft + b];
 #pragma unroll
-            for (int t = 0; t < kTB; ++t) cmac_z_c_conjm_d(acc[t], zw[t - ii + kPI - 1], c, zm[t - ii + kPI - 1], d);
+                for (int t = 0; t < kTB; ++t) cmac_z_c_conjm_d(acc[t], zw[t - ii + kPI - 1], c, zm[t - ii + kPI - 1], d);
+            }
+        } else {
+            v2f c = cd[((size_t)i0 * 2 + 0) * kFft + b], d = cd[((size_t)i0 * 2 + 1) * kFft + b];
+#pragma unroll
+            for (int ii = 0; ii < kPI; ++ii) {
+                v2f cn = c, dn = d;
+                if (ii + 1 < kPI) {
+                    cn = cd[((size_t)(i0 + ii + 1) * 2 + 0) * kFft + b];
+                    dn = cd[((size_t)(i0 + ii + 1) * 2 + 1) * kFft + b];
+                }
+                if (i0 + ii < A.Pmax) {
+#pragma unroll
+                    for (int t = 0; t < kTB; ++t) cmac_z_c_conjm_d(acc[t], zw[t - ii + kPI - 1], c, zm[t - ii + kPI - 1], d);
+                }
+                c = cn; d = dn;
+            }
         }
     }
 #pragma unroll
@@ -130,7 +153,8 @@ __device__ __forceinline__ void conv_tp_w1_job(const ConvTpArgs &A, int wg)
     const unsigned long long mask = (unsigned long long)(A.cap - 1);
     const unsigned long long last = A.cnt + (unsigned long long)(A.n_mac - 1);
     float2 acc1b = make_float2(0.f, 0.f), acc1m = make_float2(0.f, 0.f);
-    for (int i0 = 0; i0 < A.Ppad; i0 += 8) {       // Ppad is a multiple of 8: 48 loads in flight per step
+    for (int i0 = 0; i0 < A.Pmax; i0 += 8) {       // eight partitions' 48 loads in flight per step (the last step may reach into the
+                                                   // padding: Ppad is a multiple of 16, so its loads stay inside ring and tables)
         float2 zz[8], mm[8], cbv[8], dbv[8], cmv[8], dmv[8];
 #pragma unroll
         for (int ii = 0; ii < 8; ++ii) {
@@ -142,6 +166,7 @@ __device__ __forceinline__ void conv_tp_w1_job(const ConvTpArgs &A, int wg)
         }
 #pragma unroll
         for (int ii = 0; ii < 8; ++ii) {
+        if (i0 + ii >= A.Pmax) break;       // (padding: skipped, not multiplied by its zeros -- see the main job)
         const float2 z = zz[ii], m = mm[ii], cb = cbv[ii], db = dbv[ii], cm = cmv[ii], dm = dmv[ii];
         const float2 xlb = make_float2(0.5f * (z.x + m.x), 0.5f * (z.y - m.y));
         const float2 ab = make_float2(cb.x + db.x, cb.y + db.y);
@@ -172,8 +197,10 @@ static int mac_time_tile(int n)
 hipError_t launch_conv_tp_mac(const ConvTpArgs &a, hipStream_t st)
 {
     if (a.n_mac <= 0) return hipSuccess;
+    if (a.Pmax < 1 || a.Pmax > a.Ppad) return hipErrorInvalidValue;
     ConvTpArgs m = a;
-    const int kTB = mac_time_tile(a.n_mac);
+    int kTB = mac_time_tile(a.n_mac);
+    if (kTB == 32 && a.Pmax % kPI != 0) kTB = 16;       // (a last window with padding in it: the tiles that test every partition of a window)
     m.mac_tiles = (a.n_mac + kTB - 1) / kTB;
     const unsigned wps = (unsigned)(kFft / 256) * (unsigned)m.mac_tiles;
     const unsigned groups = ((unsigned)a.n_streams + 7u) / 8u;

@@ -342,7 +342,9 @@ struct ConvTpArgs {
     int n_streams;
     int seg_blocks;             // blocks whose spectra F writes
     int n_mac;                  // blocks M / I produce (= seg_blocks)
-    int Ppad;                   // partitions, padded to a multiple of 8 (CD zero beyond the real count)
+    int Ppad;                   // partitions, padded to a multiple of 16 (Ppad_for_ring; CD zero beyond the real count)
+    int Pmax;                   // the real count: partitions Pmax .. Ppad - 1 are SKIPPED, not multiplied (0 x NaN is NaN: a non-finite
+                                // block in the ring would answer for Ppad blocks instead of Pmax)
     const float2 *CD;           // [Ppad][2][1024] combined spectra C_i, D_i (bin layout)
     float2 *hist;               // [stream][cap][1024] ring
     int cap;
@@ -425,6 +427,8 @@ struct ConvLbArgs {
     int run;                    // F: consecutive windows per workgroup; 0 = the launcher's choice
     int n_big;                  // MI: output blocks 0 .. n_big - 1
     int P2pad;                  // 2048-tap partitions, padded to a multiple of 4 (zero tables beyond the real count)
+    int P2;                     // MI: the real count; partitions P2 .. P2pad - 1 are SKIPPED, not multiplied (0 x NaN is NaN: a non-finite
+                                // window in the ring would answer for P2pad blocks of 2048 instead of P2)
     float4 *ring;               // [stream][ring_cap][2048]: slot q = (Z[q], Z[4096 - q]), slot 0 = (Z[0], Z[2048])
     int ring_cap;
     long long ring_base;        // window u lives in ring slot (ring_base + u) % ring_cap; ring_base + u >= 0 for every u touched

@@ -356,3 +356,32 @@ def test_config4_shape_both_plans(oracle):
             e = _oracle_engines(oracle, irs, 1)[0]
             ref = np.stack(e.process_block(xs[s, 0], xs[s, 1]))
             assert_parity(yy[s].cpu().numpy(), ref, f"config 4, {name}, stream {s}")
+
+
+@pytest.mark.parametrize("plan,family,clean_from", [(0, "block2048", 16), (1, "block512_tp", 12)])
+def test_a_nan_sample_leaves_with_the_real_partitions_not_with_the_padding(plan, family, clean_from):
+    """1300 taps are 3 partitions of 512 taps (1 of 2048); the tables are padded with zeros to 16 (4 of 2048), and a product with a
+    padded partition is 0 x NaN = NaN: before the padding was skipped, one NaN sample in block 8 answered through block 24 (time-
+    parallel block 512) and 27 (block 2048) instead of 11 and 15 (include/ohs_hip.h: the reference's blocks 8 .. 11, plus the
+    2048-frame block behind).  The thorough version is tests/test_gpu_special_values.py."""
+    import torch
+    import open_headstage_amd as ohs
+    from open_headstage_amd import synth
+    S, calls = 2, (20, 12)
+    irs = synth.hrir_set(1300)
+    x = synth.white_noise(range(30, 30 + S), sum(calls) * 512)
+    xp = x.copy()
+    xp[0, 1, 8 * 512 + 100] = np.nan
+    outs = []
+    for sig in (xp, x):
+        bp, got, pos = _make(ohs, S, irs, plan), [], 0
+        for nb in calls:
+            got.append(bp.process(torch.from_numpy(np.ascontiguousarray(sig[:, :, pos:pos + nb * 512])).cuda()).cpu().numpy())
+            assert bp.last_conv_plan()[0] == family, bp.last_conv_plan()
+            pos += nb * 512
+        outs.append(np.concatenate(got, axis=2))
+    y, clean = outs
+    bad = sorted({int(f) // 512 for f in np.flatnonzero((y[0].view(np.uint32) != clean[0].view(np.uint32)).any(axis=0))})
+    print(f"{family}: a NaN in block 8 changes blocks {bad[0]} .. {bad[-1]}")
+    assert np.isnan(y[0][:, 8 * 512 + 100:12 * 512]).all() and bad[0] == 8 and bad[-1] < clean_from, bad
+    assert np.array_equal(y[1].view(np.uint32), clean[1].view(np.uint32))
