@@ -33,24 +33,69 @@ int eq_reset(EqState &e, hipStream_t st)
     return OHS_OK;
 }
 
+// The enabled bands of one table (coeffs [nb][5]; flags en8, or en32 where en8 is NULL) from band `start` on, in cascade order
+// and at most `cap` of them, as a pass table; -> how many it holds.  *next (optional): the first band not looked at.
+static int eq_compact_pass(size_t nb, const float *coeffs, const unsigned char *en8, const int *en32, size_t start, int cap,
+                           EqPassTable &t, size_t *next)
+{
+    std::memset(&t, 0, sizeof(t));
+    int k = 0;
+    size_t b = start, last = 0;
+    for (; b < nb && k < cap; ++b) {
+        if (en8 ? en8[b] == 0 : en32[b] == 0) continue;
+        t.slot[k] = (int)b;
+        t.b0[k] = coeffs[5 * b + 0]; t.b1[k] = coeffs[5 * b + 1]; t.b2[k] = coeffs[5 * b + 2];
+        t.a1[k] = coeffs[5 * b + 3]; t.a2[k] = coeffs[5 * b + 4];
+        last = b;
+        ++k;
+    }
+    for (int j = k; j < 16; ++j) t.slot[j] = (int)last;     // unused lanes shadow the last band's slot (never stored)
+    if (next) *next = b;
+    return k;
+}
+
 // the enabled bands, in cascade order, as ONE pass table; returns their number (the caller checks <= 16 / <= 12)
 int eq_single_pass_table(const EqState &e, EqPassTable &t)
 {
-    std::memset(&t, 0, sizeof(t));
-    int nbp = 0;
-    size_t last = 0;
-    for (size_t b = 0; b < e.nb; ++b) {
-        if (!e.en[b]) continue;
-        if (nbp < 16) {
-            t.slot[nbp] = (int)b;
-            t.b0[nbp] = e.coeffs[5 * b + 0]; t.b1[nbp] = e.coeffs[5 * b + 1]; t.b2[nbp] = e.coeffs[5 * b + 2];
-            t.a1[nbp] = e.coeffs[5 * b + 3]; t.a2[nbp] = e.coeffs[5 * b + 4];
-            last = b;
-        }
-        ++nbp;
-    }
-    for (int j = std::min(nbp, 16); j < 16; ++j) t.slot[j] = (int)last;    // unused lanes shadow the last band's slot (never stored)
+    size_t next = 0;
+    int nbp = eq_compact_pass(e.nb, e.coeffs.data(), nullptr, e.en.data(), 0, 16, t, &next);
+    for (size_t b = next; b < e.nb; ++b) nbp += e.en[b] != 0;
     return nbp;
+}
+
+// the XCDs the EQ's ring launches may use: the handle's (set per call by the batch), or the tuning's override
+static std::pair<int, int> eq_xcds(const EqState &e)
+{
+    if (tuning().eq_xcd_n > 0) return {tuning().eq_xcd_lo, tuning().eq_xcd_n};
+    return {e.xcd_lo, e.xcd_n};
+}
+
+// the ring forms (one launch for all streams, tables in device memory) may serve these frames
+static bool eq_ring_forms_serve(const EqState &e, long long ss, long long cs, long long n)
+{
+    return !e.exact_specials && !tuning().eq_conveyor && eq_ring_addressable(ss, cs, n);
+}
+
+// the scheduled kernels (k_eq_ring_sched, k_eq_ring_sched_streams: the wave ring, 32-bit sample counts per segment) may serve
+// n frames of a schedule whose tables have n_bands enabled bands
+static bool eq_sched_kernel_serves(const EqState &e, const BatchSchedule &sc, long long ss, long long cs, long long n, size_t n_bands)
+{
+    return sc.seg_blocks * BS < ((size_t)1 << 30) && eq_pass_takes_wave_ring(ss, cs, n, (int)e.chains, (int)n_bands, e.exact_specials);
+}
+
+// identity: the frames of `chains` chains still have to arrive in `out`
+static int eq_copy_through(const float *in, float *out, long long ss, long long cs, long long n, size_t chains, hipStream_t st)
+{
+    if (out == in) return OHS_OK;
+    if (chains == 2 || ss == 2 * cs) {
+        HIP_TRY(hipMemcpy2DAsync(out, (size_t)cs * sizeof(float), in, (size_t)cs * sizeof(float), (size_t)n * sizeof(float), chains,
+                                 hipMemcpyDeviceToDevice, st));
+        return OHS_OK;
+    }
+    for (size_t s = 0; s < chains / 2; ++s)
+        HIP_TRY(hipMemcpy2DAsync(out + (long long)s * ss, (size_t)cs * sizeof(float), in + (long long)s * ss, (size_t)cs * sizeof(float),
+                                 (size_t)n * sizeof(float), 2, hipMemcpyDeviceToDevice, st));
+    return OHS_OK;
 }
 
 void eq_free(EqState &e)
@@ -126,34 +171,22 @@ static int eq_launch_table(EqState &e, const float *coeffs, const unsigned char 
                            float *d_state, const float *in, float *out, long long ss, long long cs, long long n,
                            hipStream_t st, bool *did_anything, hipEvent_t ev_start, hipEvent_t ev_stop)
 {
-    bool did = false;
+    const auto [xcd_lo, xcd_n] = eq_xcds(e);
     const float *src = in;
-    std::vector<size_t> on;
-    for (size_t b = 0; b < e.nb; ++b)
-        if (en8 ? en8[b] != 0 : en32[b] != 0) on.push_back(b);
-    for (size_t p0 = 0; p0 < on.size(); p0 += 16) {
-        EqPassTable t;
-        std::memset(&t, 0, sizeof(t));
-        const int nbp = (int)std::min<size_t>(16, on.size() - p0);
-        for (int j = 0; j < 16; ++j) {
-            const size_t b = on[p0 + (size_t)std::min(j, nbp - 1)];      // unused lanes shadow the last band's slot (never stored)
-            t.slot[j] = (int)b;
-            if (j < nbp) {
-                t.b0[j] = coeffs[5 * b + 0]; t.b1[j] = coeffs[5 * b + 1]; t.b2[j] = coeffs[5 * b + 2];
-                t.a1[j] = coeffs[5 * b + 3]; t.a2[j] = coeffs[5 * b + 4];
-            }
-        }
-        int xcd_lo = e.xcd_lo, xcd_n = e.xcd_n;
-        if (tuning().eq_xcd_n > 0) { xcd_lo = tuning().eq_xcd_lo; xcd_n = tuning().eq_xcd_n; }
-        const bool first = p0 == 0, last = p0 + 16 >= on.size();
-        hipError_t err = launch_eq_pass(src, out, ss, cs, n, (int)chains, t, nbp, d_state, st, e.exact_specials, e.fp_mode,
-                                        xcd_lo, xcd_n, first ? ev_start : nullptr, last ? ev_stop : nullptr, e.d_stamps, &e.last_form);
+    EqPassTable t, t_next;
+    size_t next = 0;
+    int nbp = eq_compact_pass(e.nb, coeffs, en8, en32, 0, 16, t, &next);
+    if (did_anything) *did_anything = nbp > 0;
+    for (bool first = true; nbp > 0; first = false) {
+        const int nbp_next = eq_compact_pass(e.nb, coeffs, en8, en32, next, 16, t_next, &next);     // (none: this pass is the last)
+        hipError_t err = launch_eq_pass(src, out, ss, cs, n, (int)chains, t, nbp, d_state, st, e.exact_specials, e.fp_mode, xcd_lo, xcd_n,
+                                        first ? ev_start : nullptr, nbp_next == 0 ? ev_stop : nullptr, e.d_stamps, &e.last_form);
         if (err != hipSuccess) return fail(OHS_ERR_HIP, std::string("eq launch: ") + hipGetErrorString(err));
         e.last_scheduled = false;
         src = out;
-        did = true;
+        t = t_next;
+        nbp = nbp_next;
     }
-    if (did_anything) *did_anything = did;
     return OHS_OK;
 }
 
@@ -204,6 +237,23 @@ static int eq_upload_stream_tables(EqState &e, hipStream_t st)
     return OHS_OK;
 }
 
+// Stream s of (in, out) alone under the table (coeffs [nb][5], en8 [nb]): the conveyor kernel takes its table as a kernel
+// argument, so where the ring forms cannot serve, every stream is a launch sequence of its own (correct for any table; an
+// offline job that needs this at scale groups its streams by table and uses one batch per group).  A stream without an enabled
+// band is copied through.  *did becomes true where anything was queued.
+static int eq_launch_stream(EqState &e, size_t s, const float *coeffs, const unsigned char *en8, const float *in, float *out,
+                            long long ss, long long cs, long long n, hipStream_t st, bool *did)
+{
+    bool launched = false;
+    const float *si = in + (long long)s * ss;
+    float *so = out + (long long)s * ss;
+    int rc = eq_launch_table(e, coeffs, en8, nullptr, 2, e.d_state + s * 2 * (size_t)kEqStateSlots * 2, si, so, ss, cs, n, st, &launched,
+                             nullptr, nullptr);
+    if (rc == OHS_OK && !launched) rc = eq_copy_through(si, so, ss, cs, n, 2, st);
+    if (did) *did = *did || launched || so != si;
+    return rc;
+}
+
 // run the cascade over n frames of `chains` chains, in place allowed
 int eq_launch(EqState &e, const float *in, float *out, long long ss, long long cs, long long n,
               hipStream_t st, bool *did_anything, hipEvent_t ev_start, hipEvent_t ev_stop)
@@ -221,11 +271,10 @@ int eq_launch(EqState &e, const float *in, float *out, long long ss, long long c
         }
         if (e.max_enabled == 0) {
             // no stream has an enabled band: identity
-        } else if (!e.exact_specials && !tuning().eq_conveyor && eq_ring_addressable(ss, cs, n)) {
+        } else if (eq_ring_forms_serve(e, ss, cs, n)) {
             // one launch per 12 bands for all streams: every row reads its own stream's table when its wave starts (a stream with
             // fewer bands than the pass's first hands its samples on -- exact except for -0.0, as the ring form's spare lanes are)
-            int xcd_lo = e.xcd_lo, xcd_n = e.xcd_n;
-            if (tuning().eq_xcd_n > 0) { xcd_lo = tuning().eq_xcd_lo; xcd_n = tuning().eq_xcd_n; }
+            const auto [xcd_lo, xcd_n] = eq_xcds(e);
             const size_t S = e.chains / 2, passes = (e.max_enabled + 11) / 12;
             for (size_t pk = 0; pk < passes; ++pk) {
                 hipError_t err = launch_eq_ring_streams(pk ? out : in, out, ss, cs, n, (int)e.chains, e.d_stabs + pk * S, e.d_state, st,
@@ -236,23 +285,12 @@ int eq_launch(EqState &e, const float *in, float *out, long long ss, long long c
             }
             did = true;
         } else {
-            // The exact-specials mode, strides beyond the ring form's reach: the conveyor kernel takes its table as a kernel
-            // argument, so every stream is a launch sequence of its own (correct for any table; an offline job that needs this at
-            // scale groups its streams by table and uses one batch per group).
+            // The exact-specials mode, strides beyond the ring form's reach: every stream is a launch sequence of its own
+            // (eq_launch_stream).
             if (ev_start) HIP_TRY(hipEventRecord(ev_start, st));
-            const size_t S = e.chains / 2;
-            for (size_t s = 0; s < S; ++s) {
-                bool d1 = false;
-                const float *si = in + (long long)s * ss;
-                float *so = out + (long long)s * ss;
-                rc = eq_launch_table(e, &e.s_coeffs[s * e.nb * 5], &e.s_en[s * e.nb], nullptr, 2,
-                                     e.d_state + s * 2 * (size_t)kEqStateSlots * 2, si, so, ss, cs, n, st, &d1, nullptr, nullptr);
+            for (size_t s = 0; s < e.chains / 2; ++s) {
+                rc = eq_launch_stream(e, s, &e.s_coeffs[s * e.nb * 5], &e.s_en[s * e.nb], in, out, ss, cs, n, st, &did);
                 if (rc) return rc;
-                if (!d1 && so != si) {      // this stream has no enabled band: its frames still have to arrive in `out`
-                    HIP_TRY(hipMemcpy2DAsync(so, (size_t)cs * sizeof(float), si, (size_t)cs * sizeof(float), (size_t)n * sizeof(float),
-                                             2, hipMemcpyDeviceToDevice, st));
-                }
-                did = did || d1 || so != si;
             }
             if (ev_stop) HIP_TRY(hipEventRecord(ev_stop, st));
             if (did_anything) *did_anything = did;
@@ -390,47 +428,26 @@ int eq_launch_scheduled(EqState &e, const BatchSchedule &sc, size_t blk0, size_t
     // the events ride in the dispatch when the chunk is exactly one kernel launch sequence (as the plain call's); else around
     const bool single = groups.size() == 1 && count_on(runs[0].tab) > 0 &&
                         (groups[0].r1 - groups[0].r0 == 1 ||
-                         (sc.seg_blocks * BS < ((size_t)1 << 30) &&
-                          eq_pass_takes_wave_ring(ss, cs, (long long)n_blocks * BS, (int)e.chains, (int)count_on(runs[0].tab), e.exact_specials)));
+                         eq_sched_kernel_serves(e, sc, ss, cs, (long long)n_blocks * BS, count_on(runs[0].tab)));
     if (!single && ev_start) HIP_TRY(hipEventRecord(ev_start, st));
     for (const Group &g : groups) {
         const unsigned t0 = runs[g.r0].tab;
         const size_t on = count_on(t0);
         const size_t gb0 = runs[g.r0].b0, gb1 = runs[g.r1 - 1].b1;
         const long long off = (long long)(gb0 - blk0) * BS, n = (long long)(gb1 - gb0) * BS;
-        if (on == 0) {      // identity: the frames still have to arrive in `out`
-            if (out != in) {
-                if (e.chains == 2 || ss == 2 * cs) {
-                    HIP_TRY(hipMemcpy2DAsync(out + off, (size_t)cs * sizeof(float), in + off, (size_t)cs * sizeof(float),
-                                             (size_t)n * sizeof(float), e.chains, hipMemcpyDeviceToDevice, st));
-                } else {
-                    for (size_t s = 0; s < e.chains / 2; ++s)
-                        HIP_TRY(hipMemcpy2DAsync(out + (long long)s * ss + off, (size_t)cs * sizeof(float), in + (long long)s * ss + off,
-                                                 (size_t)cs * sizeof(float), (size_t)n * sizeof(float), 2, hipMemcpyDeviceToDevice, st));
-                }
-            }
+        if (on == 0) {
+            int rc = eq_copy_through(in + off, out + off, ss, cs, n, e.chains, st);
+            if (rc) return rc;
             continue;
         }
-        if (g.r1 - g.r0 > 1 && sc.seg_blocks * BS < ((size_t)1 << 30) &&
-            eq_pass_takes_wave_ring(ss, cs, n, (int)e.chains, (int)on, e.exact_specials)) {
-            EqPassTable t;
-            std::memset(&t, 0, sizeof(t));
-            int nbp = 0;
-            size_t last = 0;
-            for (size_t b = 0; b < e.nb; ++b) {
-                if (!e.sched_en[t0 * e.nb + b]) continue;
-                const float *c = &e.sched_coeffs[(t0 * e.nb + b) * 5];
-                t.slot[nbp] = (int)b;
-                t.b0[nbp] = c[0]; t.b1[nbp] = c[1]; t.b2[nbp] = c[2]; t.a1[nbp] = c[3]; t.a2[nbp] = c[4];
-                last = b; ++nbp;
-            }
-            for (int j = nbp; j < 16; ++j) t.slot[j] = (int)last;      // (unused lanes shadow the last band's slot, never stored)
+        if (g.r1 - g.r0 > 1 && eq_sched_kernel_serves(e, sc, ss, cs, n, on)) {
+            EqPassTable t;      // (at most 12 bands: the wave ring's)
+            const int nbp = eq_compact_pass(e.nb, &e.sched_coeffs[(size_t)t0 * e.nb * 5], &e.sched_en[(size_t)t0 * e.nb], nullptr, 0, 12, t, nullptr);
             EqRingSched sch;
             sch.lane_tabs = e.d_sched_lanes; sch.seg_tab = sc.d_tab; sch.n_segs = (int)sc.n_segs;
             sch.seg_len = (int)(sc.seg_blocks * BS);
             sch.seg0 = (int)(gb0 / sc.seg_blocks); sch.off0 = (int)((gb0 % sc.seg_blocks) * BS);
-            int xcd_lo = e.xcd_lo, xcd_n = e.xcd_n;
-            if (tuning().eq_xcd_n > 0) { xcd_lo = tuning().eq_xcd_lo; xcd_n = tuning().eq_xcd_n; }
+            const auto [xcd_lo, xcd_n] = eq_xcds(e);
             hipError_t err = launch_eq_ring_sched(in + off, out + off, ss, cs, n, (int)e.chains, t, nbp, e.d_state, sch, st, e.fp_mode,
                                                   xcd_lo, xcd_n, single ? ev_start : nullptr, single ? ev_stop : nullptr, e.d_stamps);
             if (err != hipSuccess) return fail(OHS_ERR_HIP, std::string("eq launch (scheduled): ") + hipGetErrorString(err));
@@ -490,9 +507,7 @@ int eq_launch_scheduled_streams(EqState &e, const BatchSchedule &sc, size_t blk0
     const size_t S = e.chains / 2, blk1 = blk0 + n_blocks;
     const size_t seg_first = blk0 / sc.seg_blocks, seg_last = (blk1 - 1) / sc.seg_blocks;
     auto seg_begin = [&](size_t k) { return std::max(blk0, k * sc.seg_blocks); };
-    int xcd_lo = e.xcd_lo, xcd_n = e.xcd_n;
-    if (tuning().eq_xcd_n > 0) { xcd_lo = tuning().eq_xcd_lo; xcd_n = tuning().eq_xcd_n; }
-    const bool ring_forms = !e.exact_specials && !tuning().eq_conveyor;
+    const auto [xcd_lo, xcd_n] = eq_xcds(e);
     // pieces [k0, k1] of segments without a change of flags
     struct Piece { size_t k0, k1; bool no_ring, idx_change; };
     std::vector<Piece> pieces;
@@ -505,7 +520,7 @@ int eq_launch_scheduled_streams(EqState &e, const BatchSchedule &sc, size_t blk0
     }
     auto piece_takes_kernel = [&](const Piece &p) {
         const long long n = (long long)((p.k1 == seg_last ? blk1 : (p.k1 + 1) * sc.seg_blocks) - seg_begin(p.k0)) * BS;
-        return !p.no_ring && sc.seg_blocks * BS < ((size_t)1 << 30) && eq_pass_takes_wave_ring(ss, cs, n, (int)e.chains, 1, e.exact_specials);
+        return !p.no_ring && eq_sched_kernel_serves(e, sc, ss, cs, n, 1);   // (1 .. 12 bands per stream: asked with one)
     };
     // the events ride in the dispatch when the chunk is exactly one launch of the scheduled kernel; else around
     const bool single = pieces.size() == 1 && piece_takes_kernel(pieces[0]);
@@ -535,12 +550,10 @@ int eq_launch_scheduled_streams(EqState &e, const BatchSchedule &sc, size_t blk0
             const long long off = (long long)(sb0 - blk0) * BS, n = (long long)(sb1 - sb0) * BS;
             const float *sin = in + off;
             float *sout = out + off;
-            if (mx == 0) {      // identity for every stream: the frames still have to arrive in `out`
-                if (sout != sin)
-                    for (size_t s = 0; s < S; ++s)
-                        HIP_TRY(hipMemcpy2DAsync(sout + (long long)s * ss, (size_t)cs * sizeof(float), sin + (long long)s * ss,
-                                                 (size_t)cs * sizeof(float), (size_t)n * sizeof(float), 2, hipMemcpyDeviceToDevice, st));
-            } else if (ring_forms && eq_ring_addressable(ss, cs, n)) {
+            if (mx == 0) {      // identity for every stream
+                int rc = eq_copy_through(sin, sout, ss, cs, n, e.chains, st);
+                if (rc) return rc;
+            } else if (eq_ring_forms_serve(e, ss, cs, n)) {
                 const size_t passes = ((size_t)mx + 11) / 12;
                 hipError_t err = launch_eq_gather_tables(e.d_sched_gather, e.d_sched_stabs, sc.d_tab + j0, (long long)sc.tab_stride, (int)S,
                                                          (int)e.sched_n, (int)passes, st);
@@ -554,15 +567,9 @@ int eq_launch_scheduled_streams(EqState &e, const BatchSchedule &sc, size_t blk0
             } else {
                 for (size_t s = 0; s < S; ++s) {
                     const unsigned t = sc.tab[s * sc.tab_stride + j0];
-                    bool d1 = false;
-                    const float *si = sin + (long long)s * ss;
-                    float *so = sout + (long long)s * ss;
-                    int rc = eq_launch_table(e, &e.sched_coeffs[(size_t)t * e.nb * 5], &e.sched_en[(size_t)t * e.nb], nullptr, 2,
-                                             e.d_state + s * 2 * (size_t)kEqStateSlots * 2, si, so, ss, cs, n, st, &d1, nullptr, nullptr);
+                    int rc = eq_launch_stream(e, s, &e.sched_coeffs[(size_t)t * e.nb * 5], &e.sched_en[(size_t)t * e.nb], sin, sout, ss, cs,
+                                              n, st, nullptr);
                     if (rc) return rc;
-                    if (!d1 && so != si)
-                        HIP_TRY(hipMemcpy2DAsync(so, (size_t)cs * sizeof(float), si, (size_t)cs * sizeof(float), (size_t)n * sizeof(float),
-                                                 2, hipMemcpyDeviceToDevice, st));
                 }
             }
             j0 = j1 + 1;

@@ -1,6 +1,7 @@
 // kernels.h -- host-callable launchers of the gfx950 kernels (internal to the library).
 #pragma once
 #include "experiments.h"
+#include "eq_plan.h"        // xcd_grid; the EQ launchers' one rule
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -61,17 +62,20 @@ constexpr int kEqStateSlots = 64;       // = OHS_MAX_EQ_BANDS
 // exact_specials: use the conveyor form (k_eq_pass: samples move by DPP moves only) also for <= 12 bands; it is
 // bit-exact for -0.0 and for samples next to a non-finite input, where the faster ring form is not (its
 // pass-on lanes run 1*x + 0).
+// Which form, wave body, workgroup shape and grid a launch gets is eq_plan()'s decision (eq_plan.h) for every launcher
+// below; they check their arguments, fill the kernel's and dispatch.
 hipError_t launch_eq_pass(const float *in, float *out, long long stream_stride, long long ch_stride,
                           long long n, int n_chains, const EqPassTable &tab, int n_bands, float *state,
                           hipStream_t st, bool exact_specials = false, int fp_mode = 0, int xcd_lo = 0, int xcd_n = 8,
                           hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, unsigned long long *stamps = nullptr,
                           int *form = nullptr);
 // (form, optional: which form served the launch, OHS_EQ_FORM_* of ohs_hip.h)
-// whether launch_eq_pass serves such a launch with the wave ring (one chain per wave, eq_ring64_body.hpp)
+// whether launch_eq_pass serves such a launch with the wave ring (one chain per wave): eq_plan()'s form, for the callers
+// that have to know before they launch (the scheduled batch calls)
 bool eq_pass_takes_wave_ring(long long stream_stride, long long ch_stride, long long n, int n_chains, int n_bands,
                              bool exact_specials);
 // The wave ring with a table schedule (k_eq_ring_sched): `tab` is the table of the launch's first sample, the others come from
-// `sch`.  Only where eq_pass_takes_wave_ring holds and n is a multiple of 512; everything else about the launch as launch_eq_pass.
+// `sch`.  Only where eq_plan() takes the wave ring and n is a multiple of 512; that plan's workgroups and grid, as launch_eq_pass.
 hipError_t launch_eq_ring_sched(const float *in, float *out, long long stream_stride, long long ch_stride, long long n,
                                 int n_chains, const EqPassTable &tab, int n_bands, float *state, const EqRingSched &sch,
                                 hipStream_t st, int fp_mode, int xcd_lo, int xcd_n, hipEvent_t ev_start, hipEvent_t ev_stop,
@@ -95,7 +99,8 @@ hipError_t launch_eq_gather_tables(EqStreamTable *dst, const EqStreamTable *tabs
 // itself -- hipExtLaunchKernelGGL -- which spares the queue the marker packets of hipEventRecord and the gap they open
 // between back-to-back launches: 12-13 -> 7 us per chunk boundary of the overlapped batch step with profiling on.)
 
-// the ring form with one table per stream: d_tabs[n_chains / 2] in device memory (every stream <= 12 enabled bands)
+// the ring form with one table per stream: d_tabs[n_chains / 2] in device memory (every stream <= 12 enabled bands);
+// eq_plan() without one_table: rows or the wave ring by the same rule, whatever eq_conveyor / eq_ring_v1 say
 hipError_t launch_eq_ring_streams(const float *in, float *out, long long stream_stride, long long ch_stride, long long n,
                                   int n_chains, const EqStreamTable *d_tabs, float *state, hipStream_t st, int fp_mode = 0,
                                   int xcd_lo = 0, int xcd_n = 8, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
@@ -185,15 +190,7 @@ hipError_t launch_engine_resident(RtMailbox *mb_dev, const float2 *tw, unsigned 
 // Fast path when every path has exactly one partition (taps <= 512): time-parallel over
 // `chunks` contiguous block ranges per stream, one forward + one inverse FFT per block, the
 // combined spectra C = (A - jB)/2, D = (A + jB)/2 (A = H0 + jH1, B = H2 + jH3) held in LDS.
-// XCD partition of a launch.  The dispatcher hands workgroup b of a grid to XCD b % 8 (MI355X: 8 XCDs of 32 CUs, each
-// with its own L2); a kernel confined to the XCDs [lo, lo + n) is launched with xcd_grid(workgroups, n) workgroups, those
-// on other XCDs return at once and the rest renumber themselves ((b >> 3) * n + (b & 7) - lo).  ohs_batch_process gives
-// the EQ and the overlapped convolution disjoint XCD sets: an EQ wave saturates the vector unit of its SIMD, and a
-// convolution workgroup that shares a CU with one waits for its starved waves (LABNOTES.md, "What sharing a CU is worth").
-inline unsigned xcd_grid(unsigned workgroups, int xcd_n)
-{
-    return xcd_n == 8 ? workgroups : ((workgroups + (unsigned)xcd_n - 1) / (unsigned)xcd_n) * 8u;
-}
+// (XCD partition of a launch, xcd_grid: eq_plan.h)
 
 struct ConvP1Args {
     const float *in;

@@ -208,6 +208,29 @@ def test_flags_changing_for_one_stream_end_the_launch_for_all(oracle, in_place):
     _two_calls(oracle, _ffi.lib(), [40, 23], 2, coeffs, en, rows_fn=rows_fn, in_place=in_place)
 
 
+@pytest.mark.parametrize("exact", [False, True], ids=["ring_forms", "exact_specials"])
+def test_segments_without_any_band_arrive_in_the_output(oracle, exact):
+    """out of place, every stream on one table of its own, stream 3 on the table without bands (ring forms: its rows hand the
+    samples on; exact-specials mode: that stream's launch sequence is a copy).  First call: two segments of 8 blocks = one span
+    of 8 192 frames, the wave ring's threshold, then a segment in which NO stream has a band: copied through for all streams at
+    once.  Second call: 1 024 frames, the rows."""
+    from open_headstage_amd import _ffi
+    coeffs, en = _tables(6)
+    en[5, :] = False
+
+    def rows_fn(n_blocks, seg_blocks, n_tables, call):
+        n_segs = -(-n_blocks // seg_blocks)
+        idx = np.repeat((np.arange(S, dtype=np.uint32) % 5)[:, None], n_segs, axis=1)
+        idx[3] = 5
+        if call == 0:
+            idx[:, -1] = 5
+        return idx, _rows(n_blocks, seg_blocks, 5, call)[1]
+
+    _two_calls(oracle, _ffi.lib(), [24, 2], 8, coeffs, en, rows_fn=rows_fn,
+               setup=(lambda bp: bp.set_eq_exact_specials(True)) if exact else None,
+               expect_calls=[("conveyor" if exact else "wave_ring", False), ("conveyor" if exact else "row_ring", False)])
+
+
 # ---- 4. call lengths ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("seg_blocks", [2, 3])
 @pytest.mark.parametrize("blocks", [[16, 17], [18, 19], [70, 19]], ids=lambda b: "x".join(map(str, b)))
