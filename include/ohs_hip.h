@@ -142,6 +142,15 @@ int  ohs_engine_silent_frames(const ohs_engine *e, uint64_t *frames);
  * same mode (tests/test_gpu_ftz.py) up to the default (ring) kernel's documented corners, which flushing makes
  * reachable: a result flushed to -0.0 comes out as +0.0, and a denormal INPUT sample is read as zero also in mode 1
  * (ohs_eq_set_exact_specials selects the kernel without either).
+ * The convolution (every kernel family, call kind and the single-stream engine) keeps three observable promises in modes 1
+ * and 2, each held against the same handle in mode 0 by tests/test_gpu_flush_modes.py:
+ *   A  normal range: on a signal of amplitude 1 the mode changes no output bit and not the kernel plan;
+ *   B  below the range: input so small that every sum of it is still subnormal (modes 1 and 2), or input whose every sample is
+ *      subnormal (mode 2), comes out as zeros of either sign, and leaves the state of a fresh handle behind;
+ *   C  through the range: no output sample is ever subnormal (0 < |v| < 2^-126), whatever the input -- the sums that add
+ *      pending tails behind a per-path ohs_batch_set_ir on a long response included.
+ * (In mode 0 every family still answers input of 2^-141 with subnormal samples in more than half its output, as the reference
+ * does: the block-2048, block-8192 and layout kernels apply the inverse transform's 1/N with the gain, not in their tables.)
  * Also available as ohs_eq_set_flush_denormals and ohs_batch_set_flush_denormals; clones inherit the mode. */
 int  ohs_engine_set_flush_denormals(ohs_engine *e, int mode);
 

@@ -407,7 +407,7 @@ static int conv_lb_tail_route(ConvState &c, DeviceCtx *ctx, int path, hipStream_
         e = launch_conv_lb_mac_inverse(m, st);
         if (e == hipSuccess)
             e = launch_conv_lb_tails_merge(c.pt_active ? c.d_ptail : nullptr, c.pt_pos, c.d_xhist_alt, c.d_ptail_alt, Lt, pair, keep,
-                                           (int)c.S, st);
+                                           (int)c.S, st, c.fp_mode);
     }
     if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("pending tails: ") + hipGetErrorString(e));
     std::swap(c.d_ptail, c.d_ptail_alt);
@@ -727,7 +727,7 @@ static int layout_build_tables(DeviceCtx *ctx, size_t units, size_t len, Rows ro
                 const float2 *h = d_H + p * 4 * (size_t)NF;
                 HIP_TRY(launch_build_cd(h, h + NF, h + 2 * NF, h + 3 * NF, d_cd + p * 2 * (size_t)NF, st));
             }
-            HIP_TRY(launch_irs_tables(d_cd, (int)n, dst + u0 * (size_t)NF, st));
+            HIP_TRY(launch_irs_tables(d_cd, (int)n, dst + u0 * (size_t)NF, st, kLayoutTableScale));
             HIP_TRY(hipStreamSynchronize(st));      // (staging and scratch are reused by the next slice)
         }
         return OHS_OK;
@@ -1384,7 +1384,7 @@ int conv_launch(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, 
         const long long n = (long long)n_blocks * BS;
         // (with a gain table in k_conv_p1: tail * gain[segment] is not what this launch computes -- it adds with gain 1 in front of
         // the scale pass below, so such a call takes the scale pass for the tails' sake)
-        hipError_t e = launch_conv_lb_tails_add(out, out_ss, out_cs, n, c.d_ptail, c.pt_len, c.pt_pos, k.gain, (int)c.S, st);
+        hipError_t e = launch_conv_lb_tails_add(out, out_ss, out_cs, n, c.d_ptail, c.pt_len, c.pt_pos, k.gain, (int)c.S, st, c.fp_mode);
         if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("pending tails: ") + hipGetErrorString(e));
         c.pt_pos += n;
         if (c.pt_pos >= c.pt_len) c.pt_active = false;

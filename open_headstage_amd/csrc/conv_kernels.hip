@@ -1515,7 +1515,7 @@ __global__ __launch_bounds__(64 * kLayoutWaves, kLayoutWavesPerSimd) void k_conv
             float *pl = ql + u, *pr = pl + A.out_ch_stride;
 #pragma unroll
             for (int a = 0; a < 8; ++a) {
-                OHS_P1_ST(&pl[64 * a], (w[a].x + tail[a].x) * A.gain);          // (1/N is in C and D)
+                OHS_P1_ST(&pl[64 * a], (w[a].x + tail[a].x) * A.gain);          // (1/N is in the gain)
                 OHS_P1_ST(&pr[64 * a], (w[a].y + tail[a].y) * A.gain);
             }
         }
@@ -1914,20 +1914,21 @@ hipError_t launch_conv_p1(const ConvP1Args &a, hipStream_t st, hipEvent_t ev_sta
 
 // ---- the IR-scheduled sibling (ohs_batch_process_ir_scheduled) ------------------------------------------------------
 // (C, D) of every set in the block loop's own layout: dst[set][i] = (C[src], D[src]), src = paired_to_natural(i & 63, i >> 6),
-// from the sets' k_build_cd tables cd[set][2][1024] (1/N folded in there)
-__global__ void k_irs_tables(const float2 *__restrict__ cd, int n_sets, float4 *__restrict__ dst)
+// from the sets' k_build_cd tables cd[set][2][1024] (1/N folded in there), times `scale` (a power of two: 1, or N for the layout kernels,
+// whose launchers apply the 1/N with the gain at the store instead)
+__global__ void k_irs_tables(const float2 *__restrict__ cd, int n_sets, float4 *__restrict__ dst, float scale)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, set = blockIdx.y;
     if (i >= kFft || set >= n_sets) return;
     const float2 *t = cd + (size_t)set * 2 * kFft;
     const int src = paired_to_natural(i & 63, i >> 6);
     const float2 c = t[src], d = t[kFft + src];
-    dst[(size_t)set * kFft + i] = make_float4(c.x, c.y, d.x, d.y);
+    dst[(size_t)set * kFft + i] = make_float4(scale * c.x, scale * c.y, scale * d.x, scale * d.y);
 }
-hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st)
+hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st, float scale)
 {
     if (n_sets <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_irs_tables, dim3(kFft / 256, (unsigned)n_sets), dim3(256), 0, st, cd, n_sets, dst);
+    hipLaunchKernelGGL(k_irs_tables, dim3(kFft / 256, (unsigned)n_sets), dim3(256), 0, st, cd, n_sets, dst, scale);
     return hipGetLastError();
 }
 
@@ -1998,8 +1999,10 @@ hipError_t launch_conv_p1_irs_xf(const ConvP1Args &a, const ConvIrXfArgs &i, hip
 int conv_layout_waves_per_cu() { return 4 * kLayoutWavesPerSimd; }
 
 // the layout kernel: one launch, no pre-pass, out of place
-hipError_t launch_conv_p1_layout(const ConvP1Args &a, const ConvLayoutArgs &l, hipStream_t st)
+hipError_t launch_conv_p1_layout(const ConvP1Args &args, const ConvLayoutArgs &l, hipStream_t st)
 {
+    ConvP1Args a = args;
+    a.gain = args.gain * (1.0f / kLayoutTableScale);        // the inverse transform's 1/N: the layout tables come without it
     if (a.n_blocks <= 0 || a.n_streams <= 0 || a.chunks > a.n_blocks) return hipErrorInvalidValue;
     if (!(a.chunks == 1 || a.chunks == 2 || a.chunks == 4 || a.chunks == 8 || a.chunks == 16)) return hipErrorInvalidValue;
     // (no 32-bit limit on n_blocks * 512 as in the launchers above: the kernel forms every frame offset in 64 bits)
@@ -2017,8 +2020,10 @@ hipError_t launch_conv_p1_layout(const ConvP1Args &a, const ConvLayoutArgs &l, h
 }
 
 // the scheduled layout kernel: launch_conv_p1_layout's checks and shape, plus the rows
-hipError_t launch_conv_p1_layout_irs(const ConvP1Args &a, const ConvLayoutIrArgs &l, hipStream_t st)
+hipError_t launch_conv_p1_layout_irs(const ConvP1Args &args, const ConvLayoutIrArgs &l, hipStream_t st)
 {
+    ConvP1Args a = args;
+    a.gain = args.gain * (1.0f / kLayoutTableScale);        // the inverse transform's 1/N: the layout tables come without it
     if (a.n_blocks <= 0 || a.n_streams <= 0 || a.chunks > a.n_blocks) return hipErrorInvalidValue;
     if (!(a.chunks == 1 || a.chunks == 2 || a.chunks == 4 || a.chunks == 8 || a.chunks == 16)) return hipErrorInvalidValue;
     if (a.xcd_n < 1 || a.xcd_n > 8 || a.xcd_lo < 0 || a.xcd_lo + a.xcd_n > 8) return hipErrorInvalidValue;

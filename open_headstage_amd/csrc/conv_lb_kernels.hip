@@ -457,7 +457,10 @@ __global__ __launch_bounds__(256) void k_conv_lb_build_cd(const float4 *__restri
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 a = (mask & 1) ? ab[((size_t)0 * P2pad + i) * kLbPairs + q] : z4;
     const float4 b = (mask & 2) ? ab[((size_t)1 * P2pad + i) * kLbPairs + q] : z4;
-    const float h = 0.5f / (float)kLbFft;       // the 1/2 of C, D and the 1/N of the inverse transform (powers of two)
+    // the 1/2 of C, D only: the inverse transform's 1/N is applied with the gain at the store (launch_conv_lb_mac_inverse) -- a power
+    // of two, so every bit of a normal result is the same, and a signal near 2^-149 keeps the bits that N times smaller tables would
+    // round away
+    const float h = 0.5f;
     // C = (A - jB)/2, D = (A + jB)/2 per component (k_build_cd_multi does the same for the 1024-point spectra)
     cd[((size_t)i * 2 + 0) * kLbPairs + q] = make_float4(h * (a.x + b.y), h * (a.y - b.x), h * (a.x - b.y), h * (a.y + b.x));
     cd[((size_t)i * 2 + 1) * kLbPairs + q] = make_float4(h * (a.z + b.w), h * (a.w - b.z), h * (a.z - b.w), h * (a.w + b.z));
@@ -541,9 +544,11 @@ hipError_t launch_conv_lb_forward(const ConvLbArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
-hipError_t launch_conv_lb_mac_inverse(const ConvLbArgs &a, hipStream_t st, int *tile_blocks)
+hipError_t launch_conv_lb_mac_inverse(const ConvLbArgs &args, hipStream_t st, int *tile_blocks)
 {
-    if (a.n_big <= 0) return hipSuccess;
+    if (args.n_big <= 0) return hipSuccess;
+    ConvLbArgs a = args;
+    a.gain = args.gain * (1.0f / (float)kLbFft);    // the inverse transform's 1/N (k_conv_lb_build_cd leaves it out of the tables)
     // the oldest window a tile reads is block 0's partition P2pad - 1; a tile's unused blocks read slots that alias others
     if (!lb_args_ok(a) || !a.out || !a.cd || a.P2pad < 4 || (a.P2pad & 3) || a.P2 < 1 || a.P2 > a.P2pad || a.n_big + a.P2pad - 1 > a.ring_cap ||
         a.ring_base - (a.P2pad - 1) - 8 < 0)
@@ -579,8 +584,9 @@ hipError_t launch_conv_lb_build_cd(const float4 *ab, int P2pad, float4 *cd, hipS
 // dst[s][q][j] = keep(q) ? pend[s][q][pos + j] + fresh[s][q & 1][j] : 0   for the two paths q = 2 pair, 2 pair + 1
 __global__ __launch_bounds__(256) void k_conv_lb_tails_merge(const float *__restrict__ pend, long long pos, const float *__restrict__ fresh,
                                                              float *__restrict__ dst, long long len, int pair, int keep_mask,
-                                                             unsigned wgs_per_row)
+                                                             unsigned wgs_per_row, int fp_mode)
 {
+    ohs_set_fp_mode(fp_mode);       // in front of the loads: the sum is a result like any other, and mode 2 reads subnormal rows as zero
     const long long j = 4 * ((long long)(blockIdx.x % wgs_per_row) * 256 + threadIdx.x);
     if (j >= len) return;
     const size_t row = blockIdx.x / wgs_per_row;        // stream * 2 + (q & 1)
@@ -597,8 +603,9 @@ __global__ __launch_bounds__(256) void k_conv_lb_tails_merge(const float *__rest
 // out[s][ear][f] += gain * (tails[s][ear][pos + f] + tails[s][2 + ear][pos + f]),  f < min(n_frames, len - pos)
 __global__ __launch_bounds__(256) void k_conv_lb_tails_add(float *__restrict__ out, long long out_ss, long long out_cs, long long count,
                                                            const float *__restrict__ tails, long long len, long long pos, float gain,
-                                                           unsigned wgs_per_row)
+                                                           unsigned wgs_per_row, int fp_mode)
 {
+    ohs_set_fp_mode(fp_mode);       // in front of the loads: what leaves here is the call's output
     const long long f = (long long)(blockIdx.x % wgs_per_row) * 256 + threadIdx.x;
     if (f >= count) return;
     const size_t row = blockIdx.x / wgs_per_row;        // stream * 2 + ear
@@ -609,18 +616,18 @@ __global__ __launch_bounds__(256) void k_conv_lb_tails_add(float *__restrict__ o
 }
 
 hipError_t launch_conv_lb_tails_merge(const float *pend, long long pos, const float *fresh, float *dst, long long len, int pair,
-                                      int keep_mask, int n_streams, hipStream_t st)
+                                      int keep_mask, int n_streams, hipStream_t st, int fp_mode)
 {
     if (len <= 0 || (len & 511) || (pos & 511) || pos < 0 || n_streams <= 0 || pair < 0 || pair > 1) return hipErrorInvalidValue;
     const unsigned long long wpr = (unsigned long long)((len / 4 + 255) / 256), wgs = wpr * 2ull * (unsigned long long)n_streams;
     if (wgs > 0x7fffffffull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_conv_lb_tails_merge, dim3((unsigned)wgs), dim3(256), 0, st, pend, pos, fresh, dst, len, pair, keep_mask,
-                       (unsigned)wpr);
+                       (unsigned)wpr, fp_mode);
     return hipGetLastError();
 }
 
 hipError_t launch_conv_lb_tails_add(float *out, long long out_ss, long long out_cs, long long n_frames, const float *tails,
-                                    long long len, long long pos, float gain, int n_streams, hipStream_t st)
+                                    long long len, long long pos, float gain, int n_streams, hipStream_t st, int fp_mode)
 {
     if (len <= 0 || pos < 0 || pos >= len || n_streams <= 0) return hipErrorInvalidValue;
     const long long count = n_frames < len - pos ? n_frames : len - pos;
@@ -628,7 +635,7 @@ hipError_t launch_conv_lb_tails_add(float *out, long long out_ss, long long out_
     const unsigned long long wpr = (unsigned long long)((count + 255) / 256), wgs = wpr * 2ull * (unsigned long long)n_streams;
     if (wgs > 0x7fffffffull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_conv_lb_tails_add, dim3((unsigned)wgs), dim3(256), 0, st, out, out_ss, out_cs, count, tails, len, pos, gain,
-                       (unsigned)wpr);
+                       (unsigned)wpr, fp_mode);
     return hipGetLastError();
 }
 

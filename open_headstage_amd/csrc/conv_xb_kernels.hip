@@ -342,7 +342,9 @@ __global__ __launch_bounds__(256) void k_conv_xb_build_cd(const float2 *__restri
     const int i = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;      // q < 16384
     const float2 a = ab[((size_t)0 * P2 + i) * kXbFft + q];
     const float2 b = ab[((size_t)1 * P2 + i) * kXbFft + q];
-    const float h = 0.5f / (float)kXbFft;
+    // the 1/2 of C, D only: the inverse transform's 1/N is applied with the gain at the store (launch_conv_xb) -- a power of two, so
+    // every bit of a normal result is the same, and a signal near 2^-149 keeps the bits that N times smaller tables would round away
+    const float h = 0.5f;
     cd[(size_t)i * kXbFft + q] = make_float4(h * (a.x + b.y), h * (a.y - b.x), h * (a.x - b.y), h * (a.y + b.x));
 }
 
@@ -372,8 +374,10 @@ int conv_xb_run_for(int n_streams, int n_blk, int P2, int num_cus)
     return best_run;
 }
 
-hipError_t launch_conv_xb(const ConvXbArgs &a, hipStream_t st)
+hipError_t launch_conv_xb(const ConvXbArgs &args, hipStream_t st)
 {
+    ConvXbArgs a = args;
+    a.gain = args.gain * (1.0f / (float)kXbFft);    // the inverse transform's 1/N (k_conv_xb_build_cd leaves it out of the tables)
     if (a.n_streams <= 0 || a.n_blk <= 0 || a.run <= 0 || !a.in || !a.tw || !a.tw16384 || (a.P2 != 1 && a.P2 != 2))
         return hipErrorInvalidValue;
     if (a.tables_mode ? !a.ab : (!a.out || !a.cd)) return hipErrorInvalidValue;

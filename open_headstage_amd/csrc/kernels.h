@@ -294,8 +294,12 @@ struct ConvLayoutIrArgs {
 };
 // a.chunks as for launch_conv_p1_layout; the host has checked every index against the table
 hipError_t launch_conv_p1_layout_irs(const ConvP1Args &a, const ConvLayoutIrArgs &l, hipStream_t st);
-// cd[set][2][1024] (launch_build_cd per set) -> dst[set][1024] in the block loop's layout
-hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st);
+// cd[set][2][1024] (launch_build_cd per set) -> dst[set][1024] in the block loop's layout, times `scale`
+hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st, float scale = 1.0f);
+// The layout kernels' tables are built with this scale: launch_build_cd's 1/N taken out again, which launch_conv_p1_layout and
+// launch_conv_p1_layout_irs apply with the gain at the store.  A power of two: every bit of a normal result is the same, and a
+// signal near 2^-149 keeps the bits that products with N times smaller tables round away (the sum over K / 2 pairs of quiet responses).
+constexpr float kLayoutTableScale = 1024.0f;
 // CD[0][..] = (A - jB)/2, CD[1][..] = (A + jB)/2 from four single-partition spectra
 hipError_t launch_build_cd(const float2 *h0, const float2 *h1, const float2 *h2, const float2 *h3,
                            float2 *cd, hipStream_t st);
@@ -429,7 +433,7 @@ struct ConvLbArgs {
     float4 *ring;               // [stream][ring_cap][2048]: slot q = (Z[q], Z[4096 - q]), slot 0 = (Z[0], Z[2048])
     int ring_cap;
     long long ring_base;        // window u lives in ring slot (ring_base + u) % ring_cap; ring_base + u >= 0 for every u touched
-    const float4 *cd;           // [P2pad][2 planes][2048]: plane 0 = (C[k], D[k]), plane 1 = (C[N - k], D[N - k]), 1/4096 folded in
+    const float4 *cd;           // [P2pad][2 planes][2048]: plane 0 = (C[k], D[k]), plane 1 = (C[N - k], D[N - k]); the 1/4096 goes with the gain (launch_conv_lb_mac_inverse)
     const float2 *tw;           // master twiddle table of the 1024-point transform
     const float2 *tw4096;       // [3][1024]: w4096^(n1 c), c = 1 .. 3
     float gain;
@@ -445,11 +449,12 @@ hipError_t launch_conv_lb_build_cd(const float4 *ab, int P2pad, float4 *cd, hipS
 // Pending tails [stream][4 paths][len]: what the frames in front of a per-path set_ir still contribute to the frames behind
 // it, per path (a later reset of a path zeroes its row).  merge: dst rows of the pair's two paths = the rest of the pending
 // row (from pos on) + the fresh tail fresh[stream][2][len] (re -> path 2 pair, im -> path 2 pair + 1), or zeros where
-// keep_mask has the path's bit clear; add: out += gain * (ear's two rows) for the call's frames
+// keep_mask has the path's bit clear; add: out += gain * (ear's two rows) for the call's frames.  Both do arithmetic on what
+// becomes output: fp_mode is the handle's (ohs_set_fp_mode), no default -- a caller cannot forget it
 hipError_t launch_conv_lb_tails_merge(const float *pend, long long pos, const float *fresh, float *dst, long long len, int pair,
-                                      int keep_mask, int n_streams, hipStream_t st);
+                                      int keep_mask, int n_streams, hipStream_t st, int fp_mode);
 hipError_t launch_conv_lb_tails_add(float *out, long long out_ss, long long out_cs, long long n_frames, const float *tails,
-                                    long long len, long long pos, float gain, int n_streams, hipStream_t st);
+                                    long long len, long long pos, float gain, int n_streams, hipStream_t st, int fp_mode);
 // the input history [stream][2][2 len] (a ring of twice its reach `len`): append the call's last cnt = min(n_frames, len)
 // frames at head .. head + cnt (mod 2 len); the caller then advances head by cnt.  (The forward kernels do this themselves;
 // this launch serves the calls that go through the sequential kernel.)
@@ -481,7 +486,7 @@ struct ConvXbArgs {
     int n_blk;                  // blocks of 8192 frames (the last one may reach beyond io_frames)
     int run;                    // consecutive blocks per workgroup (conv_xb_run_for)
     int P2;                     // partitions of 8192 taps: 1 or 2
-    const float4 *cd;           // [P2][8 waves][2 classes][16 registers][64 lanes]: (C[k], D[k]) of that bin, 1/16384 folded in
+    const float4 *cd;           // [P2][8 waves][2 classes][16 registers][64 lanes]: (C[k], D[k]) of that bin; the 1/16384 goes with the gain (launch_conv_xb)
     float4 *ab;                 // tables mode: the windows' spectra per bin (float2, same layout), [stream][n_blk][16384]
     const float2 *tw;           // master twiddle table of the 1024-point transform
     const float2 *tw16384;      // [15][1024]: w16384^(n1 c), c = 1 .. 15
