@@ -732,6 +732,34 @@ int ohs_eq_process_block(ohs_eq *q, float *left, float *right, size_t n)
     return OHS_OK;
 }
 
+#ifdef OHS_EXPERIMENTS
+// experiments build only (not declared in include/ohs_hip.h): the same cascade, same state, OUT OF PLACE on the device -- n
+// samples per channel of any length from one allocation to another, which the public entry points reach only in whole blocks
+// of 512 (the batch).  The output allocation starts from sentinel bits: a sample that no store reached shows.
+int ohs_debug_eq_process_block_out_of_place(ohs_eq *q, const float *left, const float *right, float *out_left, float *out_right, size_t n)
+{
+    if (!q || !left || !right || !out_left || !out_right || n == 0) return fail(OHS_ERR_INVALID_ARG, "bad argument");
+    HIP_TRY(hipSetDevice(q->device));
+    float *d_in = nullptr, *d_out = nullptr;
+    HIP_TRY(hipMalloc(&d_in, 2 * n * sizeof(float)));
+    hipError_t e = hipMalloc(&d_out, 2 * n * sizeof(float));
+    int rc = OHS_OK;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in, left, n * sizeof(float), hipMemcpyHostToDevice, q->st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in + n, right, n * sizeof(float), hipMemcpyHostToDevice, q->st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0xA5, 2 * n * sizeof(float), q->st);
+    if (e == hipSuccess) rc = eq_launch(q->eq, d_in, d_out, 0, (long long)n, (long long)n, q->st);
+    if (e == hipSuccess && rc == OHS_OK) e = hipMemcpyAsync(out_left, d_out, n * sizeof(float), hipMemcpyDeviceToHost, q->st);
+    if (e == hipSuccess && rc == OHS_OK) e = hipMemcpyAsync(out_right, d_out + n, n * sizeof(float), hipMemcpyDeviceToHost, q->st);
+    const hipError_t es = hipStreamSynchronize(q->st);
+    if (e == hipSuccess) e = es;
+    if (d_out) hipFree(d_out);
+    hipFree(d_in);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(OHS_ERR_HIP, hipGetErrorString(e));
+    return OHS_OK;
+}
+#endif
+
 int ohs_eq_set_flush_denormals(ohs_eq *q, int mode)
 {
     if (!q) return fail(OHS_ERR_INVALID_ARG, "eq is NULL");

@@ -23,7 +23,7 @@ struct EqPlan {
     int form = OHS_EQ_FORM_NONE;    // NONE with valid: nothing to launch, the events still mark this point of the stream
     int body = 0;                   // the ring kernels' `wave_ring` argument: 0 = four chains per wave in 16-lane rows; one chain
                                     // per wave: 1 = a band per pair of lanes, 2 = per quad (the experiments build: 3 = the quad
-                                    // body's fill loop, 4 = its lone-port loop)
+                                    // body's fill loop, 4 = its lone-port loop, 5 = its cluster-port loop)
     bool ring_v1 = false;           // the experiments build's k_eq_ring_v1: no XCD partition, events around the launch
     int wg_waves = 1;               // waves per workgroup
     unsigned grid = 0;              // workgroups
@@ -80,7 +80,8 @@ inline EqPlan eq_plan(bool one_table, bool addressable, long long n, int n_chain
         p.prio = tn.eq_no_prio ? 0 : 1;
         p.lds = tn.eq_lds;
 #ifdef OHS_EXPERIMENTS
-        p.body = !wave_ring ? 0 : (!one_table || tn.eq_form == 2) ? 1 : tn.eq_quad_fill ? 3 : tn.eq_quad_lone_port ? 4 : 2;
+        p.body = !wave_ring ? 0 : (!one_table || tn.eq_form == 2) ? 1 : tn.eq_quad_fill ? 3 : tn.eq_quad_lone_port ? 4 :
+                 tn.eq_quad_cluster_port ? 5 : 2;
 #else
         p.body = !wave_ring ? 0 : (!one_table || tn.eq_form == 2) ? 1 : 2;
 #endif

@@ -20,12 +20,20 @@
 // own instruction list (tools/gen_eq_quad_ring_asm.py -> eq_quad_ring_asm.inc), which also checks every DPP read's distance.
 // Where the port's memory instructions issue is what the loop's time above 4 ticks per slot is made of: each of the three,
 // alone between VALU instructions, costs the wave about 8 ticks beyond its slot, one directly behind another about none
-// (without them the loop runs at 20.41 ticks per sample, with them at 21.91).  So the loop the
-// kernel runs (eq_quad_ring_cl_asm.inc, the model's port variant C2) parks step 8's value in a holding register (v20, a
-// plain v_mov in that step's slot) and issues store, store, load back to back in step 15's slot: 83 slots per 16 samples at
-// 21.44 ticks per sample.  Same ring, same lanes, same addresses, same bits; stores and the load only issue later than they
-// did, so in place a store still never passes the load of its sample.  kQuadLoopLone (experiments build,
-// Tuning::eq_quad_lone_port) is the loop of round 12 with the three alone in the slots of steps 8, 10 and 15.
+// (without them the loop runs at 20.41 ticks per sample, with them at 21.91).  Round 15's loop
+// (eq_quad_ring_cl_asm.inc, the model's port variant C2; kQuadLoopCluster, experiments build, Tuning::eq_quad_cluster_port)
+// parks step 8's value in a holding register (v20, a plain v_mov in that step's slot) and issues store, store, load back
+// to back in step 15's slot: 83 slots per 16 samples at 21.44 ticks per sample.  The loop the kernel runs
+// (eq_quad_ring_mg_asm.inc, the model's variant D1W; round 17) pays per memory instruction, not per byte, so it stores once
+// per group: step 10's slot moves the parked value's lanes a, d to lanes b, c (v_mov_b32_dpp quad_perm:[0,0,3,3] on v20),
+// step 15's merges Zc's lanes a, d in (v_cndmask_b32_e64 under a constant SGPR-pair mask: a plain read of Zc, VCC stays
+// the injects'), and ONE store carries the group's 16 outputs -- lanes b, c with the offsets of lanes a, d seven samples
+// earlier.  Store and load issue in the next group's step-1 slot behind the group's wait (s_waitcnt, s_nop: step 14's
+// slot holds a v_nop instead), in an iteration's last group in its own step 16 behind inject A: no holding register is
+// live across the end of an iteration.  21.01 ticks per sample.  Same ring, same lanes, same addresses, same bits; stores
+// and the load only issue later than they did, so in place a store still never passes the load of its sample.
+// kQuadLoopLone (experiments build, Tuning::eq_quad_lone_port) is the loop of round 12 with the three alone in the slots
+// of steps 8, 10 and 15.
 // A slot with nothing to carry holds a v_nop.  kQuadLoopFill (experiments build, Tuning::eq_quad_fill) is round 12's loop with a fill
 // instruction there, v_and_b32_dpp on v19 (a register nothing else touches), which keeps the vector unit for the four
 // cycles a step instruction takes instead of leaving them to a convolution wave of the same SIMD: a tie -- the loop runs at
@@ -43,6 +51,7 @@
 #include "eq_ring64_body.hpp"   // kWaveRor1, ring64_rsrc, ring2_ld / ring2_st, dpp_mov
 #include "eq_quad_ring_asm.inc"
 #include "eq_quad_ring_cl_asm.inc"
+#include "eq_quad_ring_mg_asm.inc"
 #include <type_traits>
 
 namespace ohs {
@@ -52,9 +61,10 @@ constexpr int kQuadK = EQ_QUAD_RING_K;  // groups per asm iteration = input regi
 constexpr int kQp0003 = 0xC0, kQp0033 = 0xF0, kQp0012 = 0x90, kQp0101 = 0x44;
 
 struct QuadRegs { float Z0, Z1, Zp, G, P; };
-// the asm run's loop: the port's memory instructions in one cluster per group (the product's), or -- experiments build --
-// round 12's loop with each of them alone in its slot, without or with the fill instruction in the slots that carry nothing
-enum { kQuadLoopCluster, kQuadLoopLone, kQuadLoopFill };
+// the asm run's loop: one merged store and one load per group (the product's), or -- experiments build -- round 15's with
+// store, store, load in one cluster per group, or round 12's with each of them alone in its slot, without or with the fill
+// instruction in the slots that carry nothing
+enum { kQuadLoopMerged, kQuadLoopCluster, kQuadLoopLone, kQuadLoopFill };
 
 // A DPP read for the C++ form of the step.  Every control of the step (wave_ror:1, the quad_perms) gives every lane a source
 // lane, so bound_ctrl changes no value; with it the compiler folds the move into the VOP2 instruction that consumes it --
@@ -66,14 +76,15 @@ __device__ __forceinline__ float quad_dpp(float src)
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(src), CTRL, 0xf, 0xf, true));
 }
 
-template <int LOOP = kQuadLoopCluster>
+template <int LOOP = kQuadLoopMerged>
 __device__ __forceinline__ void eq_quad_ring_wave(const float *in, float *out, long long stream_stride, long long ch_stride,
                                                   long long n, int n_chains, int nb, const EqPassTable &tab,
                                                   float *__restrict__ state, long long chain)
 {
     constexpr int G = kQuadGroup, K = kQuadK;
     static_assert(K == 8, "the operand list below names x0 .. x7");
-    static_assert(EQ_QUAD_RING_CL_HOLD == 1, "the clobber list below names one holding register, v20");
+    static_assert(EQ_QUAD_RING_CL_HOLD == 1 && EQ_QUAD_RING_MG_HOLD == 1, "the clobber lists below name one holding register, v20");
+    static_assert(EQ_QUAD_RING_MG_PAIRS == 0, "the operand list below is that of one load and one store per group");
     if (chain >= n_chains) return;
     const int lane = threadIdx.x & 63, q = lane >> 2, role = lane & 3;
     const int n32 = (int)n;
@@ -179,9 +190,14 @@ __device__ __forceinline__ void eq_quad_ring_wave(const float *in, float *out, l
         const unsigned bytes = (unsigned)n32 * 4u;
         const ring64_rsrc_t rin = ring64_rsrc(src0, bytes), rout = ring64_rsrc(dst0, bytes);
         // v0: the store of step 16 (g0 - 1) + 8; v1: group g0's inputs
-        unsigned voff_st = st_lane ? (unsigned)(G * (g0 - 1) + 8 + ss) * 4u : 0xFFFFF000u;
+        // (the merged loop: v0 holds an offset in all 16 lanes of the conveyor -- every store carries the offset of its
+        // group's step 15, 28 bytes on; lanes b, c store what lanes a, d held at step 8: samples -8 - 4q and -10 - 4q from there)
+        constexpr bool kMerged = LOOP == kQuadLoopMerged;
+        const int ms = (role == 0 ? -1 : role == 1 ? -8 : role == 2 ? -10 : -3) - 4 * q;
+        unsigned voff_st = kMerged ? (conv ? (unsigned)(G * (g0 - 1) + 15 + ms) * 4u - 28u : 0xFFFFF000u)
+                                   : (st_lane ? (unsigned)(G * (g0 - 1) + 8 + ss) * 4u : 0xFFFFF000u);
         unsigned voff_ld = conv ? (unsigned)(G * g0 + xs) * 4u : 0xFFFFF000u;
-        const unsigned inc_ld = conv ? 4u * G * K : 0u, inc_st = st_lane ? 4u * G * K : 0u;
+        const unsigned inc_ld = conv ? 4u * G * K : 0u, inc_st = (kMerged ? conv : st_lane) ? 4u * G * K : 0u;
         unsigned cnt = 0u - (unsigned)__builtin_amdgcn_readfirstlane(iters);
 #ifdef OHS_EXPERIMENTS
         if constexpr (LOOP == kQuadLoopFill) {
@@ -204,17 +220,32 @@ __device__ __forceinline__ void eq_quad_ring_wave(const float *in, float *out, l
                   [x3] "+{v14}"(x3), [x4] "+{v15}"(x4), [x5] "+{v16}"(x5), [x6] "+{v17}"(x6), [x7] "+{v18}"(x7), [cnt] "+s"(cnt)
                 : [C1] "{v7}"(C1), [C2] "{v8}"(C2), [incl] "{v9}"(inc_ld), [incs] "{v10}"(inc_st), [rin] "s"(rin), [rout] "s"(rout)
                 : "memory", "scc", "vcc");
+        } else if constexpr (LOOP == kQuadLoopCluster) {
+            asm volatile(
+                "s_nop 4\n"
+                EQ_QUAD_RING_CL_LOOP
+                : [Z0] "+{v2}"(r.Z0), [Z1] "+{v3}"(r.Z1), [Zp] "+{v4}"(r.Zp), [Gr] "+{v5}"(r.G), [P] "+{v6}"(r.P),
+                  [vs] "+{v0}"(voff_st), [vl] "+{v1}"(voff_ld), [x0] "+{v11}"(xcur), [x1] "+{v12}"(xnext), [x2] "+{v13}"(x2),
+                  [x3] "+{v14}"(x3), [x4] "+{v15}"(x4), [x5] "+{v16}"(x5), [x6] "+{v17}"(x6), [x7] "+{v18}"(x7), [cnt] "+s"(cnt)
+                : [C1] "{v7}"(C1), [C2] "{v8}"(C2), [incl] "{v9}"(inc_ld), [incs] "{v10}"(inc_st), [rin] "s"(rin), [rout] "s"(rout)
+                : "memory", "scc", "vcc", "v20");
         } else
 #endif
-        // (v20: the holding register, written and read inside the loop only -- v19 is left to the fill)
-        asm volatile(
-            "s_nop 4\n"
-            EQ_QUAD_RING_CL_LOOP
-            : [Z0] "+{v2}"(r.Z0), [Z1] "+{v3}"(r.Z1), [Zp] "+{v4}"(r.Zp), [Gr] "+{v5}"(r.G), [P] "+{v6}"(r.P),
-              [vs] "+{v0}"(voff_st), [vl] "+{v1}"(voff_ld), [x0] "+{v11}"(xcur), [x1] "+{v12}"(xnext), [x2] "+{v13}"(x2),
-              [x3] "+{v14}"(x3), [x4] "+{v15}"(x4), [x5] "+{v16}"(x5), [x6] "+{v17}"(x6), [x7] "+{v18}"(x7), [cnt] "+s"(cnt)
-            : [C1] "{v7}"(C1), [C2] "{v8}"(C2), [incl] "{v9}"(inc_ld), [incs] "{v10}"(inc_st), [rin] "s"(rin), [rout] "s"(rout)
-            : "memory", "scc", "vcc", "v20");
+        {
+            static_assert(LOOP == kQuadLoopMerged, "the product library has the merged loop only");
+            // (v20: the holding register, written and read inside the loop only -- v19 is left to the fill; mk: lanes a, d of
+            // every quad, where the merge takes Zc)
+            const unsigned long long mk = 0x9999999999999999ull;
+            asm volatile(
+                "s_nop 4\n"
+                EQ_QUAD_RING_MG_LOOP
+                : [Z0] "+{v2}"(r.Z0), [Z1] "+{v3}"(r.Z1), [Zp] "+{v4}"(r.Zp), [Gr] "+{v5}"(r.G), [P] "+{v6}"(r.P),
+                  [vs] "+{v0}"(voff_st), [vl] "+{v1}"(voff_ld), [x0] "+{v11}"(xcur), [x1] "+{v12}"(xnext), [x2] "+{v13}"(x2),
+                  [x3] "+{v14}"(x3), [x4] "+{v15}"(x4), [x5] "+{v16}"(x5), [x6] "+{v17}"(x6), [x7] "+{v18}"(x7), [cnt] "+s"(cnt)
+                : [C1] "{v7}"(C1), [C2] "{v8}"(C2), [incl] "{v9}"(inc_ld), [incs] "{v10}"(inc_st), [rin] "s"(rin), [rout] "s"(rout),
+                  [mk] "s"(mk)
+                : "memory", "scc", "vcc", "v20");
+        }
         // (x0, x1 now hold the inputs of groups g1, g1 + 1: the run's last inject A took x0, group g1's inject B is next)
         g = g1;
 #pragma unroll 1

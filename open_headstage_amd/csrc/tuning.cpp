@@ -32,6 +32,7 @@ const struct { const char *env, *key; } kEnvKeys[] = {
     {"OHS_P1_LAZY_STATE", "p1_lazy_state"}, {"OHS_P1_XCD", "p1_xcd"}, {"OHS_EQ_XCD", "eq_xcd"},
     {"OHS_EQ_CONVEYOR", "eq_conveyor"}, {"OHS_EQ_RING_V1", "eq_ring_v1"}, {"OHS_EQ_NO_PRIO", "eq_no_prio"}, {"OHS_EQ_FORM", "eq_form"},
     {"OHS_EQ_QUAD_FILL", "eq_quad_fill"}, {"OHS_EQ_QUAD_LONE_PORT", "eq_quad_lone_port"},
+    {"OHS_EQ_QUAD_CLUSTER_PORT", "eq_quad_cluster_port"},
     {"OHS_EQ_WG_WAVES", "eq_wg_waves"}, {"OHS_EQ_LDS", "eq_lds"}, {"OHS_NO_OVERLAP", "no_overlap"},
     {"OHS_FORCE_OVERLAP", "force_overlap"}, {"OHS_XCD_SPLIT", "xcd_split"}, {"OHS_OVERLAP_CUTS", "overlap_cuts"},
     {"OHS_CONV_CU_MASK", "conv_cu_mask"}, {"OHS_MAC_NO_XCD", "mac_no_xcd"}, {"OHS_HOST_PIPE_TRACE", "host_pipe_trace"},
@@ -96,6 +97,7 @@ bool tuning_set(const std::string &key, const std::string &value)
     if (key == "eq_form") return one(&t.eq_form);
     if (key == "eq_quad_fill") return one(&t.eq_quad_fill);
     if (key == "eq_quad_lone_port") return one(&t.eq_quad_lone_port);
+    if (key == "eq_quad_cluster_port") return one(&t.eq_quad_cluster_port);
     if (key == "eq_wg_waves") {
         if (!one(&t.eq_wg_waves)) return false;
         const int w = t.eq_wg_waves;

@@ -36,6 +36,9 @@ struct Tuning {
     int eq_quad_lone_port = 0;              // 1: the quad body's loop of round 12, the port's two stores and its load each alone in the
                                             // slot of its step, instead of the loop with one memory cluster per group (experiments
                                             // build only; the A/B and the "same bits" test of DESIGN.md 4.5, round 15)
+    int eq_quad_cluster_port = 0;           // 1: the quad body's loop of round 15, store, store, load in one cluster per group, instead of
+                                            // the loop with one merged store per group (experiments build only; the A/B and the
+                                            // "same bits" test of DESIGN.md 4.5, round 17)
     int eq_wg_waves = 0;                    // 0: 1 wave per workgroup below one wave per CU, else 4
     int eq_lds = 0;                         // LDS reservation per EQ workgroup, bytes
     // ohs_batch_process

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Cycles and shader clock inside k_eq_ring (experiment build: OHS_BUILD_TAG=eqstamps OHS_EXTRA_DEFS=-DOHS_EQ_STAMPS): s_memtime
 (shader clock) against s_memrealtime (100 MHz) over every wave of EVERY EQ launch of one steady-state headline step, with
-and without the convolution running beside it, for the quad ring's loops: the library's (one memory cluster per group), round
-12's with the port's memory instructions each alone in its slot (Tuning::eq_quad_lone_port; the only loop of a library from
-before round 15, "v_nop" there) and that one with the fill instruction (Tuning::eq_quad_fill).  Per launch: shader-clock ticks per sample (independent of the clock), the clock, and how far the
+and without the convolution running beside it, for the quad ring's loops: the library's (one merged store per group; in a
+library from before round 17 the one below), round 15's with store, store, load in one cluster per group
+(Tuning::eq_quad_cluster_port), round 12's with the port's memory instructions each alone in its slot
+(Tuning::eq_quad_lone_port; the only loop of a library from before round 15, "v_nop" there) and that one with the fill
+instruction (Tuning::eq_quad_fill).  Per launch: shader-clock ticks per sample (independent of the clock), the clock, and how far the
 slowest wave ends behind the median one (a launch ends with its slowest wave); per step the line through the six launches'
 median ticks over their samples: slope = the loop's ticks per sample, intercept = a launch's fixed ticks.
     OHS_LIB=open_headstage_amd/libohs_hip_eqstamps.so python tools/eq_clock.py [--json FILE] [streams ...]"""
@@ -45,13 +47,18 @@ def launches(st):
 
 
 HAS_LONE = L.ohs_debug_set_tuning(b"eq_quad_lone_port", b"0") == 0
-LOOPS = ("cluster", "lone", "fill") if HAS_LONE else ("v_nop", "fill")
+HAS_CLUSTER = L.ohs_debug_set_tuning(b"eq_quad_cluster_port", b"0") == 0
+LOOPS = ("merged", "cluster", "lone", "fill") if HAS_CLUSTER else ("cluster", "lone", "fill") if HAS_LONE else ("v_nop", "fill")
+if os.environ.get("EQ_CLOCK_LOOPS"):        # a subset, in this order
+    LOOPS = tuple(l for l in os.environ["EQ_CLOCK_LOOPS"].split(",") if l in LOOPS)
 
 
 def run(S, conv_on, loop, sink):
     assert L.ohs_debug_set_tuning(b"eq_quad_fill", str(int(loop == "fill")).encode()) == 0
     if HAS_LONE:
         assert L.ohs_debug_set_tuning(b"eq_quad_lone_port", str(int(loop == "lone")).encode()) == 0
+    if HAS_CLUSTER:
+        assert L.ohs_debug_set_tuning(b"eq_quad_cluster_port", str(int(loop == "cluster")).encode()) == 0
     bp = ohs.BatchProcessor(S, num_bands=10)
     irs = synth.hrir_set(512)
     for p in range(4):

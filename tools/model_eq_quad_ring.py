@@ -47,8 +47,24 @@ unchanged.  In-place safety: stores only move LATER, and so does the load, which
 outputs exist -- so a store never passes the load of the sample whose address it takes.  Ring(in_place=True) runs a launch
 on one array and refuses a load of an address that a store has written.
 
+The merged variants D1 / D2 / D1W / D2W issue FEWER memory instructions for the same bytes (the loop pays per instruction):
+    D1   one store per group.  Step 8 parks Zc in H0 ("hold"), step 10's slot moves H0's lanes a, d to lanes b, c ("qmove":
+         v_mov_b32_dpp quad_perm 0,0,3,3), step 15's slot takes Zc's lanes a, d into H0 ("merge": v_cndmask under a constant
+         SGPR-pair mask -- a plain read of Zc, VCC stays the injects'), and one store ("mstore") carries the group's 16
+         outputs, lanes b, c at the addresses of lanes a, d seven samples earlier.  Store and load issue in the NEXT group's
+         step-1 slot; an iteration's last group issues its own in step 16 behind inject A.
+    D2   one store and one load per two groups.  "xhalf" is v_permlane32_swap vdst, src: lanes 32 .. 63 of vdst change
+         places with lanes 0 .. 31 of src.  With vdst = the even group's merged H0 and src = the odd group's H1, H1 holds the
+         even group's outputs in row 1 and its own in row 3: one "pstore".  One "pload" fetches the even group's inputs into
+         row 1 and the odd group's into row 3 of X; xhalf S, X brings row 1 to row 3 of S for the even group's injects.
+    D1W / D2W   the same with the wait (and its 4-byte partner) directly in front of the cluster's memory instructions
+         instead of in step 14's slot, which then carries nothing.
+No holding register is live across the end of an iteration in any of them.  check_waits() walks the loop with the memory
+instructions in flight and fails where an inject or an exchange reads a register whose load the waits have not covered.
+
 hazards() walks the steady-state loop and gives, per DPP read, the distance in issue slots to the register's last VALU
-writer; check_hazards() fails below 2 (gfx9 / CDNA: two wait states between a VALU write and a DPP read of a VGPR).
+writer; check_hazards() fails below 2 (gfx9 / CDNA: two wait states between a VALU write and a DPP read of a VGPR; the
+same between a VALU write of either operand and a v_permlane32_swap).
 
 Run: python tools/model_eq_quad_ring.py
 """
@@ -94,8 +110,20 @@ def lane_constants(table):
     return c1, c2
 
 
-PORTS = (None, "C1", "C2", "C3")    # where the port's three memory instructions issue (group_program)
+PORTS = (None, "C1", "C2", "C3", "D1", "D2", "D1W", "D2W")    # where and how the port's memory instructions issue (group_program)
 HOLD = ("H0", "H1", "H2")           # holding registers of the cluster variants: a parked store's value
+MERGED_PORTS = ("D1", "D1W")        # one store per group: both half ports' outputs merged in one register
+PAIR_PORTS = ("D2", "D2W")          # one store and one load per two groups: two groups' registers exchanged by halves
+WAIT_IN_CLUSTER = ("D1W", "D2W")    # the wait stands in front of the cluster's memory instructions, not in step 14's slot
+ROW = _lane >> 4
+MERGE_LANES = (ROLE == 0) | (ROLE == 3)     # the merge takes Zc here and keeps the holding register's lanes b, c
+# a merged store behind step m (a group's step 15): lanes a, d hold step m's outputs, lanes b, c those of step m - 7
+MSTORE_SAMPLE = np.array([-1, -8, -10, -3])[ROLE] - 4 * QUAD
+# a pair's store behind step m (the odd group's step 15): row 3 as the merged store, row 1 what lane + 32 held 16 steps before
+PAIR_LANES = (ROW == 1) | (ROW == 3)
+PSTORE_SAMPLE = np.where(ROW == 3, MSTORE_SAMPLE, MSTORE_SAMPLE[(_lane + 32) % LANES] - G)
+# a pair's load for the groups (e, e + 1), from 16 e: row 3 the inputs of group e + 1, row 1 those of group e as lane + 32 takes them
+PX_SAMPLE = np.where(ROW == 3, X_SAMPLE + G, X_SAMPLE[(_lane + 32) % LANES])
 
 
 def _memory_slots(g, K, port):
@@ -116,6 +144,45 @@ def _memory_slots(g, K, port):
     return {8: [("hold", t + 8, "H2", "Z0")], 10: [],          # ... the odd one its first, and issues all six
             15: [("store", t - 8, "H0"), ("store", t - 1, "H1"), ("store", t + 8, "H2"), ("store", t + 15, "Z1"),
                  ("load", t + 15, xb, g - 1 + K), ("load", t + 15, x, g + K)] + ([("nop", t + 15)] if (g + 1) % K == 0 else [])}
+
+
+def _merged_slots(g, K, port):
+    """{s: instructions} of every slot of group g that carries something, for the variants D1 / D1W / D2 / D2W"""
+    t = G * g
+    first, last = g % K == 0, (g + 1) % K == 0
+    inside = port in WAIT_IN_CLUSTER
+    if port in MERGED_PORTS:
+        x, xn, xb = f"x{g % K}", f"x{(g + 1) % K}", f"x{(g - 1) % K}"
+        slots = {8: [("hold", t + 8, "H0", "Z0")], 9: [("inject", t + 9, "B", x)], 10: [("qmove", t + 10, "H0")],
+                 15: [("merge", t + 15, "H0", "Z1")], 16: [("inject", t + 16, "A", xn)]}
+        if not inside:
+            slots[14] = [("wait", t + 14, xn), ("nop4", t + 14)]
+        if not first:       # the group before's store and load
+            slots[1] = ([("wait", t + 1, xn), ("nop4", t + 1)] if inside else []) + [("mstore", t - 1, "H0"), ("load", t + 1, xb, g - 1 + K)]
+        if last:            # ... but the last group's own: no holding register is live across the end of an iteration
+            slots[16] += (([("wait", t + 16, f"x{(g + 2) % K}"), ("nop4", t + 16)] if inside else []) +
+                          [("mstore", t + 15, "H0"), ("load", t + 16, x, g + K)])
+        return slots
+    assert port in PAIR_PORTS and K % 2 == 0, (port, K)
+    # (the wait in front of a cluster cannot cover that cluster's own load: with two registers in rotation it would have to)
+    assert not inside or K >= 6, (port, K)
+    K2 = K // 2
+    j = (g % K) // 2
+    X, Xn, Xb = f"X{j}", f"X{(j + 1) % K2}", f"X{(j - 1) % K2}"
+    if g % 2 == 0:          # the even group: its inputs are in S, its merged outputs wait in H0 for the odd group's
+        slots = {8: [("hold", t + 8, "H0", "Z0")], 9: [("inject", t + 9, "B", "S")], 10: [("qmove", t + 10, "H0")],
+                 15: [("merge", t + 15, "H0", "Z1")], 16: [("inject", t + 16, "A", X)]}
+        if not first:       # the pair before's: H1 takes H0's row 3 into its row 1; one store, one load for two groups
+            slots[1] = [("xhalf", t + 1, "H0", "H1")]
+            slots[2] = ([("wait", t + 2, Xn), ("nop4", t + 2)] if inside else []) + [("pstore", t - 1, "H1"), ("pload", t + 2, Xb, g - 2 + K)]
+        return slots
+    slots = {8: [("hold", t + 8, "H1", "Z0")], 9: [("inject", t + 9, "B", X)], 10: [("qmove", t + 10, "H1")],
+             14: ([] if inside else [("wait", t + 14, Xn), ("nop4", t + 14)]) + [("xhalf", t + 14, "S", Xn)],   # S: the next even group's inputs
+             15: [("merge", t + 15, "H1", "Z1")], 16: [("inject", t + 16, "A", "S")]}
+    if last:                # (the store offsets' advance goes behind the last cluster: the slot's ("nop", step))
+        slots[16] += ([("xhalf", t + 16, "H0", "H1")] + ([("wait", t + 16, f"X{(j + 2) % K2}"), ("nop4", t + 16)] if inside else []) +
+                      [("pstore", t + 15, "H1"), ("pload", t + 16, X, g - 1 + K), ("nop", t + 16)])
+    return slots
 
 
 def group_program(g, K=K_DEFAULT, fill=False, port=None):
@@ -142,12 +209,15 @@ def group_program(g, K=K_DEFAULT, fill=False, port=None):
     register is live across the end of an iteration (K even), so the launch's C++ head and tail stay what they are."""
     prog = []
     own = (g + 1) % K == 0
-    mem = _memory_slots(g, K, port)
+    merged = _merged_slots(g, K, port) if port in MERGED_PORTS + PAIR_PORTS else None
+    mem = _memory_slots(g, K, port) if merged is None else {}
     for s in range(1, G + 1):
         step = G * g + s
         zc, zo = f"Z{step & 1}", f"Z{(step - 1) & 1}"
         prog += [("alpha", step, zc), ("delta", step, zo)]
-        if mem.get(s):
+        if merged is not None:
+            prog += merged.get(s) or [("fill", step, "F") if fill and not (own and s in LOOP_OWN_SLOTS) else ("nop", step)]
+        elif mem.get(s):
             prog += mem[s]
         elif s == 9:
             prog.append(("inject", step, "B", f"x{g % K}"))
@@ -170,16 +240,41 @@ def _program(g, K, fill=False, port=None):
     return group_program(g, K, True) if fill else group_program(g, K)
 
 
+LOADS = ("load", "pload")
+MEMORY = ("load", "store", "mstore", "pstore", "pload")
+
+
 def wait_count(K=K_DEFAULT, port=None):
     """vmcnt of a group's wait: the memory instructions issued behind the load it waits for (they retire in issue order).
     Where the groups of a pair differ (C3), the smaller count: it is right for one and waits a little longer in the other."""
     prog = [i for g in range(0, 2 * K + 2) for i in _program(g, K, port=port)]
     counts = []
-    for at in [j for j, i in enumerate(prog) if i[0] == "wait"][-2:]:
+    waits = [j for j, i in enumerate(prog) if i[0] == "wait"]
+    # (the merged variants: every wait of an iteration -- the last group's stands elsewhere than the others')
+    for at in waits[-2:] if port not in MERGED_PORTS + PAIR_PORTS else [j for j in waits if prog[j][1] > G * (K + 2)]:
         reg = prog[at][2]
-        ld = max(j for j, i in enumerate(prog[:at]) if i[0] == "load" and i[2] == reg)
-        counts.append(sum(1 for i in prog[ld + 1:at] if i[0] in ("load", "store")))
+        ld = max(j for j, i in enumerate(prog[:at]) if i[0] in LOADS and i[2] == reg)
+        counts.append(sum(1 for i in prog[ld + 1:at] if i[0] in MEMORY))
     return min(counts)
+
+
+def check_waits(K=K_DEFAULT, port=None, count=None):
+    """Walks the steady-state loop with the memory instructions in flight (they retire in issue order; a wait leaves the
+    last `count` -- wait_count(K, port) -- of them) and fails where an inject or a half exchange reads a register whose
+    load has not been waited for.  -> the number of reads checked"""
+    count = wait_count(K, port) if count is None else count
+    flight, reads = [], 0
+    for g in range(0, 4 * K):
+        for i in _program(g, K, port=port):
+            if i[0] in MEMORY:
+                flight.append(i[2] if i[0] in LOADS else None)
+            elif i[0] == "wait":
+                flight = flight[max(0, len(flight) - count):] if count else []
+            elif i[0] in ("inject", "xhalf") and g >= 2 * K:
+                for reg in ((i[3],) if i[0] == "inject" else i[2:4]):
+                    assert reg not in flight, (i, "reads a register whose load is still in flight")
+                    reads += 1
+    return reads
 
 
 def hazards(K=K_DEFAULT, extra=(), fill=False, port=None):
@@ -203,6 +298,15 @@ def hazards(K=K_DEFAULT, extra=(), fill=False, port=None):
         elif op == "fill": dpp_read, write = ins[2], ins[2]
         elif op == "valu": dpp_read, write = ins[1], ins[2]
         elif op == "hold": write = ins[2]                          # (a plain VALU read of Zc: no wait states needed)
+        elif op == "qmove": dpp_read, write = ins[2], ins[2]       # v_mov_b32_dpp on the holding register
+        elif op == "merge": write = ins[2]                         # (v_cndmask under an SGPR mask: plain reads)
+        elif op == "xhalf":
+            # v_permlane32_swap: a VALU write of EITHER operand needs two wait states before it, as a DPP read does; it
+            # writes both (a register that a load wrote is the wait's business: check_waits)
+            for reg in ins[2:4]:
+                if reg in last_write and pos >= len(prog) // 2:
+                    out.append((op, ins[1], reg, pos - last_write[reg] - 1))
+                last_write[reg] = pos
         if dpp_read is not None and dpp_read in last_write and pos >= len(prog) // 2:     # (the second pass: all writers seen)
             out.append((op, ins[1], dpp_read, pos - last_write[dpp_read] - 1))
         if write is not None:
@@ -239,6 +343,7 @@ class Ring:
         self.r = {k: np.zeros(LANES, F) for k in ["Z0", "Z1", "Zp", "G", "P"]}
         self.r["F"] = np.zeros(LANES, np.uint32)        # the fill's own register
         self.r.update({h: np.zeros(LANES, F) for h in HOLD})
+        self.r.update({k: np.zeros(LANES, F) for k in ["S"] + [f"X{j}" for j in range(K // 2)]})   # the pair variants' inputs
         # in place the outputs go where the inputs are: load() then refuses an address that a store has written
         self.y = self.x if in_place else np.zeros(self.n, F)
         self.stored = np.zeros(self.n, np.int32)
@@ -250,6 +355,15 @@ class Ring:
     def load(self, g):
         i = G * g + X_SAMPLE
         ok = CONV & (i >= 0) & (i < self.n)
+        v = np.zeros(LANES, F)
+        v[ok] = self.x[i[ok]]
+        assert self.y is not self.x or not self.stored[i[ok]].any(), "an input is read after a store to its address"
+        return v
+
+    def pload(self, e):
+        """a pair's load: row 1 the inputs of group e, row 3 those of group e + 1"""
+        i = G * e + PX_SAMPLE
+        ok = PAIR_LANES & (i >= 0) & (i < self.n)
         v = np.zeros(LANES, F)
         v[ok] = self.x[i[ok]]
         assert self.y is not self.x or not self.stored[i[ok]].any(), "an input is read after a store to its address"
@@ -280,8 +394,23 @@ class Ring:
                 ok = STORE_LANES & (i >= 0) & (i < self.n)
                 self.y[i[ok]] = r[ins[2]][ok]
                 self.stored[i[ok]] += 1
+            elif o in ("mstore", "pstore"):     # one store for both half ports / for two groups
+                i = step + (MSTORE_SAMPLE if o == "mstore" else PSTORE_SAMPLE)
+                ok = (CONV if o == "mstore" else PAIR_LANES) & (i >= 0) & (i < self.n)
+                self.y[i[ok]] = r[ins[2]][ok]
+                self.stored[i[ok]] += 1
             elif o == "hold":
                 r[ins[2]] = r[ins[3]].copy()
+            elif o == "qmove":                  # lanes a, d of the parked value go to lanes b, c
+                r[ins[2]] = r[ins[2]][QP_BETA]
+            elif o == "merge":                  # lanes a, d take Zc, lanes b, c keep the parked value
+                r[ins[2]] = np.where(MERGE_LANES, r[ins[3]], r[ins[2]]).astype(F)
+            elif o == "xhalf":                  # lanes 32 .. 63 of the first change places with lanes 0 .. 31 of the second
+                a, b = r[ins[2]].copy(), r[ins[3]].copy()
+                a[32:], b[:32] = r[ins[3]][:32], r[ins[2]][32:]
+                r[ins[2]], r[ins[3]] = a, b
+            elif o == "pload":
+                r[ins[2]] = self.pload(ins[3])
             elif o == "inject":
                 r["Zp"] = np.where(INJECT_LANES, r[ins[3]][QP_INJECT[ins[2]]], r["Zp"]).astype(F)
             elif o == "load":
@@ -306,7 +435,15 @@ def ring_eq(x, table, state=None, K=K_DEFAULT, mode=0, fill=False, port=None, in
     port: the whole launch in that variant's program (C3: to the end of a pair of groups); in_place: on one array"""
     ring = Ring(x, table, state, K, mode, in_place)
     last = n_groups(ring.n)
-    for g in range(-1, last + (last % 2 if port == "C3" else 0)):
+    first = -1
+    if port in MERGED_PORTS:        # a group's store issues in the group behind it
+        last += 1
+    elif port in PAIR_PORTS:        # whole pairs from an even group on, and the last pair's store issues in the pair behind it
+        first, last = -2, last + last % 2 + 2
+        ring.r["S"] = ring.load(-2)
+        for p in range(-1, K // 2 - 1):
+            ring.r[f"X{p % (K // 2)}"] = ring.pload(2 * p)
+    for g in range(first, last + (last % 2 if port == "C3" else 0)):
         ring.run(_program(g, K, fill, port))
     assert np.all(ring.stored == 1), "every output is stored exactly once"
     return ring.y, ring.s_save
@@ -395,13 +532,17 @@ def check_nonfinite_reach(nb=10, n=6000, k=3001, seed=6):
 
 # ---- the launch as csrc/eq_quad_ring_body.hpp runs it: the C++ form around an interpreter of the generated asm TEXT ----------
 
-def run_asm(lines, v, x, y, stored, n, iters):
+def run_asm(lines, v, x, y, stored, n, iters, merge_lanes=None):
     """`iters` iterations of the generated loop (tools/gen_eq_quad_ring_asm.py: loop_asm) on the register file v (v[k]: 64
     lanes; uint32 for the offsets v0, v1, v9, v10, float32 elsewhere).  Buffer accesses are range-checked against 4 n as the
     hardware checks a raw buffer: VGPR offset + instruction offset >= num_records is dropped / reads 0.  VCC = every lane
-    but c, d of the conveyor quads."""
+    but c, d of the conveyor quads; %[mk], the merge's SGPR-pair mask = merge_lanes (MERGE_LANES).  Memory instructions
+    retire in issue order and s_waitcnt vmcnt(N) leaves the last N in flight: an inject or a half exchange that reads a
+    register whose load is still in flight is refused."""
     import re
     vcc = ~INJECT_LANES
+    mk = MERGE_LANES if merge_lanes is None else merge_lanes
+    flight = []             # the memory instructions in flight: the register a load writes, None for a store
     ops = {"v_add_f32_dpp": np.add, "v_mul_f32_dpp": np.multiply, "v_sub_f32_dpp": np.subtract}
 
     def dpp(src, ctrl):
@@ -419,9 +560,26 @@ def run_asm(lines, v, x, y, stored, n, iters):
                 v[d] = ops[op](dpp(v[a], ctrl), v[b]).astype(F)
             elif op == "v_cndmask_b32_dpp":
                 d, a, b = (int(r[1:]) for r in t[1:4])
+                assert a not in flight, (l, "reads a register whose load is still in flight")
                 v[d] = np.where(vcc, v[b], dpp(v[a], re.search(r"quad_perm:\[[\d,]+\]", l).group(0))).astype(F)
+            elif op == "s_waitcnt":
+                keep = int(re.search(r"vmcnt\((\d+)\)", l).group(1))
+                flight = flight[max(0, len(flight) - keep):] if keep else []
+            elif op == "v_mov_b32_dpp":         # the parked value's lanes a, d go to lanes b, c
+                v[int(t[1][1:])] = dpp(v[int(t[2][1:])], re.search(r"quad_perm:\[[\d,]+\]", l).group(0))
+            elif op == "v_cndmask_b32_e64":     # the merge: src1 where the mask is set
+                d, a, b = (int(r[1:]) for r in t[1:4])
+                assert t[4] == "%[mk]", l
+                v[d] = np.where(mk, v[b], v[a]).astype(F)
+            elif op == "v_permlane32_swap_b32":     # lanes 32 .. 63 of vdst change places with lanes 0 .. 31 of src
+                d, a = int(t[1][1:]), int(t[2][1:])
+                assert d not in flight and a not in flight, (l, "reads a register whose load is still in flight")
+                vd, va = v[d].copy(), v[a].copy()
+                vd[32:], va[:32] = v[a][:32], v[d][32:]
+                v[d], v[a] = vd, va
             elif op in ("buffer_store_dword", "buffer_load_dword"):
                 d, a = int(t[1][1:]), int(t[2][1:])
+                flight.append(d if op == "buffer_load_dword" else None)
                 off = v[a].astype(np.uint64) + int(re.search(r"offset:(\d+)", l).group(1))
                 ok = off < 4 * n
                 i = (off[ok] // 4).astype(np.int64)
@@ -444,15 +602,16 @@ def run_asm(lines, v, x, y, stored, n, iters):
                     v.setdefault(k, np.zeros(LANES, np.uint32))
                 v[d] = dpp(v[a], re.search(r"quad_perm:\[[\d,]+\]", l).group(0)) & v[b]
             else:
-                assert op in ("v_nop_e64", "s_waitcnt", "s_nop", "s_add_u32"), l
+                assert op in ("v_nop_e64", "s_nop", "s_add_u32"), l
 
 
-def ring_eq_as_launched(x, table, state=None, lines=None, K=K_DEFAULT, port=None, in_place=False):
+def ring_eq_as_launched(x, table, state=None, lines=None, K=K_DEFAULT, port=None, in_place=False, mutate=None, merge_lanes=None):
     """One launch with the structure of eq_quad_ring_wave: groups -1 .. g0 - 1 in the C++ form (inputs requested two groups
     ahead: xcur, xnext), whole iterations of K groups through run_asm on the generated text with the kernel's offsets, the
     C++ form to the end.  -> (y, new state).  port: the variant `lines` were generated for (the C++ form is the default
     program in any case: its holding registers start from whatever they hold and none is live behind an iteration);
-    in_place: inputs and outputs on one array, every load checked against the stores before it"""
+    in_place: inputs and outputs on one array, every load checked against the stores before it; mutate(v): a test's change
+    to the register file the loop starts from; merge_lanes: run_asm's"""
     ring = Ring(x, table, state, K, in_place=in_place)
     n = ring.n
     xcur, xnext = ring.load(-1), ring.load(0)
@@ -460,6 +619,7 @@ def ring_eq_as_launched(x, table, state=None, lines=None, K=K_DEFAULT, port=None
     iters = (g_hi - 5) // K if g_hi - 5 >= K else 0
     g0 = g_hi - iters * K if iters else -1
     xa = [ring.load(g0 + k) if iters else None for k in range(K)]      # (x0, x1 come from the head: checked below)
+    xp = [ring.pload(g0 + 2 * j) for j in range(1, K // 2)] if iters and port in PAIR_PORTS else None
 
     def group_cpp(g):
         nonlocal xcur, xnext
@@ -490,9 +650,27 @@ def ring_eq_as_launched(x, table, state=None, lines=None, K=K_DEFAULT, port=None
              11: xcur, 12: xnext}
         for k in range(2, K):
             v[11 + k] = xa[k]
-        if port is not None:                # (holding registers: never read before the loop has written them)
+        if port in MERGED_PORTS:
+            # one store per group: lanes b, c carry the outputs of step 8, seven samples in front of lane a's / d's of step 15
+            v[0] = np.where(CONV, (G * (g0 - 1) + 15 + MSTORE_SAMPLE) * 4 - 28, 0xFFFFF000).astype(np.uint32)
+            v[10] = v[9]
+        elif port in PAIR_PORTS:
+            # one store and one load per two groups, rows 1 and 3: v0 from the step 15 of group g0, v1 group g0's pair;
+            # v11: S (group g0's inputs, row 3), v12 ..: X0 (row 3: group g0 + 1's) .. X(K/2 - 1)
+            v[0] = np.where(PAIR_LANES, (G * g0 + 15 + PSTORE_SAMPLE) * 4, 0xFFFFF000).astype(np.uint32)
+            v[1] = np.where(PAIR_LANES, (G * g0 + PX_SAMPLE) * 4, 0xFFFFF000).astype(np.uint32)
+            v[9] = v[10] = np.where(PAIR_LANES, 4 * G * K, 0).astype(np.uint32)
+            for k in range(2, K):
+                del v[11 + k]
+            for j in range(1, K // 2):
+                v[12 + j] = xp[j - 1]
+        if port is not None:
+            assert np.all(v[0][v[0] != 0xFFFFF000] < 2 ** 31)
+            # (holding registers: never read before the loop has written them)
             v.update({20 + k: np.full(LANES, np.nan, F) for k in range(len(HOLD))})
-        run_asm(lines, v, ring.x, ring.y, ring.stored, n, iters)
+        if mutate is not None:
+            mutate(v)
+        run_asm(lines, v, ring.x, ring.y, ring.stored, n, iters, merge_lanes)
         r["Z0"], r["Z1"], r["Zp"], r["G"], r["P"] = v[2], v[3], v[4], v[5], v[6]
         xcur, xnext = v[11], v[12]
         g = g_hi

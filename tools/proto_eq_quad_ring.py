@@ -20,7 +20,11 @@ PROTO_VARIANT selects the loop, every one generated from the model's instruction
     nost / nold / nomem   attribution knock-outs: the stores / the load / all three replaced by v_nop -- the outputs are wrong
                     by construction, so these skip the bit check and only time (what does the port cost the loop?)
     C1 / C2 / C3    the cluster variants of the model's group_program(port=...): bit check and timing as for cur
-tools/ab_proto_eq_quad_port.sh runs them alternating in one call; profiles/r15_proto_eq_quad_port.txt is its table.
+    D1 / D2 / D1W / D2W   the merged variants (round 17): one store per group, one store and one load per two groups, and
+                    each with the wait in front of the cluster; their offset registers are set up as the model's
+                    ring_eq_as_launched sets them up
+tools/ab_proto_eq_quad_port.sh runs them alternating in one call; profiles/r15_proto_eq_quad_port.txt and
+profiles/r17_proto_eq_quad_port.txt are its tables.
 """
 import os
 import subprocess
@@ -42,13 +46,19 @@ assert VARIANT == "cur" or VARIANT in KNOCK_OUT or VARIANT in model.PORTS, VARIA
 def main():
     port = VARIANT if VARIANT in model.PORTS else None
     model.check_hazards(K, port=port)
+    model.check_waits(K, port=port)
     body = gen.gen_loop(K, port=port)
     # (a knock-out keeps the slot: v_nop is the 8-byte encoding the loop has wherever a slot carries nothing)
     body = ["v_nop_e64" if l.startswith(KNOCK_OUT.get(VARIANT, ())) else l for l in body]
     slots = sum(1 for l in body if not l.startswith((".", "1:"))) - 4
     asm = "\n".join('        "' + l + '\\n"' for l in body)
     xdecl = "\n".join(f"    float x{k} = conv ? src[base + 16 * (G0 + {k}) + xs] : 0.0f;" for k in range(K))
-    xops = ", ".join(f'[x{k}] "+{{v{11 + k}}}"(x{k})' for k in range(K))
+    nx = K
+    if port in model.PAIR_PORTS:        # v11: S, v12: X0 (row 3: group G0 + 1), v13 ..: the pairs (G0 + 2 j, G0 + 2 j + 1)
+        nx = 1 + K // 2
+        xdecl = "\n".join([xdecl.split("\n")[0], xdecl.split("\n")[1]] +
+                          [f"    float x{1 + j} = pair ? src[base + 16 * (G0 + {2 * j}) + pxs] : 0.0f;" for j in range(1, K // 2)])
+    xops = ", ".join(f'[x{k}] "+{{v{11 + k}}}"(x{k})' for k in range(nx))
     src = r'''
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -58,6 +68,7 @@ def main():
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int NB = 10, K = %(K)d, G0 = 5, PAD = 16 * (G0 + 1);
 constexpr bool CHECK = %(check)d;       // (a knock-out variant's outputs are wrong by construction)
+constexpr int MERGED = %(merged)d;      // 1: one store per group (D1, D1W); 2: one store and one load per two groups (D2, D2W)
 // raw buffer resource over `bytes` bytes (stride 0, DATA_FORMAT 32)
 __device__ u32x4 rsrc(const void *p, unsigned bytes)
 {
@@ -89,7 +100,21 @@ __global__ __launch_bounds__(64) void k(const float *src, float *dst, long long 
     unsigned voff_st = (q >= 12 && (role == 0 || role == 3)) ? (unsigned)(16 * (G0 - 1) + ss) * 4u : 0xFFFFF000u;
     unsigned voff_ld = conv ? (unsigned)(16 * G0 + xs) * 4u : 0xFFFFF000u;
     const bool st_lane = conv && (role == 0 || role == 3);
-    const unsigned inc_ld = conv ? 64u * K : 0u, inc_st = st_lane ? 64u * K : 0u;
+    unsigned inc_ld = conv ? 64u * K : 0u, inc_st = st_lane ? 64u * K : 0u;
+    // the merged variants (model_eq_quad_ring.py: MSTORE_SAMPLE, PSTORE_SAMPLE, PX_SAMPLE; ring_eq_as_launched)
+    const int row = lane >> 4, q3 = (lane | 32) >> 2;
+    const bool pair = row == 1 || row == 3;
+    const int ms = (role == 0 ? -1 : role == 1 ? -8 : role == 2 ? -10 : -3);
+    const int pxs = (role == 0 ? 71 : role == 1 ? 69 : role == 2 ? 62 : 60) - 4 * q3 + (row == 3 ? 16 : 0);
+    if (MERGED == 1) {
+        voff_st = conv ? (unsigned)(16 * (G0 - 1) + 15 + ms - 4 * q) * 4u - 28u : 0xFFFFF000u;
+        inc_st = inc_ld;
+    } else if (MERGED == 2) {
+        voff_st = pair ? (unsigned)(16 * G0 + 15 + ms - 4 * q3 - (row == 1 ? 16 : 0)) * 4u : 0xFFFFF000u;
+        voff_ld = pair ? (unsigned)(16 * G0 + pxs) * 4u : 0xFFFFF000u;
+        inc_ld = inc_st = pair ? 64u * K : 0u;
+    }
+    const unsigned long long mk = 0x9999999999999999ull;    // lanes a, d of every quad: the merge takes Zc there
 %(xdecl)s
     float Z0 = 0.f, Z1 = 0.f, Zp = 0.f, Gr = 0.f, P = 0.f;
     unsigned cnt = 0u - (unsigned)iters;
@@ -99,7 +124,7 @@ __global__ __launch_bounds__(64) void k(const float *src, float *dst, long long 
 %(asm)s
         : [Z0] "+{v2}"(Z0), [Z1] "+{v3}"(Z1), [Zp] "+{v4}"(Zp), [Gr] "+{v5}"(Gr), [P] "+{v6}"(P), [vs] "+{v0}"(voff_st),
           [vl] "+{v1}"(voff_ld), %(xops)s, [cnt] "+s"(cnt)
-        : [C1] "{v7}"(C1), [C2] "{v8}"(C2), [incl] "{v9}"(inc_ld), [incs] "{v10}"(inc_st), [rin] "s"(rin), [rout] "s"(rout)
+        : [C1] "{v7}"(C1), [C2] "{v8}"(C2), [incl] "{v9}"(inc_ld), [incs] "{v10}"(inc_st), [rin] "s"(rin), [rout] "s"(rout), [mk] "s"(mk)
         : "memory", "scc", "vcc", "v20", "v21", "v22");
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
     if (lane == 0 && ticks) ticks[blockIdx.x] = t1 - t0;
@@ -181,7 +206,8 @@ int main()
     printf("a lone wave: %%.3f s_memtime ticks per sample\n", (double)tk / (double)total);
     return bad_total ? 2 : 0;
 }
-''' % {"K": K, "asm": asm, "xdecl": xdecl, "xops": xops, "slots": slots, "check": int(VARIANT not in KNOCK_OUT), "variant": VARIANT}
+''' % {"K": K, "asm": asm, "xdecl": xdecl, "xops": xops, "slots": slots, "check": int(VARIANT not in KNOCK_OUT), "variant": VARIANT,
+       "merged": 1 if port in model.MERGED_PORTS else 2 if port in model.PAIR_PORTS else 0}
     tag = ("" if VARIANT == "cur" else "_" + VARIANT) + ("" if K == model.K_DEFAULT else f"_k{K}")
     path = f"/tmp/proto_eq_quad_ring{tag}.hip"
     open(path, "w").write(src)
