@@ -1,4 +1,4 @@
-"""Builds libohs_hip.so (HIP kernels + C ABI) for gfx950, in-tree.
+"""Builds libohs_hip.so (HIP kernels + C ABI) and libohs_scene.so (the same objects + the ohs_scene_* entries) for gfx950, in-tree.
 
     python -m open_headstage_amd.build [--force]
 
@@ -44,6 +44,10 @@ STAMP = os.path.join(HERE, f"libohs_hip_{TAG}.stamp" if TAG else "libohs_hip.sta
 # next to the library at build time: DESIGN.md quotes them and tests/test_cpu_host_logic.py holds k_eq_ring to its
 # 32-VGPR budget with them
 RESOURCES = os.path.join(HERE, f"libohs_hip_{TAG}.resources.json" if TAG else "libohs_hip.resources.json")
+# The SCENE library (include/ohs_scene.h): the product's object files plus api_scene.o, exporting ohs_scene_* and nothing else
+# (csrc/scene_exports.map).  Untagged build only; libohs_hip.so links without api_scene.o.
+SCENE_LIB = os.path.join(HERE, "libohs_scene.so")
+SCENE_UNIT = ("api_scene.hip", [])
 ARCH = "gfx950"
 
 
@@ -56,6 +60,7 @@ def _units():
         ("conv_os_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),   # the overlap-save plan of the P = 1 path
         ("conv_lb_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),   # block 2048 / FFT 4096 for long impulse responses
         ("conv_xb_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),   # block 8192 / FFT 16384 in one kernel: their long out-of-place calls
+        ("conv_objects_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),   # K moving sources per stream (libohs_scene.so reaches it)
         # (experiments builds only: OHS_MAC_TB / OHS_MAC_PI fix the MAC's register tile)
         ("conv_mac_kernels.hip", [f"-D{k}={os.environ[k]}" for k in ("OHS_MAC_TB", "OHS_MAC_PI")
                                   if EXPERIMENTS and k in os.environ]),
@@ -92,6 +97,9 @@ def _deps(src: str) -> list[str]:
         deps += sorted(os.path.join(exp_dir, f) for f in os.listdir(exp_dir) if f.endswith((".h", ".hpp", ".inc")))
     deps.append(os.path.join(os.path.dirname(HERE), "include", "ohs_hip.h"))
     deps.append(os.path.join(CSRC, "exports.map"))
+    if src == SCENE_UNIT[0]:
+        deps.append(os.path.join(os.path.dirname(HERE), "include", "ohs_scene.h"))
+        deps.append(os.path.join(CSRC, "scene_exports.map"))
     deps.append(os.path.abspath(__file__))
     return deps
 
@@ -106,8 +114,13 @@ def _unit_hash(src: str, extra: list[str]) -> str:
     return h.hexdigest()
 
 
+def _all_units():
+    """the product's units, and behind them the scene library's own (untagged build only)"""
+    return _units() + ([] if TAG else [SCENE_UNIT])
+
+
 def _current_hashes() -> dict:
-    return {src: _unit_hash(src, extra) for src, extra in _units()}
+    return {src: _unit_hash(src, extra) for src, extra in _all_units()}
 
 
 def _read_stamp() -> dict:
@@ -119,18 +132,18 @@ def _read_stamp() -> dict:
 
 
 def is_current() -> bool:
-    """True when libohs_hip.so exists and was built from exactly the sources in the tree."""
-    return os.path.exists(LIB) and _read_stamp() == _current_hashes()
+    """True when libohs_hip.so (and, untagged, libohs_scene.so) exists and was built from exactly the sources in the tree."""
+    return os.path.exists(LIB) and (bool(TAG) or os.path.exists(SCENE_LIB)) and _read_stamp() == _current_hashes()
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    units = _units()
+    units = _all_units()
     missing = [s for s, _ in units if not os.path.exists(os.path.join(CSRC, s))]
     if missing:
         raise RuntimeError(f"source files missing under {CSRC}: {missing}")
     want = _current_hashes()
     have = _read_stamp()
-    if not force and os.path.exists(LIB) and have == want:
+    if not force and os.path.exists(LIB) and (bool(TAG) or os.path.exists(SCENE_LIB)) and have == want:
         return LIB
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
@@ -155,11 +168,16 @@ def build(force: bool = False, verbose: bool = False) -> str:
             with open(obj + ".hash", "w") as f:
                 f.write(want[src])
     # exported surface = the C ABI (csrc/exports.map); the C++ internals stay local
-    cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB, *objs,
-           "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"), "-lz", "-ldl", "-lpthread"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
+    product_objs = objs[:len(_units())]
+    links = [(LIB, product_objs, "exports.map")]
+    if not TAG:     # the scene library: the same objects + api_scene.o, its own version script
+        links.append((SCENE_LIB, objs, "scene_exports.map"))
+    for lib, lib_objs, vscript in links:
+        cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib, *lib_objs,
+               "-Wl,--version-script=" + os.path.join(CSRC, vscript), "-lz", "-ldl", "-lpthread"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
     res = {}
     for obj in objs:
         try:

@@ -581,19 +581,24 @@ struct SchedRows {
     size_t entries() const { return src ? rows * n : 0; }
 };
 
-// Two arrays of rows into a slot, each packed n apart whatever the caller's stride and the second right behind the first, and ONE
-// copy to the device on st.  -> lease.slot->d: the first array, the second first.entries() behind it.
-static int sched_stage(ohs_batch *b, const SchedRows &first, const SchedRows &second, hipStream_t st, SchedLease &lease)
+// Arrays of rows into a slot, each packed n apart whatever the caller's stride and each right behind the one before, and ONE
+// copy to the device on st.  -> lease.slot->d: the first array, the second first.entries() behind it, and so on.
+static int sched_stage(ohs_batch *b, std::initializer_list<const SchedRows *> arrays, hipStream_t st, SchedLease &lease)
 {
-    const size_t n_first = first.entries(), n_all = n_first + second.entries();
+    size_t n_all = 0;
+    for (const SchedRows *a : arrays) n_all += a->entries();
     const int rc = sched_lease(b, n_all, st, lease);
     if (rc) return rc;
     unsigned *h = lease.slot->h;
-    for (const SchedRows *a : {&first, &second})
+    for (const SchedRows *a : arrays)
         for (size_t r = 0; a->src && r < a->rows; ++r, h += a->n)
             std::memcpy(h, static_cast<const unsigned *>(a->src) + r * a->stride, a->n * sizeof(unsigned));
     HIP_TRY(hipMemcpyAsync(lease.slot->d, lease.slot->h, n_all * sizeof(unsigned), hipMemcpyHostToDevice, st));
     return OHS_OK;
+}
+static int sched_stage(ohs_batch *b, const SchedRows &first, const SchedRows &second, hipStream_t st, SchedLease &lease)
+{
+    return sched_stage(b, {&first, &second}, st, lease);
 }
 
 int ohs_batch_process_scheduled(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t stream_stride,
@@ -976,6 +981,116 @@ int ohs_batch_process_layout_scheduled(ohs_batch *b, const float *d_in, float *d
                                               (long long)out_stream_stride, (long long)out_channel_stride, (int)n_blocks, b->gain, st,
                                               plain ? nullptr : &lr, set_idx[0]);
         if (rc) return rc;
+        if (b->eq_enable && eq_any_enabled(b->eq))      // EQ(gain * conv(x)): the two ear channels, in place, behind the whole call
+            rc = eq_launch(b->eq, d_out, d_out, (long long)out_stream_stride, (long long)out_channel_stride, (long long)frames, st);
+        return rc;
+    };
+    const int rc = body();
+    if (rc == OHS_OK || rc == OHS_ERR_INVALID_ARG) return rc;
+    return batch_mark_failed(b, rc);
+}
+
+// ---- object scenes: K moving sources per stream -> two ears (libohs_scene.so; no entry of ohs_hip.h) -------------------
+// Library-internal: api_scene.hip's shims are the only callers, and exports.map keeps the names local.
+extern "C" int ohsint_batch_set_object_dirs(ohs_batch *b, size_t n_dirs, const float *irs, size_t len)
+{
+    if (!b) return fail(OHS_ERR_INVALID_ARG, "scene is NULL");
+    if (n_dirs > 0) {
+        if (!irs) return fail(OHS_ERR_INVALID_ARG, "irs is NULL");
+        if (n_dirs > 65536) return fail(OHS_ERR_INVALID_ARG, "n_dirs must be at most 65536");
+        if (len == 0 || len > (size_t)BS) return fail(OHS_ERR_INVALID_ARG, "len must be 1 .. 512 (one partition)");
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    DeviceWideSection dws;
+    HIP_TRY(hipDeviceSynchronize());
+    return conv_set_object_dirs(b->conv, b->ctx, n_dirs, irs, len, b->st);
+}
+
+extern "C" int ohsint_batch_last_objects_launch(const ohs_batch *b, int *n_pairs, int *ranges_per_stream, unsigned long long *fading_passes)
+{
+    if (!b || !n_pairs || !ranges_per_stream || !fading_passes) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    *n_pairs = b->conv.last_obj_pairs;
+    *ranges_per_stream = b->conv.last_obj_ranges;
+    *fading_passes = b->conv.last_obj_fading;
+    return OHS_OK;
+}
+
+extern "C" int ohsint_batch_process_objects(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
+                                            size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride,
+                                            size_t n_objects, size_t seg_blocks, const unsigned *dir_idx, const float *obj_gain,
+                                            size_t idx_stride, const unsigned *prev_idx, const float *prev_gain, int switch_mode,
+                                            void *hip_stream)
+{
+    if (!b || !d_in || !d_out || !dir_idx) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    if (n_objects == 0 || n_objects > 64) return fail(OHS_ERR_INVALID_ARG, "n_objects must be 1 .. 64");
+    if (seg_blocks == 0) return fail(OHS_ERR_INVALID_ARG, "seg_blocks is 0");
+    if (switch_mode != 0 && switch_mode != 1) return fail(OHS_ERR_INVALID_ARG, "switch_mode must be OHS_SCENE_SWITCH_RING_OUT or OHS_SCENE_SWITCH_CROSSFADE");
+    ConvState &c = b->conv;
+    if (c.obj_n == 0 || !c.d_obj_ah) return fail(OHS_ERR_INVALID_ARG, "no direction table uploaded (ohs_scene_set_direction_irs)");
+    if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
+    if (b->failed) return batch_refuse_failed(b);
+    if (n_blocks == 0) return OHS_OK;
+    const size_t n_segs = sched_segments(n_blocks, &seg_blocks), frames = n_blocks * BS, S = c.S, K = n_objects;
+    if (idx_stride != 0 && idx_stride < n_segs)
+        return fail(OHS_ERR_INVALID_ARG, "idx_stride is 0 (one row for all streams) or >= the number of segments");
+    if (S * n_segs * K > (size_t)0x7fffffff) return fail(OHS_ERR_INVALID_ARG, "schedule too large");
+    const bool fade = switch_mode == 1, shared = idx_stride == 0;
+    if (!fade) { prev_idx = nullptr; prev_gain = nullptr; }     // (read under CROSSFADE only)
+    // one pass over every row that will be read: the indices against the table, and the passes through old directions
+    const size_t n_rows = shared ? 1 : S;
+    const unsigned *gain_bits = reinterpret_cast<const unsigned *>(obj_gain), *pgain_bits = reinterpret_cast<const unsigned *>(prev_gain);
+    unsigned long long fading = 0;
+    for (size_t r = 0; r < n_rows; ++r) {
+        const unsigned *row = dir_idx + r * idx_stride * K, *grow = gain_bits ? gain_bits + r * idx_stride * K : nullptr;
+        const unsigned *oi = prev_idx ? prev_idx + r * K : nullptr, *og = pgain_bits ? pgain_bits + r * K : (fade ? grow : nullptr);
+        if (oi)
+            for (size_t o = 0; o < K; ++o)
+                if (oi[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "prev_idx entry out of range");
+        if (fade && !oi) oi = row;      // (no boundary at the call's start)
+        for (size_t k = 0; k < n_segs; ++k) {
+            const unsigned *ci = row + k * K, *cg = grow ? grow + k * K : nullptr;
+            for (size_t o = 0; o < K; ++o)
+                if (ci[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "dir_idx entry out of range");
+            if (fade)
+                for (size_t p = 0; 2 * p < K; ++p) {
+                    bool ch = false;
+                    for (size_t o = 2 * p; o < std::min(2 * p + 2, K); ++o)
+                        ch = ch || ci[o] != oi[o] || (cg ? cg[o] : 0x3f800000u) != (og ? og[o] : 0x3f800000u);
+                    fading += ch ? 1 : 0;
+                }
+            oi = ci; og = cg;
+        }
+    }
+    if (shared) fading *= S;
+    if (!layout_regions_ok(S, K, frames, d_in, in_stream_stride, in_channel_stride, d_out, out_stream_stride, out_channel_stride))
+        return OHS_ERR_INVALID_ARG;
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    SchedLease lease;
+    auto body = [&]() -> int {
+        if (b->join_pending) {      // (a deferred call's last convolutions: the EQ state and d_out may be theirs)
+            HIP_TRY(hipStreamWaitEvent(st, b->chunk_done[(size_t)b->chunk_done_n - 1], 0));
+            b->join_pending = false;
+        }
+        // the rows' staging slot (the scheduled calls'): indices, gains, prev_idx, prev_gain, each packed and one behind the other
+        const SchedRows ri{dir_idx, idx_stride * K, n_rows, n_segs * K}, rg{obj_gain, idx_stride * K, n_rows, n_segs * K},
+            pi{prev_idx, K, n_rows, K}, pg{prev_gain, K, n_rows, K};
+        const int rcs = sched_stage(b, {&ri, &rg, &pi, &pg}, st, lease);
+        if (rcs) return rcs;
+        ConvObjectRows rows;
+        const unsigned *d = lease.slot->d;
+        rows.idx = d; d += ri.entries();
+        if (obj_gain) rows.gain = d;
+        d += rg.entries();
+        if (prev_idx) rows.prev_idx = d;
+        d += pi.entries();
+        if (prev_gain) rows.prev_gain = d;
+        rows.seg_blocks = (int)seg_blocks; rows.stream_stride = shared ? 0 : (int)(n_segs * K); rows.prev_stride = shared ? 0 : (int)K;
+        rows.fade = fade;
+        int rc = conv_launch_objects(c, b->ctx, d_in, (long long)in_stream_stride, (long long)in_channel_stride, d_out,
+                                     (long long)out_stream_stride, (long long)out_channel_stride, (int)n_blocks, b->gain, st, (int)K, rows);
+        if (rc) return rc;
+        c.last_obj_fading = fading;
         if (b->eq_enable && eq_any_enabled(b->eq))      // EQ(gain * conv(x)): the two ear channels, in place, behind the whole call
             rc = eq_launch(b->eq, d_out, d_out, (long long)out_stream_stride, (long long)out_channel_stride, (long long)frames, st);
         return rc;

@@ -30,7 +30,7 @@ void conv_free(ConvState &c)
                                                  c.d_W1, c.d_merged, c.d_merged_alt, c.d_last_in, c.d_irt, c.d_cd_os, c.d_irl,
                                                  c.d_xhist, c.d_xhist_alt, c.d_lb_ring, c.d_lb_cd, c.d_lb_ab, c.d_lb_cd_alt,
                                                  c.d_xb_cd, c.d_xb_ab, c.d_ptail, c.d_ptail_alt, c.d_irs_cd, c.d_irs_H, c.d_irs_t,
-                                                 c.d_lay_cd, c.d_lay_ov, c.d_lay_ov_alt, c.d_lays_cd})
+                                                 c.d_lay_cd, c.d_lay_ov, c.d_lay_ov_alt, c.d_lays_cd, c.d_obj_ah})
         if (d) hipFree(d);
 }
 
@@ -738,7 +738,8 @@ static int layout_build_tables(DeviceCtx *ctx, size_t units, size_t len, Rows ro
     return rc;
 }
 
-// the layout overlap, shared by the single layout and the table of layouts: allocated while either exists, zeroed by every upload
+// the layout overlap, shared by the single layout, the table of layouts and the scenes' direction table: allocated while any of them
+// exists, zeroed by every upload
 static int layout_overlap_zeroed(ConvState &c, hipStream_t st)
 {
     if (!c.d_lay_ov) HIP_TRY(hipMalloc(&c.d_lay_ov, c.S * 8 * 64 * sizeof(float2)));
@@ -749,7 +750,7 @@ static int layout_overlap_zeroed(ConvState &c, hipStream_t st)
 
 static void layout_overlap_release_if_unused(ConvState &c)
 {
-    if (c.d_lay_cd || c.d_lays_cd) return;
+    if (c.d_lay_cd || c.d_lays_cd || c.d_obj_ah) return;
     for (void *d : std::initializer_list<void *>{c.d_lay_ov, c.d_lay_ov_alt})
         if (d) hipFree(d);
     c.d_lay_ov = nullptr; c.d_lay_ov_alt = nullptr;
@@ -888,6 +889,81 @@ int conv_launch_layout_scheduled(ConvState &c, DeviceCtx *ctx, const float *in, 
     if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_layout_irs launch: ") + hipGetErrorString(e));
     std::swap(c.d_lay_ov, c.d_lay_ov_alt);
     c.last_lay_pairs = P; c.last_lay_ranges = a.chunks; c.last_lay_scheduled = rows != nullptr;
+    return OHS_OK;
+}
+
+// The direction table of the object scenes: per direction the two ear spectra by k_ir_spectrum -- the kernel every layout table starts
+// from --, then k_object_tables; in slices, as layout_build_tables builds its units, so that staging and scratch do not grow with it.
+int conv_set_object_dirs(ConvState &c, DeviceCtx *ctx, size_t n_dirs, const float *irs, size_t len, hipStream_t st)
+{
+    DeviceWideSection dws;      // (frees below)
+    if (c.d_obj_ah) hipFree(c.d_obj_ah);
+    c.d_obj_ah = nullptr; c.obj_n = 0; c.obj_len = 0;
+    if (n_dirs == 0) {
+        layout_overlap_release_if_unused(c);
+        if (c.d_lay_ov) {       // (a layout keeps the slabs: zeroed, as behind every upload)
+            HIP_TRY(hipMemsetAsync(c.d_lay_ov, 0, c.S * 8 * 64 * sizeof(float2), st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        return OHS_OK;
+    }
+    constexpr size_t kSlice = 1024;
+    const size_t slice = std::min(n_dirs, kSlice);
+    std::vector<float> padded;  // [slice][2][512]
+    try {
+        padded.resize(slice * 2 * (size_t)BS);
+    } catch (const std::bad_alloc &) {
+        return fail(OHS_ERR_HIP, "out of host memory for the table's staging");
+    }
+    float *d_t = nullptr;       // [slice][2][512] scratch
+    float2 *d_H = nullptr;      // [slice][2][1024] scratch
+    auto body = [&]() -> int {
+        HIP_TRY(hipMalloc(&c.d_obj_ah, (n_dirs + 1) * (size_t)NF * sizeof(float2)));
+        HIP_TRY(hipMemsetAsync(c.d_obj_ah + n_dirs * (size_t)NF, 0, (size_t)NF * sizeof(float2), st));    // (the odd object's partner)
+        const int rco = layout_overlap_zeroed(c, st);
+        if (rco) return rco;
+        HIP_TRY(hipMalloc(&d_t, slice * 2 * (size_t)BS * sizeof(float)));
+        HIP_TRY(hipMalloc(&d_H, slice * 2 * (size_t)NF * sizeof(float2)));
+        for (size_t u0 = 0; u0 < n_dirs; u0 += slice) {
+            const size_t n = std::min(slice, n_dirs - u0);
+            std::fill(padded.begin(), padded.end(), 0.0f);
+            for (size_t r = 0; r < 2 * n; ++r) std::memcpy(&padded[r * BS], irs + (2 * u0 + r) * len, len * sizeof(float));
+            HIP_TRY(hipMemcpyAsync(d_t, padded.data(), n * 2 * (size_t)BS * sizeof(float), hipMemcpyHostToDevice, st));
+            HIP_TRY(launch_ir_spectrum(d_t, (int)(n * 2 * (size_t)BS), (int)(n * 2), d_H, ctx->d_tw, st));
+            HIP_TRY(launch_object_tables(d_H, (int)n, c.d_obj_ah + u0 * (size_t)NF, st));
+            HIP_TRY(hipStreamSynchronize(st));      // (staging and scratch are reused by the next slice)
+        }
+        return OHS_OK;
+    };
+    const int rc = body();
+    for (void *d : std::initializer_list<void *>{d_t, d_H})
+        if (d) hipFree(d);
+    if (rc) {
+        if (c.d_obj_ah) hipFree(c.d_obj_ah);
+        c.d_obj_ah = nullptr;
+        layout_overlap_release_if_unused(c);
+        return rc;
+    }
+    c.obj_n = n_dirs; c.obj_len = len;
+    return OHS_OK;
+}
+
+// The scene call: conv_launch_layout's plan -- the same chunks per stream, the same overlap slabs --, on the direction table
+int conv_launch_objects(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out, long long out_ss,
+                        long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, const ConvObjectRows &rows)
+{
+    if (!c.d_obj_ah || c.obj_n == 0) return fail(OHS_ERR_INVALID_ARG, "no direction table uploaded (ohs_scene_set_direction_irs)");
+    if (n_blocks <= 0) return OHS_OK;
+    const ConvP1Args a = layout_launch_args(c, ctx, in, in_ss, in_cs, out, out_ss, out_cs, n_blocks, gain);
+    ConvObjectsArgs l;
+    l.ahalf = c.d_obj_ah; l.zero_dir = (unsigned)c.obj_n; l.n_objects = n_objects; l.n_pairs = (n_objects + 1) / 2;
+    l.idx = rows.idx; l.gain = rows.gain; l.stream = rows.stream_stride; l.seg = rows.seg_blocks;
+    l.prev_idx = rows.fade ? rows.prev_idx : nullptr; l.prev_gain = rows.fade ? rows.prev_gain : nullptr;
+    l.prev_stream = rows.prev_stride; l.fade = rows.fade ? 1 : 0;
+    const hipError_t e = launch_conv_p1_objects(a, l, st);
+    if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_objects launch: ") + hipGetErrorString(e));
+    std::swap(c.d_lay_ov, c.d_lay_ov_alt);
+    c.last_obj_pairs = l.n_pairs; c.last_obj_ranges = a.chunks;
     return OHS_OK;
 }
 

@@ -221,6 +221,13 @@ struct ConvState {
     size_t lays_n = 0, lays_K = 0, lays_len = 0;
     float4 *d_lays_cd = nullptr;    // [lays_n][ceil(lays_K / 2)][1024]
     bool last_lay_scheduled = false;    // k_conv_p1_layout_irs served the most recent layout launch (ohs_batch_last_layout_scheduled)
+    // The direction table of the object scenes (ohs_scene_set_direction_irs; no entry of ohs_hip.h reaches it): obj_n directions of two
+    // responses each, as the half-sums k_conv_p1_objects combines per pass, and one all-zero row behind them.  The scene call continues
+    // the layout overlap: d_lay_ov / d_lay_ov_alt live while any of the three tables exists.
+    size_t obj_n = 0, obj_len = 0;
+    float2 *d_obj_ah = nullptr;     // [obj_n + 1][1024]
+    int last_obj_pairs = 0, last_obj_ranges = 0;    // the most recent scene launch (ohs_scene_last_launch)
+    unsigned long long last_obj_fading = 0;         // ... and its passes through old directions, summed over the streams
     // ohs_*_set_speakers: what it last loaded into each path (a set_ir from anywhere else forgets it), so that a
     // change of the speaker angles re-loads only the paths whose impulse response really changed
     std::vector<float> spk_ir[4];
@@ -324,6 +331,18 @@ struct ConvLayoutRows {
 int conv_launch_layout_scheduled(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs,
                                  float *out, long long out_ss, long long out_cs, int n_blocks, float gain, hipStream_t st,
                                  const ConvLayoutRows *rows, size_t one_set);
+// the direction table of the object scenes (host array irs[n_dirs][2][len], 1 <= len <= 512; n_dirs == 0 frees it); zeroes the layout
+// overlap; the caller has drained the device
+int conv_set_object_dirs(ConvState &c, DeviceCtx *ctx, size_t n_dirs, const float *irs, size_t len, hipStream_t st);
+// rows of direction indices and gains per object (device memory; validated by the caller), as ConvObjectsArgs reads them
+struct ConvObjectRows {
+    const unsigned *idx = nullptr, *gain = nullptr, *prev_idx = nullptr, *prev_gain = nullptr;
+    int seg_blocks = 1, stream_stride = 0, prev_stride = 0;
+    bool fade = false;
+};
+// n_blocks of every stream's n_objects channels -> two ears, times gain: one launch of k_conv_p1_objects.  Out of place, asynchronous on st
+int conv_launch_objects(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out, long long out_ss,
+                        long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, const ConvObjectRows &rows);
 // the handle's four responses become set `set` of the table, overlaps and history untouched (asynchronous on st)
 int conv_adopt_schedule_set(ConvState &c, size_t set, hipStream_t st);
 // the per-path overlaps from the lazy state with the CURRENT spectra, the lazy state kept valid beside them (tails_both)

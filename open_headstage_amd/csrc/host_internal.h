@@ -11,6 +11,16 @@ struct ohs_batch;
 struct ohs_sofa;
 // api_batch.hip: ohs_batch_set_ir with the impulse response already in memory of the batch's device
 extern "C" int ohsint_batch_set_ir_device(ohs_batch *b, int path, const float *d_ir, size_t len);
+// api_batch.hip: what libohs_scene.so's entries (api_scene.hip, include/ohs_scene.h) call on the batch object a scene owns -- the
+// direction table, the scene call (K moving sources per stream -> two ears, then the layout call's epilogue) and its launch record
+extern "C" int ohsint_batch_set_object_dirs(ohs_batch *b, size_t n_dirs, const float *irs, size_t len);
+extern "C" int ohsint_batch_process_objects(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
+                                            size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride,
+                                            size_t n_objects, size_t seg_blocks, const unsigned *dir_idx, const float *obj_gain,
+                                            size_t idx_stride, const unsigned *prev_idx, const float *prev_gain, int switch_mode,
+                                            void *hip_stream);
+extern "C" int ohsint_batch_last_objects_launch(const ohs_batch *b, int *n_pairs, int *ranges_per_stream,
+                                                unsigned long long *fading_passes);
 
 namespace ohs_host {
 

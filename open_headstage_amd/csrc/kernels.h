@@ -294,6 +294,39 @@ struct ConvLayoutIrArgs {
 };
 // a.chunks as for launch_conv_p1_layout; the host has checked every index against the table
 hipError_t launch_conv_p1_layout_irs(const ConvP1Args &a, const ConvLayoutIrArgs &l, hipStream_t st);
+// the layout kernels' workgroup shape, shared by conv_kernels.hip and conv_objects_kernels.hip: waves per workgroup (one per SIMD),
+// resident waves per SIMD
+#ifndef OHS_LAYOUT_WAVES
+#define OHS_LAYOUT_WAVES 4
+#endif
+#ifndef OHS_LAYOUT_WAVES_PER_SIMD
+#define OHS_LAYOUT_WAVES_PER_SIMD 3
+#endif
+// K moving sources per stream -> two ears (ohs_scene_process; library-internal, no entry of ohs_hip.h): k_conv_p1_objects
+// (conv_objects_kernels.hip), the body of
+// k_conv_p1_layout_irs with a table per DIRECTION instead of per set -- the pair's (C, D) is formed per pass from the two objects' rows
+// of `ahalf` -- and with one direction index and one gain per object, stream and segment: block t uses entry
+// [s * stream + (t / seg) * n_objects + c] of `idx` and `gain`.  A struct of its own, so that the layout kernels' stay what they are.
+// Of ConvP1Args the kernel reads what k_conv_p1_layout reads.
+struct ConvObjectsArgs {
+    const float2 *ahalf;        // [n_dirs + 1][1024] 0.5 (Hl + j Hr) per direction in the paired layout (launch_object_tables); row n_dirs
+                                // is all zero: the partner of an odd last object
+    unsigned zero_dir;          // n_dirs
+    int n_pairs;                // ceil(n_objects / 2)
+    int n_objects;              // odd: channel 2 n_pairs - 1 is not read
+    const unsigned *idx;        // rows of direction indices (device memory), [row][segment][n_objects]
+    const unsigned *gain;       // the same shape, f32 bits; nullptr: 1.0 everywhere
+    int stream;                 // stream s reads its rows at idx + s * stream, gain + s * stream (0: one row for all streams)
+    int seg;                    // blocks per segment
+    const unsigned *prev_idx;   // [row][n_objects] in front of the call's first block, or nullptr: the first segment's own (no change there)
+    const unsigned *prev_gain;  // the same for the gains
+    int prev_stream;            // stream s reads prev_* + s * prev_stream (0: one row for all streams)
+    int fade;                   // 1: CROSSFADE; 0: RING_OUT, no pair fades (prev_* are not read)
+};
+// a.chunks as for launch_conv_p1_layout; the host has checked every index against the table
+hipError_t launch_conv_p1_objects(const ConvP1Args &a, const ConvObjectsArgs &l, hipStream_t st);
+// H[dir][2][1024] (launch_ir_spectrum: left ear, right ear) -> dst[dir][1024] = 0.5 (Hl.x - Hr.y, Hl.y + Hr.x) in the block loop's layout
+hipError_t launch_object_tables(const float2 *H, int n_dirs, float2 *dst, hipStream_t st);
 // cd[set][2][1024] (launch_build_cd per set) -> dst[set][1024] in the block loop's layout, times `scale`
 hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st, float scale = 1.0f);
 // The layout kernels' tables are built with this scale: launch_build_cd's 1/N taken out again, which launch_conv_p1_layout and
