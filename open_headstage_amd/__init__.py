@@ -13,6 +13,7 @@ from .session import HeadTrack, SessionRenderer, nearest_set, plan_calls, render
 from .pcm import WavReader, pcm_decode_device, pcm_encode_device
 from .autoeq import BandSetting, apply_bands, parse_autoeq_csv, parse_autoeq_csv_text
 from .scene import SceneError, SceneProcessor, nearest_directions, rotate_sources
+from .scene2 import BlendSceneProcessor, bracket_directions
 from ._ffi import OhsError
 
 __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter", "ConvolutionEngine",
@@ -20,4 +21,5 @@ __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter
            "process_chain", "BatchProcessor", "NodeBatchProcessor", "OhsError", "BandSetting", "apply_bands",
            "parse_autoeq_csv", "parse_autoeq_csv_text", "LAYOUT_5_1", "LAYOUT_7_1", "SessionRenderer",
            "HeadTrack", "nearest_set", "yaw_rows", "plan_calls", "render_files", "WavReader", "pcm_decode_device",
-           "pcm_encode_device", "SceneProcessor", "SceneError", "rotate_sources", "nearest_directions"]
+           "pcm_encode_device", "SceneProcessor", "SceneError", "rotate_sources", "nearest_directions",
+           "BlendSceneProcessor", "bracket_directions"]

@@ -1,4 +1,5 @@
-"""Builds libohs_hip.so (HIP kernels + C ABI) and libohs_scene.so (the same objects + the ohs_scene_* entries) for gfx950, in-tree.
+"""Builds libohs_hip.so (HIP kernels + C ABI), libohs_scene.so (the same objects + the ohs_scene_* entries) and libohs_scene2.so (the
+same objects + the ohs_scene2_* entries) for gfx950, in-tree.
 
     python -m open_headstage_amd.build [--force]
 
@@ -48,6 +49,10 @@ RESOURCES = os.path.join(HERE, f"libohs_hip_{TAG}.resources.json" if TAG else "l
 # (csrc/scene_exports.map).  Untagged build only; libohs_hip.so links without api_scene.o.
 SCENE_LIB = os.path.join(HERE, "libohs_scene.so")
 SCENE_UNIT = ("api_scene.hip", [])
+# The second SCENE library (include/ohs_scene2.h): the product's object files plus api_scene2.o, exporting ohs_scene2_* and nothing
+# else (csrc/scene2_exports.map).  Untagged build only.
+SCENE2_LIB = os.path.join(HERE, "libohs_scene2.so")
+SCENE2_UNIT = ("api_scene2.hip", [])
 ARCH = "gfx950"
 
 
@@ -61,6 +66,7 @@ def _units():
         ("conv_lb_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),   # block 2048 / FFT 4096 for long impulse responses
         ("conv_xb_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),   # block 8192 / FFT 16384 in one kernel: their long out-of-place calls
         ("conv_objects_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),   # K moving sources per stream (libohs_scene.so reaches it)
+        ("conv_objects_blend_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),   # ... between two directions each (libohs_scene2.so)
         # (experiments builds only: OHS_MAC_TB / OHS_MAC_PI fix the MAC's register tile)
         ("conv_mac_kernels.hip", [f"-D{k}={os.environ[k]}" for k in ("OHS_MAC_TB", "OHS_MAC_PI")
                                   if EXPERIMENTS and k in os.environ]),
@@ -100,6 +106,9 @@ def _deps(src: str) -> list[str]:
     if src == SCENE_UNIT[0]:
         deps.append(os.path.join(os.path.dirname(HERE), "include", "ohs_scene.h"))
         deps.append(os.path.join(CSRC, "scene_exports.map"))
+    if src == SCENE2_UNIT[0]:
+        deps.append(os.path.join(os.path.dirname(HERE), "include", "ohs_scene2.h"))
+        deps.append(os.path.join(CSRC, "scene2_exports.map"))
     deps.append(os.path.abspath(__file__))
     return deps
 
@@ -115,8 +124,12 @@ def _unit_hash(src: str, extra: list[str]) -> str:
 
 
 def _all_units():
-    """the product's units, and behind them the scene library's own (untagged build only)"""
-    return _units() + ([] if TAG else [SCENE_UNIT])
+    """the product's units, and behind them the two scene libraries' own (untagged build only)"""
+    return _units() + ([] if TAG else [SCENE_UNIT, SCENE2_UNIT])
+
+
+def _libs_exist() -> bool:
+    return os.path.exists(LIB) and (bool(TAG) or (os.path.exists(SCENE_LIB) and os.path.exists(SCENE2_LIB)))
 
 
 def _current_hashes() -> dict:
@@ -132,8 +145,9 @@ def _read_stamp() -> dict:
 
 
 def is_current() -> bool:
-    """True when libohs_hip.so (and, untagged, libohs_scene.so) exists and was built from exactly the sources in the tree."""
-    return os.path.exists(LIB) and (bool(TAG) or os.path.exists(SCENE_LIB)) and _read_stamp() == _current_hashes()
+    """True when libohs_hip.so (and, untagged, libohs_scene.so and libohs_scene2.so) exists and was built from exactly the sources in
+    the tree."""
+    return _libs_exist() and _read_stamp() == _current_hashes()
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -143,7 +157,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError(f"source files missing under {CSRC}: {missing}")
     want = _current_hashes()
     have = _read_stamp()
-    if not force and os.path.exists(LIB) and (bool(TAG) or os.path.exists(SCENE_LIB)) and have == want:
+    if not force and _libs_exist() and have == want:
         return LIB
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
@@ -170,8 +184,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
     # exported surface = the C ABI (csrc/exports.map); the C++ internals stay local
     product_objs = objs[:len(_units())]
     links = [(LIB, product_objs, "exports.map")]
-    if not TAG:     # the scene library: the same objects + api_scene.o, its own version script
-        links.append((SCENE_LIB, objs, "scene_exports.map"))
+    if not TAG:     # the scene libraries: the same objects + api_scene.o / api_scene2.o, each its own version script
+        links.append((SCENE_LIB, product_objs + [objs[-2]], "scene_exports.map"))
+        links.append((SCENE2_LIB, product_objs + [objs[-1]], "scene2_exports.map"))
     for lib, lib_objs, vscript in links:
         cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib, *lib_objs,
                "-Wl,--version-script=" + os.path.join(CSRC, vscript), "-lz", "-ldl", "-lpthread"]

@@ -1015,13 +1015,18 @@ extern "C" int ohsint_batch_last_objects_launch(const ohs_batch *b, int *n_pairs
     return OHS_OK;
 }
 
-extern "C" int ohsint_batch_process_objects(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
-                                            size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride,
-                                            size_t n_objects, size_t seg_blocks, const unsigned *dir_idx, const float *obj_gain,
-                                            size_t idx_stride, const unsigned *prev_idx, const float *prev_gain, int switch_mode,
-                                            void *hip_stream)
+// The scene call, one direction per object (dir_idx1 == weight == nullptr: k_conv_p1_objects) or two with a weight (both given:
+// k_conv_p1_objects_blend): one set of checks, one scan over every row that will be read, one staging path, one epilogue.
+static int batch_process_objects_any(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
+                                     size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride, size_t n_objects,
+                                     size_t seg_blocks, const unsigned *dir_idx, const float *obj_gain, size_t idx_stride,
+                                     const unsigned *prev_idx, const float *prev_gain, int switch_mode, void *hip_stream,
+                                     const unsigned *dir_idx1, const float *weight, const unsigned *prev_idx1, const float *prev_weight)
 {
     if (!b || !d_in || !d_out || !dir_idx) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    if ((dir_idx1 == nullptr) != (weight == nullptr)) return fail(OHS_ERR_INVALID_ARG, "dir_idx1 and weight are both NULL or both given");
+    const bool blend = dir_idx1 != nullptr;
+    if (!blend) { prev_idx1 = nullptr; prev_weight = nullptr; }     // (nothing for them to stand in front of)
     if (n_objects == 0 || n_objects > 64) return fail(OHS_ERR_INVALID_ARG, "n_objects must be 1 .. 64");
     if (seg_blocks == 0) return fail(OHS_ERR_INVALID_ARG, "seg_blocks is 0");
     if (switch_mode != 0 && switch_mode != 1) return fail(OHS_ERR_INVALID_ARG, "switch_mode must be OHS_SCENE_SWITCH_RING_OUT or OHS_SCENE_SWITCH_CROSSFADE");
@@ -1033,35 +1038,85 @@ extern "C" int ohsint_batch_process_objects(ohs_batch *b, const float *d_in, flo
     const size_t n_segs = sched_segments(n_blocks, &seg_blocks), frames = n_blocks * BS, S = c.S, K = n_objects;
     if (idx_stride != 0 && idx_stride < n_segs)
         return fail(OHS_ERR_INVALID_ARG, "idx_stride is 0 (one row for all streams) or >= the number of segments");
-    if (S * n_segs * K > (size_t)0x7fffffff) return fail(OHS_ERR_INVALID_ARG, "schedule too large");
+    if ((blend ? 4 : 1) * S * n_segs * K > (size_t)0x7fffffff) return fail(OHS_ERR_INVALID_ARG, "schedule too large");
     const bool fade = switch_mode == 1, shared = idx_stride == 0;
-    if (!fade) { prev_idx = nullptr; prev_gain = nullptr; }     // (read under CROSSFADE only)
-    // one pass over every row that will be read: the indices against the table, and the passes through old directions
+    if (!fade) { prev_idx = nullptr; prev_gain = nullptr; prev_idx1 = nullptr; prev_weight = nullptr; }    // (read under CROSSFADE only)
     const size_t n_rows = shared ? 1 : S;
+    // The blended kernel reads four planes of one shape and, under CROSSFADE, four planes in front of the call that the host always
+    // stages (the first segment's own entries where the caller names none).  A gain in front of the call beside no gain rows: the
+    // rows read as 1.0, so they are staged as that.
+    std::vector<float> ones;
+    std::vector<unsigned> prev;     // [4][n_rows][K]: idx, idx1, weight, gain in front of the call
+    size_t gain_stride = idx_stride;
+    if (blend) {
+        try {
+            if (!obj_gain && prev_gain) ones.assign(n_rows * n_segs * K, 1.0f);
+            if (fade) prev.resize(4 * n_rows * K);
+        } catch (const std::bad_alloc &) {
+            return fail(OHS_ERR_ALLOC, "out of host memory for the rows' staging");
+        }
+        if (!ones.empty()) { obj_gain = ones.data(); gain_stride = shared ? 0 : n_segs; }
+    }
+    const unsigned kOne = 0x3f800000u;
     const unsigned *gain_bits = reinterpret_cast<const unsigned *>(obj_gain), *pgain_bits = reinterpret_cast<const unsigned *>(prev_gain);
-    unsigned long long fading = 0;
+    const unsigned *w_bits = reinterpret_cast<const unsigned *>(weight), *pw_bits = reinterpret_cast<const unsigned *>(prev_weight);
+    auto weight_ok = [](unsigned bits) {
+        float w;
+        std::memcpy(&w, &bits, sizeof w);
+        return w >= 0.0f && w <= 1.0f;      // (NaN fails both; -0.0 passes)
+    };
+    // one pass over every row that will be read: the indices against the table, the weights against [0, 1], the passes through old
+    // directions and the passes that load four rows
+    unsigned long long fading = 0, blended = 0;
     for (size_t r = 0; r < n_rows; ++r) {
-        const unsigned *row = dir_idx + r * idx_stride * K, *grow = gain_bits ? gain_bits + r * idx_stride * K : nullptr;
-        const unsigned *oi = prev_idx ? prev_idx + r * K : nullptr, *og = pgain_bits ? pgain_bits + r * K : (fade ? grow : nullptr);
-        if (oi)
-            for (size_t o = 0; o < K; ++o)
-                if (oi[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "prev_idx entry out of range");
-        if (fade && !oi) oi = row;      // (no boundary at the call's start)
+        const size_t ro = r * idx_stride * K;
+        const unsigned *row = dir_idx + ro, *row1 = blend ? dir_idx1 + ro : nullptr, *wrow = blend ? w_bits + ro : nullptr;
+        const unsigned *grow = gain_bits ? gain_bits + r * gain_stride * K : nullptr;
+        const unsigned *oi = prev_idx ? prev_idx + r * K : nullptr, *oj = prev_idx1 ? prev_idx1 + r * K : nullptr;
+        const unsigned *ow = pw_bits ? pw_bits + r * K : nullptr, *og = pgain_bits ? pgain_bits + r * K : nullptr;
+        for (size_t o = 0; o < K; ++o) {
+            if (oi && oi[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "prev_idx entry out of range");
+            if (oj && oj[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "prev_idx1 entry out of range");
+            if (ow && !weight_ok(ow[o])) return fail(OHS_ERR_INVALID_ARG, "prev_weight entry outside [0, 1]");
+        }
+        if (fade) {         // (no boundary at the call's start for what the caller does not name)
+            if (!oi) oi = row;
+            if (!oj) oj = row1;
+            if (!ow) ow = wrow;
+            if (!og) og = grow;
+            for (size_t o = 0; blend && o < K; ++o) {
+                prev[(0 * n_rows + r) * K + o] = oi[o];
+                prev[(1 * n_rows + r) * K + o] = oj[o];
+                prev[(2 * n_rows + r) * K + o] = ow[o];
+                prev[(3 * n_rows + r) * K + o] = og ? og[o] : kOne;
+            }
+        }
         for (size_t k = 0; k < n_segs; ++k) {
-            const unsigned *ci = row + k * K, *cg = grow ? grow + k * K : nullptr;
-            for (size_t o = 0; o < K; ++o)
+            const unsigned *ci = row + k * K, *cj = blend ? row1 + k * K : nullptr, *cw = blend ? wrow + k * K : nullptr;
+            const unsigned *cg = grow ? grow + k * K : nullptr;
+            for (size_t o = 0; o < K; ++o) {
                 if (ci[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "dir_idx entry out of range");
-            if (fade)
-                for (size_t p = 0; 2 * p < K; ++p) {
-                    bool ch = false;
-                    for (size_t o = 2 * p; o < std::min(2 * p + 2, K); ++o)
-                        ch = ch || ci[o] != oi[o] || (cg ? cg[o] : 0x3f800000u) != (og ? og[o] : 0x3f800000u);
-                    fading += ch ? 1 : 0;
+                if (blend && cj[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "dir_idx1 entry out of range");
+                if (blend && !weight_ok(cw[o])) return fail(OHS_ERR_INVALID_ARG, "weight entry outside [0, 1]");
+            }
+            const unsigned long long seg_len = std::min(seg_blocks, n_blocks - k * seg_blocks);
+            for (size_t p = 0; 2 * p < K; ++p) {
+                bool ch = false, cur_blend = false, old_blend = false;
+                for (size_t o = 2 * p; o < std::min(2 * p + 2, K); ++o) {
+                    cur_blend = cur_blend || (blend && cw[o] != 0u);
+                    if (!fade) continue;
+                    old_blend = old_blend || (blend && ow[o] != 0u);
+                    ch = ch || ci[o] != oi[o] || (cg ? cg[o] : kOne) != (og ? og[o] : kOne);
+                    // (idx1 beside a weight of +0.0 before and after is never read: no change, as in the kernel)
+                    ch = ch || (blend && (cw[o] != ow[o] || ((cw[o] | ow[o]) != 0u && cj[o] != oj[o])));
                 }
-            oi = ci; og = cg;
+                fading += ch ? 1 : 0;
+                blended += (cur_blend ? seg_len : 0) + (ch && old_blend ? 1 : 0);
+            }
+            oi = ci; oj = cj; ow = cw; og = cg;
         }
     }
-    if (shared) fading *= S;
+    if (shared) { fading *= S; blended *= S; }
     if (!layout_regions_ok(S, K, frames, d_in, in_stream_stride, in_channel_stride, d_out, out_stream_stride, out_channel_stride))
         return OHS_ERR_INVALID_ARG;
     HIP_TRY(hipSetDevice(b->device));
@@ -1072,25 +1127,42 @@ extern "C" int ohsint_batch_process_objects(ohs_batch *b, const float *d_in, flo
             HIP_TRY(hipStreamWaitEvent(st, b->chunk_done[(size_t)b->chunk_done_n - 1], 0));
             b->join_pending = false;
         }
-        // the rows' staging slot (the scheduled calls'): indices, gains, prev_idx, prev_gain, each packed and one behind the other
-        const SchedRows ri{dir_idx, idx_stride * K, n_rows, n_segs * K}, rg{obj_gain, idx_stride * K, n_rows, n_segs * K},
-            pi{prev_idx, K, n_rows, K}, pg{prev_gain, K, n_rows, K};
-        const int rcs = sched_stage(b, {&ri, &rg, &pi, &pg}, st, lease);
-        if (rcs) return rcs;
-        ConvObjectRows rows;
-        const unsigned *d = lease.slot->d;
-        rows.idx = d; d += ri.entries();
-        if (obj_gain) rows.gain = d;
-        d += rg.entries();
-        if (prev_idx) rows.prev_idx = d;
-        d += pi.entries();
-        if (prev_gain) rows.prev_gain = d;
-        rows.seg_blocks = (int)seg_blocks; rows.stream_stride = shared ? 0 : (int)(n_segs * K); rows.prev_stride = shared ? 0 : (int)K;
-        rows.fade = fade;
-        int rc = conv_launch_objects(c, b->ctx, d_in, (long long)in_stream_stride, (long long)in_channel_stride, d_out,
+        // the rows' staging slot (the scheduled calls'), each array packed and one behind the other
+        const SchedRows ri{dir_idx, idx_stride * K, n_rows, n_segs * K}, rg{obj_gain, gain_stride * K, n_rows, n_segs * K};
+        int rc;
+        if (blend) {        // indices, second indices, weights, gains -- four planes of one size, the last possibly absent --, then prev
+            const size_t plane = n_rows * n_segs * K;
+            const SchedRows rj{dir_idx1, idx_stride * K, n_rows, n_segs * K}, rw{weight, idx_stride * K, n_rows, n_segs * K},
+                pv{fade ? prev.data() : nullptr, prev.size(), 1, prev.size()};
+            const int rcs = sched_stage(b, {&ri, &rj, &rw, &rg, &pv}, st, lease);
+            if (rcs) return rcs;
+            ConvObjectBlendRows rows;
+            rows.rows = lease.slot->d; rows.plane = (int)plane; rows.has_gain = obj_gain != nullptr;
+            if (fade) rows.prev = lease.slot->d + 3 * plane + rg.entries();
+            rows.prev_plane = (int)(n_rows * K);
+            rows.seg_blocks = (int)seg_blocks; rows.stream_stride = shared ? 0 : (int)(n_segs * K); rows.prev_stride = shared ? 0 : (int)K;
+            rows.fade = fade;
+            rc = conv_launch_objects_blend(c, b->ctx, d_in, (long long)in_stream_stride, (long long)in_channel_stride, d_out,
+                                           (long long)out_stream_stride, (long long)out_channel_stride, (int)n_blocks, b->gain, st, (int)K, rows);
+        } else {            // indices, gains, prev_idx, prev_gain
+            const SchedRows pi{prev_idx, K, n_rows, K}, pg{prev_gain, K, n_rows, K};
+            const int rcs = sched_stage(b, {&ri, &rg, &pi, &pg}, st, lease);
+            if (rcs) return rcs;
+            ConvObjectRows rows;
+            const unsigned *d = lease.slot->d;
+            rows.idx = d; d += ri.entries();
+            if (obj_gain) rows.gain = d;
+            d += rg.entries();
+            if (prev_idx) rows.prev_idx = d;
+            d += pi.entries();
+            if (prev_gain) rows.prev_gain = d;
+            rows.seg_blocks = (int)seg_blocks; rows.stream_stride = shared ? 0 : (int)(n_segs * K); rows.prev_stride = shared ? 0 : (int)K;
+            rows.fade = fade;
+            rc = conv_launch_objects(c, b->ctx, d_in, (long long)in_stream_stride, (long long)in_channel_stride, d_out,
                                      (long long)out_stream_stride, (long long)out_channel_stride, (int)n_blocks, b->gain, st, (int)K, rows);
+        }
         if (rc) return rc;
-        c.last_obj_fading = fading;
+        c.last_obj_fading = fading; c.last_obj_blended = blended;
         if (b->eq_enable && eq_any_enabled(b->eq))      // EQ(gain * conv(x)): the two ear channels, in place, behind the whole call
             rc = eq_launch(b->eq, d_out, d_out, (long long)out_stream_stride, (long long)out_channel_stride, (long long)frames, st);
         return rc;
@@ -1098,6 +1170,42 @@ extern "C" int ohsint_batch_process_objects(ohs_batch *b, const float *d_in, flo
     const int rc = body();
     if (rc == OHS_OK || rc == OHS_ERR_INVALID_ARG) return rc;
     return batch_mark_failed(b, rc);
+}
+
+extern "C" int ohsint_batch_process_objects(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
+                                            size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride,
+                                            size_t n_objects, size_t seg_blocks, const unsigned *dir_idx, const float *obj_gain,
+                                            size_t idx_stride, const unsigned *prev_idx, const float *prev_gain, int switch_mode,
+                                            void *hip_stream)
+{
+    return batch_process_objects_any(b, d_in, d_out, n_blocks, in_stream_stride, in_channel_stride, out_stream_stride, out_channel_stride,
+                                     n_objects, seg_blocks, dir_idx, obj_gain, idx_stride, prev_idx, prev_gain, switch_mode, hip_stream,
+                                     nullptr, nullptr, nullptr, nullptr);
+}
+
+// ---- blended object scenes: two directions and a weight per object (libohs_scene2.so; no entry of ohs_hip.h or ohs_scene.h) ------
+// dir_idx1 and weight both NULL: ohsint_batch_process_objects
+extern "C" int ohsint_batch_process_objects_blend(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
+                                                  size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride,
+                                                  size_t n_objects, size_t seg_blocks, const unsigned *dir_idx, const float *obj_gain,
+                                                  size_t idx_stride, const unsigned *prev_idx, const float *prev_gain, int switch_mode,
+                                                  void *hip_stream, const unsigned *dir_idx1, const float *weight,
+                                                  const unsigned *prev_idx1, const float *prev_weight)
+{
+    return batch_process_objects_any(b, d_in, d_out, n_blocks, in_stream_stride, in_channel_stride, out_stream_stride, out_channel_stride,
+                                     n_objects, seg_blocks, dir_idx, obj_gain, idx_stride, prev_idx, prev_gain, switch_mode, hip_stream,
+                                     dir_idx1, weight, prev_idx1, prev_weight);
+}
+
+extern "C" int ohsint_batch_last_objects_blend_launch(const ohs_batch *b, int *n_pairs, int *ranges_per_stream,
+                                                      unsigned long long *fading_passes, unsigned long long *blended_passes)
+{
+    if (!b || !n_pairs || !ranges_per_stream || !fading_passes || !blended_passes) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    *n_pairs = b->conv.last_obj_pairs;
+    *ranges_per_stream = b->conv.last_obj_ranges;
+    *fading_passes = b->conv.last_obj_fading;
+    *blended_passes = b->conv.last_obj_blended;
+    return OHS_OK;
 }
 
 int ohs_batch_process_deferred(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,

@@ -228,6 +228,7 @@ struct ConvState {
     float2 *d_obj_ah = nullptr;     // [obj_n + 1][1024]
     int last_obj_pairs = 0, last_obj_ranges = 0;    // the most recent scene launch (ohs_scene_last_launch)
     unsigned long long last_obj_fading = 0;         // ... and its passes through old directions, summed over the streams
+    unsigned long long last_obj_blended = 0;        // ... and its passes that load four rows (0 behind a plain scene call)
     // ohs_*_set_speakers: what it last loaded into each path (a set_ir from anywhere else forgets it), so that a
     // change of the speaker angles re-loads only the paths whose impulse response really changed
     std::vector<float> spk_ir[4];
@@ -343,6 +344,17 @@ struct ConvObjectRows {
 // n_blocks of every stream's n_objects channels -> two ears, times gain: one launch of k_conv_p1_objects.  Out of place, asynchronous on st
 int conv_launch_objects(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out, long long out_ss,
                         long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, const ConvObjectRows &rows);
+// the blended scene call's rows (device memory; validated by the caller), as ConvObjectsBlendArgs reads them: four planes -- first
+// direction, second direction, weight, gain (if has_gain) -- `plane` entries apart, and in front of the call four planes of
+// [row][n_objects], `prev_plane` apart (all four staged whenever fade is set)
+struct ConvObjectBlendRows {
+    const unsigned *rows = nullptr, *prev = nullptr;
+    int plane = 0, prev_plane = 0, seg_blocks = 1, stream_stride = 0, prev_stride = 0;
+    bool has_gain = false, fade = false;
+};
+// conv_launch_objects with two directions and a weight per object: one launch of k_conv_p1_objects_blend
+int conv_launch_objects_blend(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out, long long out_ss,
+                              long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, const ConvObjectBlendRows &rows);
 // the handle's four responses become set `set` of the table, overlaps and history untouched (asynchronous on st)
 int conv_adopt_schedule_set(ConvState &c, size_t set, hipStream_t st);
 // the per-path overlaps from the lazy state with the CURRENT spectra, the lazy state kept valid beside them (tails_both)

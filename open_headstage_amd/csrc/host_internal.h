@@ -21,6 +21,16 @@ extern "C" int ohsint_batch_process_objects(ohs_batch *b, const float *d_in, flo
                                             void *hip_stream);
 extern "C" int ohsint_batch_last_objects_launch(const ohs_batch *b, int *n_pairs, int *ranges_per_stream,
                                                 unsigned long long *fading_passes);
+// api_batch.hip: what libohs_scene2.so adds (api_scene2.hip, include/ohs_scene2.h) -- the scene call with a second direction and a
+// weight per object (dir_idx1 and weight both NULL: ohsint_batch_process_objects), and the launch record with its blended passes
+extern "C" int ohsint_batch_process_objects_blend(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
+                                                  size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride,
+                                                  size_t n_objects, size_t seg_blocks, const unsigned *dir_idx, const float *obj_gain,
+                                                  size_t idx_stride, const unsigned *prev_idx, const float *prev_gain, int switch_mode,
+                                                  void *hip_stream, const unsigned *dir_idx1, const float *weight,
+                                                  const unsigned *prev_idx1, const float *prev_weight);
+extern "C" int ohsint_batch_last_objects_blend_launch(const ohs_batch *b, int *n_pairs, int *ranges_per_stream,
+                                                      unsigned long long *fading_passes, unsigned long long *blended_passes);
 
 namespace ohs_host {
 

@@ -327,6 +327,29 @@ struct ConvObjectsArgs {
 hipError_t launch_conv_p1_objects(const ConvP1Args &a, const ConvObjectsArgs &l, hipStream_t st);
 // H[dir][2][1024] (launch_ir_spectrum: left ear, right ear) -> dst[dir][1024] = 0.5 (Hl.x - Hr.y, Hl.y + Hr.x) in the block loop's layout
 hipError_t launch_object_tables(const float2 *H, int n_dirs, float2 *dst, hipStream_t st);
+// K moving sources per stream, each between TWO directions (ohs_scene2_process_blended; library-internal): k_conv_p1_objects_blend
+// (conv_objects_blend_kernels.hip), the body of k_conv_p1_objects on the same direction table, with a second index and a weight per
+// object, stream and segment: the object's row is (1 - w) ahalf[idx] + w ahalf[idx1].  idx1 and the weight have the shape and the
+// stride rule of idx and the gain, and stand in one staging buffer with them.  A struct of its own, so that ConvObjectsArgs and its kernel stay what they are.
+struct ConvObjectsBlendArgs {
+    const float2 *ahalf;        // ConvObjectsArgs's table, row n_dirs all zero
+    unsigned zero_dir;          // n_dirs
+    int n_pairs;                // ceil(n_objects / 2)
+    int n_objects;
+    const unsigned *rows;       // four planes of [row][segment][n_objects] 32-bit entries, `plane` entries apart: first direction, second
+                                // direction, weight (f32 bits in [0, 1]: the second direction's share), gain (f32 bits)
+    int plane;
+    int has_gain;               // 0: the gain plane is not there, 1.0 everywhere
+    int stream;                 // stream s reads its rows at rows + s * stream (0: one row for all streams)
+    int seg;                    // blocks per segment
+    const unsigned *prev;       // four planes of [row][n_objects] in front of the call's first block, `prev_plane` apart; under CROSSFADE the
+                                // host always stages them (the first segment's own entries where the caller names none); else nullptr
+    int prev_plane;
+    int prev_stream;            // stream s reads prev + s * prev_stream (0: one row for all streams)
+    int fade;                   // 1: CROSSFADE; 0: RING_OUT, no pair fades (prev is not read)
+};
+// a.chunks as for launch_conv_p1_layout; the host has checked every index against the table and every weight against [0, 1]
+hipError_t launch_conv_p1_objects_blend(const ConvP1Args &a, const ConvObjectsBlendArgs &l, hipStream_t st);
 // cd[set][2][1024] (launch_build_cd per set) -> dst[set][1024] in the block loop's layout, times `scale`
 hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st, float scale = 1.0f);
 // The layout kernels' tables are built with this scale: launch_build_cd's 1/N taken out again, which launch_conv_p1_layout and

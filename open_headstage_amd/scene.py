@@ -63,14 +63,22 @@ def scene_lib() -> C.CDLL:
 
 
 class SceneError(RuntimeError):
-    def __init__(self, status: int, detail: str):
+    def __init__(self, status: int, detail: str, text: str | None = None):
         self.status = status
-        super().__init__(f"{scene_lib().ohs_scene_status_string(status).decode()} ({status}): {detail}")
+        text = scene_lib().ohs_scene_status_string(status).decode() if text is None else text
+        super().__init__(f"{text} ({status}): {detail}")
+
+
+def _check_status(L: C.CDLL, prefix: str, status: int) -> None:
+    """the one place a status of either scene library becomes a SceneError: that library's last error and status string"""
+    if status != OHS_OK:
+        raise SceneError(status, getattr(L, prefix + "last_error")().decode(errors="replace"),
+                         getattr(L, prefix + "status_string")(status).decode())
 
 
 def scene_check(status: int) -> None:
-    if status != OHS_OK:
-        raise SceneError(status, scene_lib().ohs_scene_last_error().decode(errors="replace"))
+    """Public: for callers that use scene_lib()'s entries directly.  The classes check through their own library (_check)."""
+    _check_status(scene_lib(), "ohs_scene_", status)
 
 
 # -- host helpers: where the objects are, seen from the head -----------------------------------------------------------
@@ -103,19 +111,22 @@ def rotate_sources(az, el, yaw, pitch=0.0, roll=0.0):
     return np.where(flat, az_y, az2).astype(np.float32), np.where(flat, el, el2).astype(np.float32)
 
 
+def _xyz(a, e, r):
+    """(azimuth, elevation in degrees, radius), f32 -> Cartesian f64 [..., 3]"""
+    a, e = np.radians(np.asarray(a, np.float32).astype(np.float64)), np.radians(np.asarray(e, np.float32).astype(np.float64))
+    r = np.asarray(r, np.float32).astype(np.float64)
+    return np.stack([r * np.cos(e) * np.cos(a), r * np.cos(e) * np.sin(a), r * np.sin(e) + 0.0 * a], -1)
+
+
 def nearest_directions(positions, az, el, radius_m: float = 1.0) -> np.ndarray:
     """The measurement nearest to each query in Cartesian space -- what ohs_sofa_nearest answers for a file opened without
     interpolation (the first of equally near ones).  positions: [M][3] (azimuth, elevation, radius) as MySofa.position gives
     them, SOFA degrees (azimuth positive to the LEFT; a plugin azimuth is its negative); az, el: queries in the same degrees,
     any shape -> uint32 indices of that shape."""
-    def xyz(a, e, r):
-        a, e = np.radians(np.asarray(a, np.float32).astype(np.float64)), np.radians(np.asarray(e, np.float32).astype(np.float64))
-        r = np.asarray(r, np.float32).astype(np.float64)
-        return np.stack([r * np.cos(e) * np.cos(a), r * np.cos(e) * np.sin(a), r * np.sin(e) + 0.0 * a], -1)
     pos = np.asarray(positions, np.float32).reshape(-1, 3)
-    p = xyz(pos[:, 0], pos[:, 1], pos[:, 2]).astype(np.float32).astype(np.float64)      # (the handle keeps f32 coordinates)
+    p = _xyz(pos[:, 0], pos[:, 1], pos[:, 2]).astype(np.float32).astype(np.float64)     # (the handle keeps f32 coordinates)
     azq, elq = np.broadcast_arrays(np.asarray(az, np.float32), np.asarray(el, np.float32))
-    q = xyz(azq.ravel(), elq.ravel(), np.float32(radius_m))
+    q = _xyz(azq.ravel(), elq.ravel(), np.float32(radius_m))
     out = np.empty(q.shape[0], np.uint32)
     for i0 in range(0, q.shape[0], 4096):       # (slices: M x queries distances at a time)
         d = p[None, :, :] - q[i0:i0 + 4096, None, :]
@@ -135,13 +146,25 @@ def _object_rows(a, n_streams, n_segs, K, what, dtype):
 
 
 class SceneProcessor:
+    # the library an instance talks to and the prefix of its entries: a subclass on another library with the same surface under
+    # another prefix (scene2.BlendSceneProcessor) overrides the two
+    _prefix = "ohs_scene_"
+    _loader = staticmethod(scene_lib)
+
+    def _fn(self, name: str):
+        return getattr(self._loader(), self._prefix + name)
+
+    def _check(self, status: int) -> None:
+        _check_status(self._loader(), self._prefix, status)
+
     def __init__(self, n_streams: int, num_bands: int = 10, device: int = 0):
         self.n_streams, self.num_bands, self.device = int(n_streams), int(num_bands), int(device)
         self.n_directions = 0
         self._h = None
         h = C.c_void_p()
-        scene_check(scene_lib().ohs_scene_create(self.device, self.n_streams, self.num_bands, C.byref(h)))
+        self._check(self._fn("create")(self.device, self.n_streams, self.num_bands, C.byref(h)))
         self._h = h
+        self._destroy = self._fn("destroy")
 
     # -- the direction table ------------------------------------------------------------------
     def set_directions(self, irs) -> None:
@@ -149,13 +172,13 @@ class SceneProcessor:
         earlier table and zeroes the overlap; an empty array frees it (ohs_scene_set_direction_irs)."""
         a = np.ascontiguousarray(irs, dtype=np.float32)
         if a.size == 0:
-            scene_check(scene_lib().ohs_scene_set_direction_irs(self._h, 0, None, 0))
+            self._check(self._fn("set_direction_irs")(self._h, 0, None, 0))
             self.n_directions = 0
             return
         if a.ndim != 3 or a.shape[1] != 2:
             raise ValueError(f"expected irs [n_dirs][2][len], got {a.shape}")
         self.n_directions = 0
-        scene_check(scene_lib().ohs_scene_set_direction_irs(self._h, a.shape[0], a.ctypes.data_as(fp), a.shape[2]))
+        self._check(self._fn("set_direction_irs")(self._h, a.shape[0], a.ctypes.data_as(fp), a.shape[2]))
         self.n_directions = int(a.shape[0])
 
     def set_directions_from_sofa(self, sofa, fs: float = 0.0) -> np.ndarray:
@@ -201,7 +224,7 @@ class SceneProcessor:
                 raise ValueError(f"{what}: expected {n_prev} entries, got {v.size}")
             return v
         pi, pg = prev(prev_idx, np.uint32, "prev_idx"), prev(prev_gains, np.float32, "prev_gains")
-        scene_check(scene_lib().ohs_scene_process(
+        self._check(self._fn("process")(
             self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(in_stream_stride), int(in_channel_stride),
             int(out_stream_stride), int(out_channel_stride), K, int(seg_blocks), a.ctypes.data_as(u32p),
             None if g is None else g.ctypes.data_as(fp), stride, None if pi is None else pi.ctypes.data_as(u32p),
@@ -223,33 +246,33 @@ class SceneProcessor:
 
     # -- the chain behind the renderer --------------------------------------------------------------
     def set_gain(self, gain: float) -> None:
-        scene_check(scene_lib().ohs_scene_set_gain(self._h, float(gain)))
+        self._check(self._fn("set_gain")(self._h, float(gain)))
 
     def set_band_coeffs(self, band_idx: int, coeffs, enabled: bool) -> None:
         c = np.ascontiguousarray(coeffs, dtype=np.float32).ravel()
         if c.size != 5:
             raise ValueError("coeffs must be [b0, b1, b2, a1, a2]")
-        scene_check(scene_lib().ohs_scene_set_eq_band_coeffs(self._h, int(band_idx), c.ctypes.data_as(fp), int(bool(enabled))))
+        self._check(self._fn("set_eq_band_coeffs")(self._h, int(band_idx), c.ctypes.data_as(fp), int(bool(enabled))))
 
     def set_eq_enabled(self, eq_enable: bool) -> None:
-        scene_check(scene_lib().ohs_scene_set_eq_enabled(self._h, int(bool(eq_enable))))
+        self._check(self._fn("set_eq_enabled")(self._h, int(bool(eq_enable))))
 
     def set_flush_denormals(self, mode: int) -> None:
-        scene_check(scene_lib().ohs_scene_set_flush_denormals(self._h, int(mode)))
+        self._check(self._fn("set_flush_denormals")(self._h, int(mode)))
 
     def reset(self) -> None:
-        scene_check(scene_lib().ohs_scene_reset(self._h))
+        self._check(self._fn("reset")(self._h))
 
     def sync(self, hip_stream: int = 0) -> None:
-        scene_check(scene_lib().ohs_scene_sync(self._h, C.c_void_p(hip_stream) if hip_stream else None))
+        self._check(self._fn("sync")(self._h, C.c_void_p(hip_stream) if hip_stream else None))
 
     def last_launch(self):
         """(pairs of objects, block ranges per stream, passes through old directions) of the most recent launch; zeros: none yet"""
         p, r, f = C.c_int(), C.c_int(), C.c_ulonglong()
-        scene_check(scene_lib().ohs_scene_last_launch(self._h, C.byref(p), C.byref(r), C.byref(f)))
+        self._check(self._fn("last_launch")(self._h, C.byref(p), C.byref(r), C.byref(f)))
         return int(p.value), int(r.value), int(f.value)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.ohs_scene_destroy(h)
+        if h and getattr(self, "_destroy", None) is not None:
+            self._destroy(h)
