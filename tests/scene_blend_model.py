@@ -15,7 +15,7 @@ one time-domain convolution each.  as_2k_scene is the identity conv(u h0 + w h1,
 one-direction model and library: 2 K objects on duplicated channels."""
 import numpy as np
 
-from tests.scene_model import BLOCK, RAMP_F, RAMP_G, _prev, _rows, _weighted
+from tests.scene_model import BLOCK, RAMP_F, RAMP_G, WIDE_MUTANTS, _prev, _rows, _weighted, chan  # noqa: F401
 
 MUTANTS = ("swap_w", "partner_weight", "weight_no_fade", "old_half_cur_weight", "prev_weight_ignored")
 
@@ -54,6 +54,8 @@ def blend_plan(S, K, n_blocks, idx, idx1, weights, seg_blocks, gains, prev_idx, 
                 ch = (ci != oi) | ((cj != oj) & ((_bits(cw) | _bits(ow)) != 0)) | (_bits(cg) != _bits(og))
                 if mutant != "weight_no_fade":
                     ch = ch | (_bits(cw) != _bits(ow))
+                if mutant == "mask32":
+                    ch[32:] = False
             passes = []
             for c in range(K):
                 partner = c ^ 1
@@ -61,10 +63,14 @@ def blend_plan(S, K, n_blocks, idx, idx1, weights, seg_blocks, gains, prev_idx, 
                 e = partner if mutant == "partner_weight" and partner < K else c     # the entry the WEIGHT is read from
                 if fading:
                     w_old = cw[e] if mutant == "old_half_cur_weight" else ow[e]
-                    passes.append((c, int(oi[c]), int(oj[c]), np.float32(w_old), np.float32(og[c]), RAMP_G, True))
+                    if not (mutant == "pair31_dropped" and c // 2 == 31):
+                        passes.append((c, int(oi[c]), int(oj[c]), np.float32(w_old), np.float32(og[c]), RAMP_G, True))
                     passes.append((c, int(ci[c]), int(cj[c]), np.float32(cw[e]), np.float32(cg[c]), RAMP_F, False))
                 else:
                     passes.append((c, int(ci[c]), int(cj[c]), np.float32(cw[e]), np.float32(cg[c]), None, False))
+            if mutant == "odd_partner_row0" and K % 2 == 1:     # "object" K (scene_model.chan) through row 0, w = +0.0, gain 1
+                z, one = np.float32(0), np.float32(1)
+                passes += [(K, 0, 0, z, one, RAMP_G, True), (K, 0, 0, z, one, RAMP_F, False)] if ch[K - 1] else [(K, 0, 0, z, one, None, False)]
             row.append(passes)
         plan.append(row)
     return plan
@@ -111,7 +117,7 @@ def model_blend_f64(x, dirs, idx, idx1, weights, seg_blocks, gains=None, prev_id
             sl = slice(t * BLOCK, (t + 1) * BLOCK)
             u = {}
             for c, d0, d1, w, g, ramp, _ in plan[s][t]:
-                v = _weighted(x[s, c, sl], g, ramp).astype(np.float64)
+                v = _weighted(chan(x, s, c)[sl], g, ramp).astype(np.float64)
                 s0, s1 = _shares(w, mutant)
                 u[d0] = u.get(d0, 0.0) + s0 * v
                 u[d1] = u.get(d1, 0.0) + s1 * v
@@ -223,3 +229,16 @@ def make_blend_scene(S, K, n_blocks, seg_blocks, n_dirs=7, seed=0, shared=False)
         idx1, w, prev_idx1, prev_w = idx1[0], w[0], prev_idx1[0], prev_w[0]
     return dict(idx=idx, idx1=idx1, weights=w, gains=gains, prev_idx=prev_idx, prev_idx1=prev_idx1, prev_weights=prev_w,
                 prev_gains=prev_gains)
+
+
+def make_wide_blend_scene(S, K, n_blocks, seg_blocks, changed, loud=None, n_dirs=7, seed=0):
+    """tests.scene_model.make_wide_scene with a second direction and a weight per object: segment k changes exactly the objects
+    changed[k] and holds all others -> dict(idx, idx1, weights, gains, prev_idx, prev_idx1, prev_weights, prev_gains), rows per stream.
+    A changed object in turn moves, changes its gain, changes ONLY its weight, changes ONLY its second direction (_wide_rows)."""
+    from tests.scene_model import _wide_rows
+    n_segs = -(-n_blocks // min(seg_blocks, n_blocks))
+    r = _wide_rows(S, K, n_segs, changed, loud, n_dirs, seed, True)
+    out = {}
+    for k, v in r.items():
+        out[k], out["prev_" + k] = np.ascontiguousarray(v[:, 1:]), np.ascontiguousarray(v[:, 0])
+    return out

@@ -121,6 +121,27 @@ def test_oracle_c_through_the_range(oracle, noise, shape, mode):
     print(f"flush-modes oracle C, {shape}: subnormal samples per stream of the IEEE run: {counts}")
 
 
+# ---- the object scenes' case C is not vacuous ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kernel", ["plain", "blend"])
+def test_scene_case_c_leaves_every_stream_subnormal_samples(kernel):
+    """tests/test_gpu_scene_modes.py's falling input on its scene and call list: the f64 model of the two calls, rounded to f32, holds
+    at least NEED subnormal samples in every stream, and every stream's input passes 2^-126 inside the first call"""
+    from tests import test_gpu_scene_modes as gm
+    x = fm.falling_input(gm.modes_noise(), gm.CROSSING)
+    assert x.shape == (gm.S, gm.K, gm.TOTAL * BLOCK)
+    for s in range(gm.S):
+        peak = np.abs(x[s]).reshape(gm.K, gm.TOTAL, BLOCK).max(axis=(0, 2))
+        below = np.flatnonzero(peak < fm.TINY)
+        assert peak[0] >= fm.TINY and below.size and 0 < below[0] < gm.CALLS[0], (s, below)
+    ref = gm.model_calls(kernel, x, gm.C_GAIN_POW).astype(np.float32)
+    counts = fm.subnormal_mask(ref).sum(axis=(1, 2))
+    print(f"scene case C, {kernel} kernel: subnormal samples per stream of the f64 model rounded to f32: {counts.tolist()}")
+    assert (counts >= fm.NEED).all(), counts
+    normal = (np.abs(ref) >= fm.TINY).sum(axis=(1, 2))
+    print(f"scene case C, {kernel} kernel: samples per stream in the normal range: {normal.tolist()}")
+    assert (normal >= fm.NEED).all(), normal            # (the output starts in the normal range and falls through it)
+
+
 # ---- the checkers can fail -----------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def clean(oracle, noise):

@@ -6,6 +6,9 @@
   wrong object, `old` taken from two segments back -- are far above the project's FFT bar (1e-6 relative RMS per stream, DESIGN
   section 2), per stream and in the worst 512-frame block; fading EVERY pair when one changes is the same mathematics and stays below
   it, which is why that case is compared in bits only where the header promises them;
+* on the wide scenes of tests/test_gpu_scene_wide.py (K = 33, 63, 64) three more -- a change set cut to 32 bits, an old half that
+  stops in front of pair 31, an odd K's missing partner rendered instead of silent -- are more than 1e3 times the bar away in some
+  block of every scene, and the model still equals the direct evaluation at K = 64;
 * the header's names, the library's dynamic symbols and SCENE_PROTOTYPES are one list, every entry refuses NULL, and libohs_hip.so
   still exports exactly ohs_hip.h's 119;
 * k_conv_p1_objects was built without scratch at three waves per SIMD, the layout kernels have the figures they had;
@@ -92,6 +95,42 @@ def test_mutants_against_the_bar_on_the_gpu_tests_inputs():
     for m in ("gain_no_fade", "wrong_partner", "old_two_back"):
         assert seen[m] > 1e3 * BAR, (m, seen[m])       # some case of the GPU file shows the mutant, far above the bar
     assert 0.0 < seen["fade_all"] <= BAR, seen
+
+
+def wide_mutant_applies(m, K):
+    """mask32 needs an object past 31 (every wide K), pair31_dropped a pair 31 (K >= 63), odd_partner_row0 an odd K"""
+    return {"mask32": K > 32, "pair31_dropped": K >= 63, "odd_partner_row0": K % 2 == 1}[m]
+
+
+def test_wide_mutants_are_far_from_every_wide_scene():
+    """every scene of tests/test_gpu_scene_wide.py, few loud and all loud, against each wide mutant that exists at its K: more than
+    1e3 BAR away in at least one 512-frame block"""
+    from tests.test_gpu_scene_wide import WIDE_CASES, wide_case
+    for K, half in WIDE_CASES:
+        assert [m for m in sm.WIDE_MUTANTS if wide_mutant_applies(m, K)], K
+        for all_loud in (False, True):
+            x, dirs, seg, (idx, gains, pi, pg) = wide_case(K, half, all_loud, False)
+            ref = sm.model_scene_f64(x, dirs, idx, seg, gains, pi, pg, True, GAIN)
+            for m in sm.WIDE_MUTANTS:
+                y = sm.model_scene_f64(x, dirs, idx, seg, gains, pi, pg, True, GAIN, mutant=m)
+                eb = rel_rms_per_block(y, ref)
+                print(f"K = {K}, patterns {3 * half} .. {3 * half + 2}, {'all' if all_loud else 'few'} loud: mutant {m}: worst block {eb.max():.3e}")
+                if wide_mutant_applies(m, K):
+                    assert eb.max() > 1e3 * BAR, (K, half, all_loud, m, eb.max())
+                else:
+                    assert eb.max() == 0.0, (K, half, all_loud, m, eb.max())
+
+
+def test_block_wise_model_is_the_direct_evaluation_at_64_objects():
+    S, K, blocks, seg = 1, 64, 6, 2
+    dirs = make_layout(N_DIRS, 8)
+    x = make_input(S, K, blocks, seed=7300)
+    idx, gains, pi, pg = sm.make_wide_scene(S, K, blocks, seg, sm.wide_patterns(K)[3:6], None, N_DIRS, seed=64)
+    a = sm.model_scene_f64(x, dirs, idx, seg, gains, pi, pg, True, GAIN)
+    b = sm.direct_scene_f64(x, dirs, idx, seg, gains, pi, pg, True, GAIN)
+    err = rel_rms_per_stream(a, b)
+    print(f"K = 64: block-wise against direct, relative RMS per stream, worst {err.max():.3e}")
+    assert (err <= 1e-13).all(), err
 
 
 # ---- 3. the surface -------------------------------------------------------------------------------------------------------------

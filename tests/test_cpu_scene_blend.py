@@ -5,7 +5,9 @@
 * the model agrees with the 2 K identity -- conv(u h0 + w h1, x) = conv(h0, u x) + conv(h1, w x) -- evaluated by the EXISTING
   tests/scene_model.py on 2 K objects: the two differ in which pairs fade and in f32 products, and stay below the project's FFT bar
   (1e-6 relative RMS, DESIGN section 2);
-* five wrong readings of the rule are each above that bar on the GPU tests' own inputs;
+* five wrong readings of the rule are each above that bar on the GPU tests' own inputs; on the wide scenes of
+  tests/test_gpu_scene_wide.py the three wide mutants of tests/scene_model.py are more than 1e3 times the bar away in some block of
+  every scene, and the model still equals the direct evaluation at K = 64;
 * the header's names, libohs_scene2.so's dynamic symbols and SCENE2_PROTOTYPES are one list of fourteen, every entry refuses NULL;
   libohs_scene.so still exports thirteen names and libohs_hip.so 119;
 * k_conv_p1_objects_blend was built without scratch, and every kernel that existed has the figures it had;
@@ -145,6 +147,56 @@ def test_mutants_against_the_bar_on_the_gpu_tests_inputs():
             seen[m] = max(seen[m], float(e.max()))
     for m in bm.MUTANTS:
         assert seen[m] > 1e3 * BAR, (m, seen[m])        # some case of the GPU file shows the mutant, far above the bar
+
+
+def test_wide_mutants_are_far_from_every_wide_scene():
+    """every scene of tests/test_gpu_scene_wide.py, few loud and all loud, against each wide mutant that exists at its K: more than
+    1e3 BAR away in at least one 512-frame block"""
+    from tests.test_cpu_scene import wide_mutant_applies
+    from tests.test_gpu_scene_wide import WIDE_CASES, kinds_of_change, wide_case
+    for K, half in WIDE_CASES:
+        for all_loud in (False, True):
+            x, dirs, seg, sc = wide_case(K, half, all_loud, True)
+            print(f"K = {K}, patterns {3 * half} .. {3 * half + 2}: changes in w alone, in idx1 alone: {kinds_of_change(sc)}")
+            ref = bm.model_blend_f64(x, dirs, *_args(sc), seg, gain=GAIN, **_kw(sc))
+            for m in bm.WIDE_MUTANTS:
+                y = bm.model_blend_f64(x, dirs, *_args(sc), seg, gain=GAIN, mutant=m, **_kw(sc))
+                eb = rel_rms_per_block(y, ref)
+                print(f"K = {K}, patterns {3 * half} .. {3 * half + 2}, {'all' if all_loud else 'few'} loud: mutant {m}: worst block {eb.max():.3e}")
+                if wide_mutant_applies(m, K):
+                    assert eb.max() > 1e3 * BAR, (K, half, all_loud, m, eb.max())
+                else:
+                    assert eb.max() == 0.0, (K, half, all_loud, m, eb.max())
+
+
+def test_block_wise_model_is_the_direct_evaluation_at_64_objects():
+    S, K, blocks, seg = 1, 64, 6, 2
+    dirs = make_layout(N_DIRS, 8)
+    x = make_input(S, K, blocks, seed=7800)
+    sc = bm.make_wide_blend_scene(S, K, blocks, seg, sm.wide_patterns(K)[3:6], None, N_DIRS, seed=64)
+    a = bm.model_blend_f64(x, dirs, *_args(sc), seg, gain=GAIN, **_kw(sc))
+    b = bm.direct_blend_f64(x, dirs, *_args(sc), seg, gain=GAIN, **_kw(sc))
+    err = rel_rms_per_stream(a, b)
+    print(f"K = 64: signals blended against responses blended, relative RMS per stream, worst {err.max():.3e}")
+    assert (err <= 1e-13).all(), err
+
+
+def test_the_fuzz_sequences_cover_what_they_name():
+    """over the four seeds: both entries, both switch modes, both row forms, gains and every prev_* given and None, every K, every
+    seg_blocks, every setter, 64 objects in a blended CROSSFADE call (tests/test_gpu_scene_fuzz.py's generator alone)"""
+    from tests.test_gpu_scene_fuzz import KS, SEEDS, SEGS, draw_sequence
+    calls = [op[1] for seed in SEEDS for op in draw_sequence(seed) if op[0] == "call"]
+    setters = {op[0] for seed in SEEDS for op in draw_sequence(seed) if op[0] != "call"}
+    assert setters == {"set_gain", "reset", "set_directions"}, setters
+    assert {c["K"] for c in calls} == set(KS) and {c["seg"] for c in calls} == set(SEGS)
+    for flag in ("blended", "fade", "shared"):
+        assert {c[flag] for c in calls} == {True, False}, flag
+    for name in ("gains", "prev_idx", "prev_gains"):
+        assert {c[name] is None for c in calls} == {True, False}, name
+    for name in ("prev_idx1", "prev_weights"):
+        assert {c[name] is None for c in calls if c["blended"]} == {True, False}, name
+    assert any(c["K"] == 64 and c["blended"] and c["fade"] for c in calls)
+    assert any(c["gains"] is None and c["prev_gains"] is not None and c["shared"] for c in calls)
 
 
 # ---- 4. the surface ------------------------------------------------------------------------------------------------------------

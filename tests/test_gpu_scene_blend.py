@@ -139,6 +139,33 @@ def test_unit_weights_are_the_plain_call_on_idx1():
     diff = int((y.view(np.uint32) != want.view(np.uint32)).sum())
     print(f"w = 1 everywhere against the plain call on idx1: {diff} of {y.size} samples differ in bits")
     _within_bar(y, want.astype(np.float64), "w = 1 against the plain call on idx1")
+    # 0 A[d0] + 1 A[d1] is A[d1], each operation rounded by itself: equal as numbers (a zero's sign may differ)
+    ne = np.argwhere(~(y == want))
+    assert ne.size == 0, f"w = 1: {len(ne)} samples differ from the plain call on idx1 as numbers, first (stream, ear, frame) {ne[0].tolist()}: " \
+                         f"{y[tuple(ne[0])]!r} against {want[tuple(ne[0])]!r}"
+
+
+def test_negative_zero_weights_are_the_plain_call_on_idx():
+    """w = -0.0 everywhere is not +0.0: every pass loads four rows, and 1 A[d0] + (-0) A[d1] is A[d0] -- the four-row pass against the
+    two-row pass, operation for operation, equal as numbers.  idx1 is held per object, so the blended call fades where the plain one does."""
+    case = BLEND_CASES[2]
+    x, dirs, seg, sc = blend_case(*case)
+    K = case[0]
+    held = np.broadcast_to(sc["idx1"][:, :1], sc["idx1"].shape).copy()
+    neg = np.full_like(sc["weights"], -0.0)
+    assert np.signbit(neg).all() and (held != sc["idx"]).any()
+    h, ref = _blend(dirs), _plain(dirs)
+    y = _run(h, x, seg, sc, idx1=held, weights=neg, prev_idx1=None, prev_weights=None)
+    want = _run_plain(ref, x, sc["idx"], seg, sc["gains"], sc["prev_idx"], sc["prev_gains"])
+    pairs, _, fading, blended = h.last_launch()
+    # every pass is a blended one: per stream and block one per pair, and one more per pair with an old half
+    assert (pairs, fading) == (ref.last_launch()[0], ref.last_launch()[2]) and fading > 0, (h.last_launch(), ref.last_launch())
+    assert blended == S * case[4] * ((K + 1) // 2) + fading, h.last_launch()
+    diff = int((y.view(np.uint32) != want.view(np.uint32)).sum())
+    print(f"w = -0.0 everywhere against the plain call on idx: {diff} of {y.size} samples differ in bits")
+    ne = np.argwhere(~(y == want))
+    assert ne.size == 0, f"w = -0.0: {len(ne)} samples differ from the plain call on idx as numbers, first (stream, ear, frame) {ne[0].tolist()}: " \
+                         f"{y[tuple(ne[0])]!r} against {want[tuple(ne[0])]!r}"
 
 
 # ---- c. trajectories against the f64 model -------------------------------------------------------------------------------------
