@@ -442,7 +442,34 @@ int  ohs_batch_conv_plan_counts(ohs_batch *b, uint64_t counts[8] /* OHS_CONV_KER
 int  ohs_batch_reset(ohs_batch *b);
 /* Process n_blocks * 512 frames of every stream: [EQ] -> convolution -> gain.
  * Asynchronous on `hip_stream` (a hipStream_t, NULL = default stream).
- * d_in may equal d_out. Strides are in floats. */
+ * d_in may equal d_out. Strides are in floats.
+ *
+ * THE STREAM CONTRACT of every entry point that takes a `hip_stream` -- the seven processing calls of a batch handle,
+ * ohs_batch_process_deferred / ohs_batch_join / ohs_batch_sync --, of ohs_node_batch_process on the stream ohs_node_batch_stream
+ * names, and of the processing and sync calls of ohs_scene.h and ohs_scene2.h; tests/test_gpu_stream_order.py holds each of them
+ * to it on a stream that is busy while the call is made:
+ *   Input.  d_in may be PRODUCED by work queued earlier on hip_stream (a kernel, a copy): every read of it is ordered behind
+ *     that work, on whichever internal stream it happens.  Nothing of d_in or d_out is touched on the host.
+ *   Output and reuse.  Work queued on hip_stream behind the call sees d_out complete (behind ohs_batch_join for a deferred call)
+ *     and may overwrite d_in and d_out at once: "the buffers are the caller's again on the stream".
+ *   Host rows.  Every host array of a call (table_idx, gain, ir_idx, set_idx, prev_idx; the rows of the scene calls) has been
+ *     copied when the call returns and is the caller's again ON RETURN, whatever is still queued.
+ *   By-value settings.  A call leaves with the gain, shared EQ bands, EQ switch, flush-denormals mode and plan in force when it
+ *     was MADE; their setters touch nothing on the device and may be called while earlier calls are still queued.
+ *   Device tables.  ohs_batch_set_ir, ohs_batch_reset, ohs_batch_set_schedule_tables, ohs_batch_set_schedule_irs,
+ *     ohs_batch_set_layout_irs, ohs_batch_set_layout_schedule_irs (and the direction table of the scene libraries) wait for the
+ *     whole device first: a call queued in front of them runs on the old tables, the next one on the new ones.
+ *   Moving between streams.  One handle serves one signal; a caller that makes its next call on another stream orders that
+ *     stream behind the previous one (an event, hipStreamWaitEvent) -- the library orders its internal stream, and a pending
+ *     deferred call, by itself.  ohs_batch_join on a stream makes that stream alone wait for the deferred call's output.
+ *   The calls return without waiting for hip_stream, with these exceptions, none of them for an audio thread:
+ *     - the scheduled kinds and the scene calls stage their rows in one of four slots: with four such calls of a handle still in
+ *       flight the fifth waits, on the host, for the first to complete;
+ *     - the first processing call after ohs_batch_set_stream_eq_band_coeffs (or any per-stream band edit) uploads the tables and
+ *       waits for the work queued on its stream;
+ *     - a call that needs more scratch than any call of the handle before it (more blocks in one convolution launch, another
+ *       plan or kernel family, a staging slot's first use) allocates, and waits for its stream where it has to free;
+ *     - ohs_batch_sync, and the setters of device tables above. */
 int  ohs_batch_process(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks,
                        size_t stream_stride, size_t channel_stride, void *hip_stream);
 /* ---- a schedule of EQ tables and gains inside one call ----

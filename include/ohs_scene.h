@@ -9,7 +9,9 @@
  * Conventions are ohs_hip.h's: every function returns a status (0 = ok; the values are ohs_hip.h's OHS_* codes, restated
  * below), ohs_scene_last_error() is the thread-local detail of the last failure in THIS library, audio buffers are DEVICE
  * pointers, planar f32, `irs` and every row are HOST pointers that are free again when the call returns.  A handle is used
- * from one thread at a time.  Blocks are 512 frames.
+ * from one thread at a time.  Blocks are 512 frames.  What "asynchronous on hip_stream" promises -- input produced on the stream,
+ * buffers reusable on the stream and rows on return, which calls may wait on the host (the fifth call in flight) -- is THE STREAM
+ * CONTRACT beside ohs_batch_process in ohs_hip.h; tests/test_gpu_stream_order.py holds this library's calls to it.
  *
  * Out of scope (none of it is built): a session-renderer mode over scenes; interpolation between two directions per
  * object (an object takes the table's entry it names); responses beyond one partition (512 taps); in-place calls; a

@@ -10,6 +10,7 @@
  * Conventions are ohs_scene.h's: every function returns a status (0 = ok), the last-error entry gives the thread-local
  * detail of the last failure in THIS library, audio buffers are DEVICE pointers, planar f32, `irs` and every row are HOST
  * pointers that are free again when the call returns.  A handle is used from one thread at a time.  Blocks are 512 frames.
+ * Asynchrony is THE STREAM CONTRACT beside ohs_batch_process in ohs_hip.h, for the three calls here that take a hip_stream.
  *
  * Out of scope (none of it is built): three or more directions per object; per-sample weight ramps other than the
  * one-block fade; and the rest of ohs_scene.h's list -- a session-renderer mode over scenes, responses beyond one partition
