@@ -1,5 +1,5 @@
-"""Builds libohs_hip.so (HIP kernels + C ABI), libohs_scene.so (the same objects + the ohs_scene_* entries) and libohs_scene2.so (the
-same objects + the ohs_scene2_* entries) for gfx950, in-tree.
+"""Builds libohs_hip.so (HIP kernels + C ABI), libohs_scene.so (the same objects + the ohs_scene_* entries), libohs_scene2.so (the
+same objects + the ohs_scene2_* entries) and libohs_lookup.so (its own two objects and nothing of the product's) for gfx950, in-tree.
 
     python -m open_headstage_amd.build [--force]
 
@@ -53,6 +53,12 @@ SCENE_UNIT = ("api_scene.hip", [])
 # else (csrc/scene2_exports.map).  Untagged build only.
 SCENE2_LIB = os.path.join(HERE, "libohs_scene2.so")
 SCENE2_UNIT = ("api_scene2.hip", [])
+# The LOOKUP library (include/ohs_lookup.h): direction indices and weights for the scene calls, found on the device.  Its own two
+# units and none of the product's objects, exporting ohs_lookup_* and nothing else (csrc/lookup_exports.map).  Untagged build only.
+# Every operation of the search rounds by itself (-ffp-contract=off): the answers are tests/lookup_model.py's bits.
+LOOKUP_LIB = os.path.join(HERE, "libohs_lookup.so")
+LOOKUP_UNITS = [("lookup_kernels.hip", ["-ffp-contract=off"]), ("api_lookup.hip", ["-ffp-contract=off"])]
+LOOKUP_HEADERS = ("lookup_body.hpp", "lookup_internal.h")
 ARCH = "gfx950"
 
 
@@ -97,7 +103,11 @@ def _hipcc() -> str:
 
 def _deps(src: str) -> list[str]:
     deps = [os.path.join(CSRC, src)]
-    deps += sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp", ".inc")))
+    if src in [u for u, _ in LOOKUP_UNITS]:             # (the lookup library includes its own headers and ohs_hip.h's status codes)
+        deps += [os.path.join(CSRC, f) for f in LOOKUP_HEADERS]
+        deps += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("ohs_hip.h", "ohs_lookup.h")]
+        return deps + [os.path.join(CSRC, "lookup_exports.map"), os.path.abspath(__file__)]
+    deps += sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp", ".inc")) and f not in LOOKUP_HEADERS)
     exp_dir = os.path.join(CSRC, "experiments")         # (included under -DOHS_EXPERIMENTS only)
     if os.path.isdir(exp_dir):
         deps += sorted(os.path.join(exp_dir, f) for f in os.listdir(exp_dir) if f.endswith((".h", ".hpp", ".inc")))
@@ -124,12 +134,12 @@ def _unit_hash(src: str, extra: list[str]) -> str:
 
 
 def _all_units():
-    """the product's units, and behind them the two scene libraries' own (untagged build only)"""
-    return _units() + ([] if TAG else [SCENE_UNIT, SCENE2_UNIT])
+    """the product's units, and behind them the two scene libraries' own and the lookup library's (untagged build only)"""
+    return _units() + ([] if TAG else [SCENE_UNIT, SCENE2_UNIT] + LOOKUP_UNITS)
 
 
 def _libs_exist() -> bool:
-    return os.path.exists(LIB) and (bool(TAG) or (os.path.exists(SCENE_LIB) and os.path.exists(SCENE2_LIB)))
+    return os.path.exists(LIB) and (bool(TAG) or all(os.path.exists(p) for p in (SCENE_LIB, SCENE2_LIB, LOOKUP_LIB)))
 
 
 def _current_hashes() -> dict:
@@ -145,8 +155,8 @@ def _read_stamp() -> dict:
 
 
 def is_current() -> bool:
-    """True when libohs_hip.so (and, untagged, libohs_scene.so and libohs_scene2.so) exists and was built from exactly the sources in
-    the tree."""
+    """True when libohs_hip.so (and, untagged, libohs_scene.so, libohs_scene2.so and libohs_lookup.so) exists and was built from
+    exactly the sources in the tree."""
     return _libs_exist() and _read_stamp() == _current_hashes()
 
 
@@ -182,11 +192,13 @@ def build(force: bool = False, verbose: bool = False) -> str:
             with open(obj + ".hash", "w") as f:
                 f.write(want[src])
     # exported surface = the C ABI (csrc/exports.map); the C++ internals stay local
-    product_objs = objs[:len(_units())]
+    n_product = len(_units())
+    product_objs = objs[:n_product]
     links = [(LIB, product_objs, "exports.map")]
     if not TAG:     # the scene libraries: the same objects + api_scene.o / api_scene2.o, each its own version script
-        links.append((SCENE_LIB, product_objs + [objs[-2]], "scene_exports.map"))
-        links.append((SCENE2_LIB, product_objs + [objs[-1]], "scene2_exports.map"))
+        links.append((SCENE_LIB, product_objs + [objs[n_product]], "scene_exports.map"))
+        links.append((SCENE2_LIB, product_objs + [objs[n_product + 1]], "scene2_exports.map"))
+        links.append((LOOKUP_LIB, objs[n_product + 2:], "lookup_exports.map"))      # (its own objects only)
     for lib, lib_objs, vscript in links:
         cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib, *lib_objs,
                "-Wl,--version-script=" + os.path.join(CSRC, vscript), "-lz", "-ldl", "-lpthread"]
