@@ -23,8 +23,9 @@
  *                      no m survives (every point is a copy of P[idx0]): idx1 = idx0, w = +0.0
  * There is no trigonometry here: angles become coordinates on the caller's side.
  *
- * Out of scope (none of it is built): rows handed to the scene calls on the device (their ABI takes host rows); three or more
- * directions per object; a session renderer over scenes. */
+ * Out of scope (none of it is built): rows handed to the scene calls on the device (their ABI takes host rows); the three
+ * directions and two weights per object that libohs_scene3.so renders (ohs_scene3.h: the caller computes those rows); a session
+ * renderer over scenes. */
 #ifndef OHS_LOOKUP_H
 #define OHS_LOOKUP_H
 

@@ -14,6 +14,7 @@ from .pcm import WavReader, pcm_decode_device, pcm_encode_device
 from .autoeq import BandSetting, apply_bands, parse_autoeq_csv, parse_autoeq_csv_text
 from .scene import SceneError, SceneProcessor, nearest_directions, rotate_sources
 from .scene2 import BlendSceneProcessor, bracket_directions
+from .scene3 import TriSceneProcessor, triangle_directions, triangulate_directions
 from .lookup import DirectionLookup, DirectionLookupError
 from ._ffi import OhsError
 
@@ -23,4 +24,5 @@ __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter
            "parse_autoeq_csv", "parse_autoeq_csv_text", "LAYOUT_5_1", "LAYOUT_7_1", "SessionRenderer",
            "HeadTrack", "nearest_set", "yaw_rows", "plan_calls", "render_files", "WavReader", "pcm_decode_device",
            "pcm_encode_device", "SceneProcessor", "SceneError", "rotate_sources", "nearest_directions",
-           "BlendSceneProcessor", "bracket_directions", "DirectionLookup", "DirectionLookupError"]
+           "BlendSceneProcessor", "bracket_directions", "TriSceneProcessor", "triangle_directions",
+           "triangulate_directions", "DirectionLookup", "DirectionLookupError"]

@@ -1,5 +1,6 @@
 """Builds libohs_hip.so (HIP kernels + C ABI), libohs_scene.so (the same objects + the ohs_scene_* entries), libohs_scene2.so (the
-same objects + the ohs_scene2_* entries) and libohs_lookup.so (its own two objects and nothing of the product's) for gfx950, in-tree.
+same objects + the ohs_scene2_* entries), libohs_scene3.so (the same objects + the ohs_scene3_* entries) and libohs_lookup.so (its
+own two objects and nothing of the product's) for gfx950, in-tree.
 
     python -m open_headstage_amd.build [--force]
 
@@ -53,6 +54,10 @@ SCENE_UNIT = ("api_scene.hip", [])
 # else (csrc/scene2_exports.map).  Untagged build only.
 SCENE2_LIB = os.path.join(HERE, "libohs_scene2.so")
 SCENE2_UNIT = ("api_scene2.hip", [])
+# The third SCENE library (include/ohs_scene3.h): the product's object files plus api_scene3.o, exporting ohs_scene3_* and nothing
+# else (csrc/scene3_exports.map).  Untagged build only.
+SCENE3_LIB = os.path.join(HERE, "libohs_scene3.so")
+SCENE3_UNIT = ("api_scene3.hip", [])
 # The LOOKUP library (include/ohs_lookup.h): direction indices and weights for the scene calls, found on the device.  Its own two
 # units and none of the product's objects, exporting ohs_lookup_* and nothing else (csrc/lookup_exports.map).  Untagged build only.
 # Every operation of the search rounds by itself (-ffp-contract=off): the answers are tests/lookup_model.py's bits.
@@ -73,6 +78,7 @@ def _units():
         ("conv_xb_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),   # block 8192 / FFT 16384 in one kernel: their long out-of-place calls
         ("conv_objects_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),   # K moving sources per stream (libohs_scene.so reaches it)
         ("conv_objects_blend_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),   # ... between two directions each (libohs_scene2.so)
+        ("conv_objects_blend3_kernels.hip", ["-fno-slp-vectorize", "-ffp-contract=off"]),  # ... inside a triangle of three (libohs_scene3.so)
         # (experiments builds only: OHS_MAC_TB / OHS_MAC_PI fix the MAC's register tile)
         ("conv_mac_kernels.hip", [f"-D{k}={os.environ[k]}" for k in ("OHS_MAC_TB", "OHS_MAC_PI")
                                   if EXPERIMENTS and k in os.environ]),
@@ -119,6 +125,9 @@ def _deps(src: str) -> list[str]:
     if src == SCENE2_UNIT[0]:
         deps.append(os.path.join(os.path.dirname(HERE), "include", "ohs_scene2.h"))
         deps.append(os.path.join(CSRC, "scene2_exports.map"))
+    if src == SCENE3_UNIT[0]:
+        deps.append(os.path.join(os.path.dirname(HERE), "include", "ohs_scene3.h"))
+        deps.append(os.path.join(CSRC, "scene3_exports.map"))
     deps.append(os.path.abspath(__file__))
     return deps
 
@@ -134,12 +143,12 @@ def _unit_hash(src: str, extra: list[str]) -> str:
 
 
 def _all_units():
-    """the product's units, and behind them the two scene libraries' own and the lookup library's (untagged build only)"""
-    return _units() + ([] if TAG else [SCENE_UNIT, SCENE2_UNIT] + LOOKUP_UNITS)
+    """the product's units, and behind them the three scene libraries' own and the lookup library's (untagged build only)"""
+    return _units() + ([] if TAG else [SCENE_UNIT, SCENE2_UNIT, SCENE3_UNIT] + LOOKUP_UNITS)
 
 
 def _libs_exist() -> bool:
-    return os.path.exists(LIB) and (bool(TAG) or all(os.path.exists(p) for p in (SCENE_LIB, SCENE2_LIB, LOOKUP_LIB)))
+    return os.path.exists(LIB) and (bool(TAG) or all(os.path.exists(p) for p in (SCENE_LIB, SCENE2_LIB, SCENE3_LIB, LOOKUP_LIB)))
 
 
 def _current_hashes() -> dict:
@@ -155,8 +164,8 @@ def _read_stamp() -> dict:
 
 
 def is_current() -> bool:
-    """True when libohs_hip.so (and, untagged, libohs_scene.so, libohs_scene2.so and libohs_lookup.so) exists and was built from
-    exactly the sources in the tree."""
+    """True when libohs_hip.so (and, untagged, libohs_scene.so, libohs_scene2.so, libohs_scene3.so and libohs_lookup.so)
+    exists and was built from exactly the sources in the tree."""
     return _libs_exist() and _read_stamp() == _current_hashes()
 
 
@@ -195,10 +204,11 @@ def build(force: bool = False, verbose: bool = False) -> str:
     n_product = len(_units())
     product_objs = objs[:n_product]
     links = [(LIB, product_objs, "exports.map")]
-    if not TAG:     # the scene libraries: the same objects + api_scene.o / api_scene2.o, each its own version script
+    if not TAG:     # the scene libraries: the same objects + api_scene.o / api_scene2.o / api_scene3.o, each its own version script
         links.append((SCENE_LIB, product_objs + [objs[n_product]], "scene_exports.map"))
         links.append((SCENE2_LIB, product_objs + [objs[n_product + 1]], "scene2_exports.map"))
-        links.append((LOOKUP_LIB, objs[n_product + 2:], "lookup_exports.map"))      # (its own objects only)
+        links.append((SCENE3_LIB, product_objs + [objs[n_product + 2]], "scene3_exports.map"))
+        links.append((LOOKUP_LIB, objs[n_product + 3:], "lookup_exports.map"))      # (its own objects only)
     for lib, lib_objs, vscript in links:
         cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib, *lib_objs,
                "-Wl,--version-script=" + os.path.join(CSRC, vscript), "-lz", "-ldl", "-lpthread"]

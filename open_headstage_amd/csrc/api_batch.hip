@@ -1015,43 +1015,52 @@ extern "C" int ohsint_batch_last_objects_launch(const ohs_batch *b, int *n_pairs
     return OHS_OK;
 }
 
-// The scene call, one direction per object (dir_idx1 == weight == nullptr: k_conv_p1_objects) or two with a weight (both given:
-// k_conv_p1_objects_blend): one set of checks, one scan over every row that will be read, one staging path, one epilogue.
+// The scene call, one direction per object (dir_idx1 == weight == nullptr: k_conv_p1_objects), two with a weight (both given:
+// k_conv_p1_objects_blend) or three with two weights (dir_idx2 and weight2 given as well: k_conv_p1_objects_blend3): one set of
+// checks, one scan over every row that will be read, one staging path, one epilogue.
 static int batch_process_objects_any(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
                                      size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride, size_t n_objects,
                                      size_t seg_blocks, const unsigned *dir_idx, const float *obj_gain, size_t idx_stride,
                                      const unsigned *prev_idx, const float *prev_gain, int switch_mode, void *hip_stream,
-                                     const unsigned *dir_idx1, const float *weight, const unsigned *prev_idx1, const float *prev_weight)
+                                     const unsigned *dir_idx1, const float *weight, const unsigned *prev_idx1, const float *prev_weight,
+                                     const unsigned *dir_idx2 = nullptr, const float *weight2 = nullptr, const unsigned *prev_idx2 = nullptr,
+                                     const float *prev_weight2 = nullptr)
 {
     if (!b || !d_in || !d_out || !dir_idx) return fail(OHS_ERR_INVALID_ARG, "NULL argument");
     if ((dir_idx1 == nullptr) != (weight == nullptr)) return fail(OHS_ERR_INVALID_ARG, "dir_idx1 and weight are both NULL or both given");
-    const bool blend = dir_idx1 != nullptr;
+    if ((dir_idx2 == nullptr) != (weight2 == nullptr)) return fail(OHS_ERR_INVALID_ARG, "dir_idx2 and weight2 are both NULL or both given");
+    if (dir_idx2 && !dir_idx1) return fail(OHS_ERR_INVALID_ARG, "dir_idx2 and weight2 need dir_idx1 and weight");
+    const bool blend = dir_idx1 != nullptr, tri = dir_idx2 != nullptr;
     if (!blend) { prev_idx1 = nullptr; prev_weight = nullptr; }     // (nothing for them to stand in front of)
+    if (!tri) { prev_idx2 = nullptr; prev_weight2 = nullptr; }
     if (n_objects == 0 || n_objects > 64) return fail(OHS_ERR_INVALID_ARG, "n_objects must be 1 .. 64");
     if (seg_blocks == 0) return fail(OHS_ERR_INVALID_ARG, "seg_blocks is 0");
     if (switch_mode != 0 && switch_mode != 1) return fail(OHS_ERR_INVALID_ARG, "switch_mode must be OHS_SCENE_SWITCH_RING_OUT or OHS_SCENE_SWITCH_CROSSFADE");
     ConvState &c = b->conv;
-    if (c.obj_n == 0 || !c.d_obj_ah) return fail(OHS_ERR_INVALID_ARG, "no direction table uploaded (ohs_scene_set_direction_irs)");
+    if (c.obj_n == 0 || !c.d_obj_ah)
+        return fail(OHS_ERR_INVALID_ARG, tri ? "no direction table uploaded (ohs_scene3_set_direction_irs)"
+                                             : "no direction table uploaded (ohs_scene_set_direction_irs)");
     if (n_blocks > (size_t)1 << 24) return fail(OHS_ERR_INVALID_ARG, "n_blocks too large");
     if (b->failed) return batch_refuse_failed(b);
     if (n_blocks == 0) return OHS_OK;
     const size_t n_segs = sched_segments(n_blocks, &seg_blocks), frames = n_blocks * BS, S = c.S, K = n_objects;
     if (idx_stride != 0 && idx_stride < n_segs)
         return fail(OHS_ERR_INVALID_ARG, "idx_stride is 0 (one row for all streams) or >= the number of segments");
-    if ((blend ? 4 : 1) * S * n_segs * K > (size_t)0x7fffffff) return fail(OHS_ERR_INVALID_ARG, "schedule too large");
+    if ((tri ? 6 : blend ? 4 : 1) * S * n_segs * K > (size_t)0x7fffffff) return fail(OHS_ERR_INVALID_ARG, "schedule too large");
     const bool fade = switch_mode == 1, shared = idx_stride == 0;
     if (!fade) { prev_idx = nullptr; prev_gain = nullptr; prev_idx1 = nullptr; prev_weight = nullptr; }    // (read under CROSSFADE only)
+    if (!fade) { prev_idx2 = nullptr; prev_weight2 = nullptr; }
     const size_t n_rows = shared ? 1 : S;
     // The blended kernel reads four planes of one shape and, under CROSSFADE, four planes in front of the call that the host always
     // stages (the first segment's own entries where the caller names none).  A gain in front of the call beside no gain rows: the
-    // rows read as 1.0, so they are staged as that.
+    // rows read as 1.0, so they are staged as that.  The three-direction kernel reads six planes where that one reads four.
     std::vector<float> ones;
-    std::vector<unsigned> prev;     // [4][n_rows][K]: idx, idx1, weight, gain in front of the call
+    std::vector<unsigned> prev;     // [4][n_rows][K]: idx, idx1, weight, gain in front of the call; [6]: idx, idx1, idx2, w1, w2, gain
     size_t gain_stride = idx_stride;
     if (blend) {
         try {
             if (!obj_gain && prev_gain) ones.assign(n_rows * n_segs * K, 1.0f);
-            if (fade) prev.resize(4 * n_rows * K);
+            if (fade) prev.resize((tri ? 6 : 4) * n_rows * K);
         } catch (const std::bad_alloc &) {
             return fail(OHS_ERR_ALLOC, "out of host memory for the rows' staging");
         }
@@ -1060,31 +1069,57 @@ static int batch_process_objects_any(ohs_batch *b, const float *d_in, float *d_o
     const unsigned kOne = 0x3f800000u;
     const unsigned *gain_bits = reinterpret_cast<const unsigned *>(obj_gain), *pgain_bits = reinterpret_cast<const unsigned *>(prev_gain);
     const unsigned *w_bits = reinterpret_cast<const unsigned *>(weight), *pw_bits = reinterpret_cast<const unsigned *>(prev_weight);
+    const unsigned *w2_bits = reinterpret_cast<const unsigned *>(weight2), *pw2_bits = reinterpret_cast<const unsigned *>(prev_weight2);
     auto weight_ok = [](unsigned bits) {
         float w;
         std::memcpy(&w, &bits, sizeof w);
         return w >= 0.0f && w <= 1.0f;      // (NaN fails both; -0.0 passes)
     };
-    // one pass over every row that will be read: the indices against the table, the weights against [0, 1], the passes through old
-    // directions and the passes that load four rows
-    unsigned long long fading = 0, blended = 0;
+    auto weights_ok = [](unsigned bits1, unsigned bits2) {
+        float w1, w2;
+        std::memcpy(&w1, &bits1, sizeof w1);
+        std::memcpy(&w2, &bits2, sizeof w2);
+        const volatile float sum = w1 + w2;     // (the sum in f32, whatever the host compiler would keep it in)
+        return w1 >= 0.0f && w2 >= 0.0f && sum <= 1.0f;     // (NaN fails; -0.0 passes)
+    };
+    // one pass over every row that will be read: the indices against the table, the weights against [0, 1] (three directions: against
+    // the triangle), the passes through old directions, the passes that load four rows and the passes that load six
+    unsigned long long fading = 0, blended = 0, blended3 = 0;
     for (size_t r = 0; r < n_rows; ++r) {
         const size_t ro = r * idx_stride * K;
         const unsigned *row = dir_idx + ro, *row1 = blend ? dir_idx1 + ro : nullptr, *wrow = blend ? w_bits + ro : nullptr;
         const unsigned *grow = gain_bits ? gain_bits + r * gain_stride * K : nullptr;
         const unsigned *oi = prev_idx ? prev_idx + r * K : nullptr, *oj = prev_idx1 ? prev_idx1 + r * K : nullptr;
         const unsigned *ow = pw_bits ? pw_bits + r * K : nullptr, *og = pgain_bits ? pgain_bits + r * K : nullptr;
+        const unsigned *row2 = tri ? dir_idx2 + ro : nullptr, *w2row = tri ? w2_bits + ro : nullptr;
+        const unsigned *ok = prev_idx2 ? prev_idx2 + r * K : nullptr, *ov = pw2_bits ? pw2_bits + r * K : nullptr;
         for (size_t o = 0; o < K; ++o) {
             if (oi && oi[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "prev_idx entry out of range");
             if (oj && oj[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "prev_idx1 entry out of range");
-            if (ow && !weight_ok(ow[o])) return fail(OHS_ERR_INVALID_ARG, "prev_weight entry outside [0, 1]");
+            if (ok && ok[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "prev_idx2 entry out of range");
+            if (!tri && ow && !weight_ok(ow[o])) return fail(OHS_ERR_INVALID_ARG, "prev_weight entry outside [0, 1]");
         }
+        const bool prev_w_named = ow || ov;
         if (fade) {         // (no boundary at the call's start for what the caller does not name)
             if (!oi) oi = row;
             if (!oj) oj = row1;
             if (!ow) ow = wrow;
             if (!og) og = grow;
-            for (size_t o = 0; blend && o < K; ++o) {
+            if (!ok) ok = row2;
+            if (!ov) ov = w2row;
+            // (the pair in front of the call, whichever half of it the caller named; with neither named it is the first segment's
+            // own pair, which the scan below checks under its own name)
+            for (size_t o = 0; tri && o < K; ++o) {
+                if (prev_w_named && !weights_ok(ow[o], ov[o]))
+                    return fail(OHS_ERR_INVALID_ARG, "prev_weight / prev_weight2 entry outside w1 >= 0, w2 >= 0, w1 + w2 <= 1");
+                prev[(0 * n_rows + r) * K + o] = oi[o];
+                prev[(1 * n_rows + r) * K + o] = oj[o];
+                prev[(2 * n_rows + r) * K + o] = ok[o];
+                prev[(3 * n_rows + r) * K + o] = ow[o];
+                prev[(4 * n_rows + r) * K + o] = ov[o];
+                prev[(5 * n_rows + r) * K + o] = og ? og[o] : kOne;
+            }
+            for (size_t o = 0; blend && !tri && o < K; ++o) {
                 prev[(0 * n_rows + r) * K + o] = oi[o];
                 prev[(1 * n_rows + r) * K + o] = oj[o];
                 prev[(2 * n_rows + r) * K + o] = ow[o];
@@ -1094,29 +1129,39 @@ static int batch_process_objects_any(ohs_batch *b, const float *d_in, float *d_o
         for (size_t k = 0; k < n_segs; ++k) {
             const unsigned *ci = row + k * K, *cj = blend ? row1 + k * K : nullptr, *cw = blend ? wrow + k * K : nullptr;
             const unsigned *cg = grow ? grow + k * K : nullptr;
+            const unsigned *ck = tri ? row2 + k * K : nullptr, *cv = tri ? w2row + k * K : nullptr;
             for (size_t o = 0; o < K; ++o) {
                 if (ci[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "dir_idx entry out of range");
                 if (blend && cj[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "dir_idx1 entry out of range");
-                if (blend && !weight_ok(cw[o])) return fail(OHS_ERR_INVALID_ARG, "weight entry outside [0, 1]");
+                if (tri && ck[o] >= c.obj_n) return fail(OHS_ERR_INVALID_ARG, "dir_idx2 entry out of range");
+                if (blend && !tri && !weight_ok(cw[o])) return fail(OHS_ERR_INVALID_ARG, "weight entry outside [0, 1]");
+                if (tri && !weights_ok(cw[o], cv[o]))
+                    return fail(OHS_ERR_INVALID_ARG, "weight / weight2 entry outside w1 >= 0, w2 >= 0, w1 + w2 <= 1");
             }
             const unsigned long long seg_len = std::min(seg_blocks, n_blocks - k * seg_blocks);
             for (size_t p = 0; 2 * p < K; ++p) {
-                bool ch = false, cur_blend = false, old_blend = false;
+                bool ch = false, cur_blend = false, old_blend = false, cur_tri = false, old_tri = false;
                 for (size_t o = 2 * p; o < std::min(2 * p + 2, K); ++o) {
                     cur_blend = cur_blend || (blend && cw[o] != 0u);
+                    cur_tri = cur_tri || (tri && cv[o] != 0u);
                     if (!fade) continue;
                     old_blend = old_blend || (blend && ow[o] != 0u);
+                    old_tri = old_tri || (tri && ov[o] != 0u);
+                    // (idx2 beside a w2 of +0.0 before and after is never read either)
+                    ch = ch || (tri && (cv[o] != ov[o] || ((cv[o] | ov[o]) != 0u && ck[o] != ok[o])));
                     ch = ch || ci[o] != oi[o] || (cg ? cg[o] : kOne) != (og ? og[o] : kOne);
                     // (idx1 beside a weight of +0.0 before and after is never read: no change, as in the kernel)
                     ch = ch || (blend && (cw[o] != ow[o] || ((cw[o] | ow[o]) != 0u && cj[o] != oj[o])));
                 }
                 fading += ch ? 1 : 0;
-                blended += (cur_blend ? seg_len : 0) + (ch && old_blend ? 1 : 0);
+                // (a pass with a nonzero w2 loads six rows; one without it and with a nonzero w1 loads four)
+                blended += (cur_blend && !cur_tri ? seg_len : 0) + (ch && old_blend && !old_tri ? 1 : 0);
+                blended3 += (cur_tri ? seg_len : 0) + (ch && old_tri ? 1 : 0);
             }
-            oi = ci; oj = cj; ow = cw; og = cg;
+            oi = ci; oj = cj; ow = cw; og = cg; ok = ck; ov = cv;
         }
     }
-    if (shared) { fading *= S; blended *= S; }
+    if (shared) { fading *= S; blended *= S; blended3 *= S; }
     if (!layout_regions_ok(S, K, frames, d_in, in_stream_stride, in_channel_stride, d_out, out_stream_stride, out_channel_stride))
         return OHS_ERR_INVALID_ARG;
     HIP_TRY(hipSetDevice(b->device));
@@ -1130,7 +1175,22 @@ static int batch_process_objects_any(ohs_batch *b, const float *d_in, float *d_o
         // the rows' staging slot (the scheduled calls'), each array packed and one behind the other
         const SchedRows ri{dir_idx, idx_stride * K, n_rows, n_segs * K}, rg{obj_gain, gain_stride * K, n_rows, n_segs * K};
         int rc;
-        if (blend) {        // indices, second indices, weights, gains -- four planes of one size, the last possibly absent --, then prev
+        if (tri) {          // indices, second and third indices, both weights, gains -- six planes of one size, the last possibly absent --, then prev
+            const size_t plane = n_rows * n_segs * K;
+            const SchedRows rj{dir_idx1, idx_stride * K, n_rows, n_segs * K}, rk{dir_idx2, idx_stride * K, n_rows, n_segs * K},
+                rw{weight, idx_stride * K, n_rows, n_segs * K}, rv{weight2, idx_stride * K, n_rows, n_segs * K},
+                pv{fade ? prev.data() : nullptr, prev.size(), 1, prev.size()};
+            const int rcs = sched_stage(b, {&ri, &rj, &rk, &rw, &rv, &rg, &pv}, st, lease);
+            if (rcs) return rcs;
+            ConvObjectBlendRows rows;
+            rows.rows = lease.slot->d; rows.plane = (int)plane; rows.has_gain = obj_gain != nullptr;
+            if (fade) rows.prev = lease.slot->d + 5 * plane + rg.entries();
+            rows.prev_plane = (int)(n_rows * K);
+            rows.seg_blocks = (int)seg_blocks; rows.stream_stride = shared ? 0 : (int)(n_segs * K); rows.prev_stride = shared ? 0 : (int)K;
+            rows.fade = fade;
+            rc = conv_launch_objects_blend3(c, b->ctx, d_in, (long long)in_stream_stride, (long long)in_channel_stride, d_out,
+                                            (long long)out_stream_stride, (long long)out_channel_stride, (int)n_blocks, b->gain, st, (int)K, rows);
+        } else if (blend) { // indices, second indices, weights, gains -- four planes of one size, the last possibly absent --, then prev
             const size_t plane = n_rows * n_segs * K;
             const SchedRows rj{dir_idx1, idx_stride * K, n_rows, n_segs * K}, rw{weight, idx_stride * K, n_rows, n_segs * K},
                 pv{fade ? prev.data() : nullptr, prev.size(), 1, prev.size()};
@@ -1162,7 +1222,7 @@ static int batch_process_objects_any(ohs_batch *b, const float *d_in, float *d_o
                                      (long long)out_stream_stride, (long long)out_channel_stride, (int)n_blocks, b->gain, st, (int)K, rows);
         }
         if (rc) return rc;
-        c.last_obj_fading = fading; c.last_obj_blended = blended;
+        c.last_obj_fading = fading; c.last_obj_blended = blended; c.last_obj_blended3 = blended3;
         if (b->eq_enable && eq_any_enabled(b->eq))      // EQ(gain * conv(x)): the two ear channels, in place, behind the whole call
             rc = eq_launch(b->eq, d_out, d_out, (long long)out_stream_stride, (long long)out_channel_stride, (long long)frames, st);
         return rc;
@@ -1205,6 +1265,35 @@ extern "C" int ohsint_batch_last_objects_blend_launch(const ohs_batch *b, int *n
     *ranges_per_stream = b->conv.last_obj_ranges;
     *fading_passes = b->conv.last_obj_fading;
     *blended_passes = b->conv.last_obj_blended;
+    return OHS_OK;
+}
+
+// ---- three directions and two weights per object (libohs_scene3.so; no entry of ohs_hip.h, ohs_scene.h or ohs_scene2.h) ------------
+// dir_idx2 and weight2 both NULL: ohsint_batch_process_objects_blend
+extern "C" int ohsint_batch_process_objects_blend3(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
+                                                   size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride,
+                                                   size_t n_objects, size_t seg_blocks, const unsigned *dir_idx, const float *obj_gain,
+                                                   size_t idx_stride, const unsigned *prev_idx, const float *prev_gain, int switch_mode,
+                                                   void *hip_stream, const unsigned *dir_idx1, const float *weight,
+                                                   const unsigned *prev_idx1, const float *prev_weight, const unsigned *dir_idx2,
+                                                   const float *weight2, const unsigned *prev_idx2, const float *prev_weight2)
+{
+    return batch_process_objects_any(b, d_in, d_out, n_blocks, in_stream_stride, in_channel_stride, out_stream_stride, out_channel_stride,
+                                     n_objects, seg_blocks, dir_idx, obj_gain, idx_stride, prev_idx, prev_gain, switch_mode, hip_stream,
+                                     dir_idx1, weight, prev_idx1, prev_weight, dir_idx2, weight2, prev_idx2, prev_weight2);
+}
+
+extern "C" int ohsint_batch_last_objects_blend3_launch(const ohs_batch *b, int *n_pairs, int *ranges_per_stream,
+                                                       unsigned long long *fading_passes, unsigned long long *blended_passes,
+                                                       unsigned long long *blended3_passes)
+{
+    if (!b || !n_pairs || !ranges_per_stream || !fading_passes || !blended_passes || !blended3_passes)
+        return fail(OHS_ERR_INVALID_ARG, "NULL argument");
+    *n_pairs = b->conv.last_obj_pairs;
+    *ranges_per_stream = b->conv.last_obj_ranges;
+    *fading_passes = b->conv.last_obj_fading;
+    *blended_passes = b->conv.last_obj_blended;
+    *blended3_passes = b->conv.last_obj_blended3;
     return OHS_OK;
 }
 

@@ -229,6 +229,7 @@ struct ConvState {
     int last_obj_pairs = 0, last_obj_ranges = 0;    // the most recent scene launch (ohs_scene_last_launch)
     unsigned long long last_obj_fading = 0;         // ... and its passes through old directions, summed over the streams
     unsigned long long last_obj_blended = 0;        // ... and its passes that load four rows (0 behind a plain scene call)
+    unsigned long long last_obj_blended3 = 0;       // ... and its passes that load six rows (0 behind a one- or two-direction call)
     // ohs_*_set_speakers: what it last loaded into each path (a set_ir from anywhere else forgets it), so that a
     // change of the speaker angles re-loads only the paths whose impulse response really changed
     std::vector<float> spk_ir[4];
@@ -355,6 +356,10 @@ struct ConvObjectBlendRows {
 // conv_launch_objects with two directions and a weight per object: one launch of k_conv_p1_objects_blend
 int conv_launch_objects_blend(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out, long long out_ss,
                               long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, const ConvObjectBlendRows &rows);
+// conv_launch_objects with three directions and two weights per object: one launch of k_conv_p1_objects_blend3.  The rows are
+// ConvObjectBlendRows with six planes each -- first, second, third direction, w1, w2, gain (if has_gain)
+int conv_launch_objects_blend3(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out, long long out_ss,
+                               long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, const ConvObjectBlendRows &rows);
 // the handle's four responses become set `set` of the table, overlaps and history untouched (asynchronous on st)
 int conv_adopt_schedule_set(ConvState &c, size_t set, hipStream_t st);
 // the per-path overlaps from the lazy state with the CURRENT spectra, the lazy state kept valid beside them (tails_both)

@@ -31,6 +31,19 @@ extern "C" int ohsint_batch_process_objects_blend(ohs_batch *b, const float *d_i
                                                   const unsigned *prev_idx1, const float *prev_weight);
 extern "C" int ohsint_batch_last_objects_blend_launch(const ohs_batch *b, int *n_pairs, int *ranges_per_stream,
                                                       unsigned long long *fading_passes, unsigned long long *blended_passes);
+// api_batch.hip: what libohs_scene3.so adds (api_scene3.hip, include/ohs_scene3.h) -- the scene call with a third direction and a
+// second weight per object (dir_idx2 and weight2 both NULL: ohsint_batch_process_objects_blend), and the launch record with its
+// six-row passes
+extern "C" int ohsint_batch_process_objects_blend3(ohs_batch *b, const float *d_in, float *d_out, size_t n_blocks, size_t in_stream_stride,
+                                                   size_t in_channel_stride, size_t out_stream_stride, size_t out_channel_stride,
+                                                   size_t n_objects, size_t seg_blocks, const unsigned *dir_idx, const float *obj_gain,
+                                                   size_t idx_stride, const unsigned *prev_idx, const float *prev_gain, int switch_mode,
+                                                   void *hip_stream, const unsigned *dir_idx1, const float *weight,
+                                                   const unsigned *prev_idx1, const float *prev_weight, const unsigned *dir_idx2,
+                                                   const float *weight2, const unsigned *prev_idx2, const float *prev_weight2);
+extern "C" int ohsint_batch_last_objects_blend3_launch(const ohs_batch *b, int *n_pairs, int *ranges_per_stream,
+                                                       unsigned long long *fading_passes, unsigned long long *blended_passes,
+                                                       unsigned long long *blended3_passes);
 
 namespace ohs_host {
 

@@ -350,6 +350,29 @@ struct ConvObjectsBlendArgs {
 };
 // a.chunks as for launch_conv_p1_layout; the host has checked every index against the table and every weight against [0, 1]
 hipError_t launch_conv_p1_objects_blend(const ConvP1Args &a, const ConvObjectsBlendArgs &l, hipStream_t st);
+// K moving sources per stream, each between THREE directions (ohs_scene3_process_blended3; library-internal): k_conv_p1_objects_blend3
+// (conv_objects_blend3_kernels.hip), the body of k_conv_p1_objects_blend with a third index and a second weight per object, stream and
+// segment: the object's row is (u ahalf[idx] + w1 ahalf[idx1]) + w2 ahalf[idx2], u = (1 - w1) - w2.  A struct of its own, so that
+// the two kernels in front stay what they are.
+struct ConvObjectsBlend3Args {
+    const float2 *ahalf;        // ConvObjectsArgs's table, row n_dirs all zero
+    unsigned zero_dir;          // n_dirs
+    int n_pairs;                // ceil(n_objects / 2)
+    int n_objects;
+    const unsigned *rows;       // six planes of [row][segment][n_objects] 32-bit entries, `plane` entries apart: first, second, third
+                                // direction, w1, w2 (f32 bits, each >= 0 and w1 + w2 <= 1), gain (f32 bits)
+    int plane;
+    int has_gain;               // 0: the gain plane is not there, 1.0 everywhere
+    int stream;                 // stream s reads its rows at rows + s * stream (0: one row for all streams)
+    int seg;                    // blocks per segment
+    const unsigned *prev;       // six planes of [row][n_objects] in front of the call's first block, `prev_plane` apart; under CROSSFADE the
+                                // host always stages them (the first segment's own entries where the caller names none); else nullptr
+    int prev_plane;
+    int prev_stream;            // stream s reads prev + s * prev_stream (0: one row for all streams)
+    int fade;                   // 1: CROSSFADE; 0: RING_OUT, no pair fades (prev is not read)
+};
+// a.chunks as for launch_conv_p1_layout; the host has checked every index against the table and every weight pair against the triangle
+hipError_t launch_conv_p1_objects_blend3(const ConvP1Args &a, const ConvObjectsBlend3Args &l, hipStream_t st);
 // cd[set][2][1024] (launch_build_cd per set) -> dst[set][1024] in the block loop's layout, times `scale`
 hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st, float scale = 1.0f);
 // The layout kernels' tables are built with this scale: launch_build_cd's 1/N taken out again, which launch_conv_p1_layout and

@@ -86,6 +86,36 @@ def bracket_directions(positions, az, el, radius_m: float = 1.0):
     return idx0.reshape(azq.shape).astype(np.uint32), idx1.reshape(azq.shape).astype(np.uint32), w.reshape(azq.shape)
 
 
+def _scene_rows(n_streams, K, n_segs, idx, rows, prevs):
+    """The rows of a scene call as the C entries read them, for this module's call and scene3's.  idx: [n_segs][K] for all streams or
+    [n_streams][n_segs][K]; rows: (value or None, dtype, name) each, of idx's shape; prevs: the same for what stood in front of the
+    call's first block, [K] beside shared rows, [n_streams][K] beside rows per stream.
+    -> (idx array, idx_stride, [row arrays or None], [prev arrays or None]); the arrays live as long as the caller holds them."""
+    if idx is None:
+        raise ValueError("idx is required")
+    a, stride = _object_rows(idx, n_streams, n_segs, K, "idx", np.uint32)
+    out = []
+    for v, dtype, what in rows:
+        if v is not None:
+            v, rs = _object_rows(v, n_streams, n_segs, K, what, dtype)
+            if rs != stride:
+                raise ValueError(f"{what} must have idx's shape")
+        out.append(v)
+    n_prev = (n_streams if stride else 1) * K
+    front = []
+    for v, dtype, what in prevs:
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=dtype).reshape(-1)
+            if v.size != n_prev:
+                raise ValueError(f"{what}: expected {n_prev} entries, got {v.size}")
+        front.append(v)
+    return a, stride, out, front
+
+
+def _ptr(v, t):
+    return None if v is None else v.ctypes.data_as(t)
+
+
 class BlendSceneProcessor(SceneProcessor):
     """A SceneProcessor on libohs_scene2.so: every method of it, and two directions with a weight per object."""
     _prefix = "ohs_scene2_"
@@ -100,38 +130,15 @@ class BlendSceneProcessor(SceneProcessor):
         if idx1 is None and weights is None:
             return super().process_ptr(d_in, d_out, n_blocks, in_stream_stride, in_channel_stride, out_stream_stride, out_channel_stride,
                                        n_objects, seg_blocks, idx, gains, prev_idx, prev_gains, crossfade, hip_stream)
-        K, n_segs = int(n_objects), _n_segs(n_blocks, seg_blocks)
-        if idx is None:
-            raise ValueError("idx is required")
-        a, stride = _object_rows(idx, self.n_streams, n_segs, K, "idx", np.uint32)
-
-        def rows(v, dtype, what):
-            if v is None:
-                return None
-            r, rs = _object_rows(v, self.n_streams, n_segs, K, what, dtype)
-            if rs != stride:
-                raise ValueError(f"{what} must have idx's shape")
-            return r
-        g, a1, w = rows(gains, np.float32, "gains"), rows(idx1, np.uint32, "idx1"), rows(weights, np.float32, "weights")
-        n_prev = (self.n_streams if stride else 1) * K
-
-        def prev(v, dtype, what):
-            if v is None:
-                return None
-            v = np.ascontiguousarray(v, dtype=dtype).reshape(-1)
-            if v.size != n_prev:
-                raise ValueError(f"{what}: expected {n_prev} entries, got {v.size}")
-            return v
-        pi, pg = prev(prev_idx, np.uint32, "prev_idx"), prev(prev_gains, np.float32, "prev_gains")
-        pi1, pw = prev(prev_idx1, np.uint32, "prev_idx1"), prev(prev_weights, np.float32, "prev_weights")
-
-        def ptr(v, t):
-            return None if v is None else v.ctypes.data_as(t)
+        K, u32, f32 = int(n_objects), np.uint32, np.float32
+        a, stride, (g, a1, w), (pi, pg, pi1, pw) = _scene_rows(
+            self.n_streams, K, _n_segs(n_blocks, seg_blocks), idx, [(gains, f32, "gains"), (idx1, u32, "idx1"), (weights, f32, "weights")],
+            [(prev_idx, u32, "prev_idx"), (prev_gains, f32, "prev_gains"), (prev_idx1, u32, "prev_idx1"), (prev_weights, f32, "prev_weights")])
         self._check(self._fn("process_blended")(
             self._h, C.c_void_p(d_in), C.c_void_p(d_out), int(n_blocks), int(in_stream_stride), int(in_channel_stride),
-            int(out_stream_stride), int(out_channel_stride), K, int(seg_blocks), ptr(a, u32p), ptr(g, fp), stride, ptr(pi, u32p), ptr(pg, fp),
-            SWITCH_CROSSFADE if crossfade else SWITCH_RING_OUT, C.c_void_p(hip_stream) if hip_stream else None, ptr(a1, u32p), ptr(w, fp),
-            ptr(pi1, u32p), ptr(pw, fp)))
+            int(out_stream_stride), int(out_channel_stride), K, int(seg_blocks), _ptr(a, u32p), _ptr(g, fp), stride, _ptr(pi, u32p), _ptr(pg, fp),
+            SWITCH_CROSSFADE if crossfade else SWITCH_RING_OUT, C.c_void_p(hip_stream) if hip_stream else None, _ptr(a1, u32p), _ptr(w, fp),
+            _ptr(pi1, u32p), _ptr(pw, fp)))
 
     def process(self, x, idx, seg_blocks: int, gains=None, prev_idx=None, prev_gains=None, crossfade: bool = True, idx1=None,
                 weights=None, prev_idx1=None, prev_weights=None, out=None, hip_stream: int | None = None):
