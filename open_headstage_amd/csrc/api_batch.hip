@@ -1051,9 +1051,9 @@ static int batch_process_objects_any(ohs_batch *b, const float *d_in, float *d_o
     if (!fade) { prev_idx = nullptr; prev_gain = nullptr; prev_idx1 = nullptr; prev_weight = nullptr; }    // (read under CROSSFADE only)
     if (!fade) { prev_idx2 = nullptr; prev_weight2 = nullptr; }
     const size_t n_rows = shared ? 1 : S;
-    // The blended kernel reads four planes of one shape and, under CROSSFADE, four planes in front of the call that the host always
-    // stages (the first segment's own entries where the caller names none).  A gain in front of the call beside no gain rows: the
-    // rows read as 1.0, so they are staged as that.  The three-direction kernel reads six planes where that one reads four.
+    // The blended kernels read 2 n_dirs planes of one shape -- four for two directions, six for three -- and, under CROSSFADE, as many
+    // planes in front of the call that the host always stages (the first segment's own entries where the caller names none).  A gain
+    // in front of the call beside no gain rows: the rows read as 1.0, so they are staged as that.
     std::vector<float> ones;
     std::vector<unsigned> prev;     // [4][n_rows][K]: idx, idx1, weight, gain in front of the call; [6]: idx, idx1, idx2, w1, w2, gain
     size_t gain_stride = idx_stride;
@@ -1109,21 +1109,15 @@ static int batch_process_objects_any(ohs_batch *b, const float *d_in, float *d_o
             if (!ov) ov = w2row;
             // (the pair in front of the call, whichever half of it the caller named; with neither named it is the first segment's
             // own pair, which the scan below checks under its own name)
-            for (size_t o = 0; tri && o < K; ++o) {
+            for (size_t o = 0; tri && o < K; ++o)
                 if (prev_w_named && !weights_ok(ow[o], ov[o]))
                     return fail(OHS_ERR_INVALID_ARG, "prev_weight / prev_weight2 entry outside w1 >= 0, w2 >= 0, w1 + w2 <= 1");
-                prev[(0 * n_rows + r) * K + o] = oi[o];
-                prev[(1 * n_rows + r) * K + o] = oj[o];
-                prev[(2 * n_rows + r) * K + o] = ok[o];
-                prev[(3 * n_rows + r) * K + o] = ow[o];
-                prev[(4 * n_rows + r) * K + o] = ov[o];
-                prev[(5 * n_rows + r) * K + o] = og ? og[o] : kOne;
-            }
-            for (size_t o = 0; blend && !tri && o < K; ++o) {
-                prev[(0 * n_rows + r) * K + o] = oi[o];
-                prev[(1 * n_rows + r) * K + o] = oj[o];
-                prev[(2 * n_rows + r) * K + o] = ow[o];
-                prev[(3 * n_rows + r) * K + o] = og ? og[o] : kOne;
+            // the planes in front of the call, in the kernel's order: the directions, the weights, the gain
+            if (blend) {        // (one direction: prev is empty, the kernel reads prev_idx / prev_gain themselves)
+                const unsigned *const front3[6] = {oi, oj, ok, ow, ov, og}, *const front2[4] = {oi, oj, ow, og};
+                const unsigned *const *front = tri ? front3 : front2;
+                for (size_t pl = 0; pl < (tri ? 6u : 4u); ++pl)
+                    for (size_t o = 0; o < K; ++o) prev[(pl * n_rows + r) * K + o] = front[pl] ? front[pl][o] : kOne;     // (only the gain can be absent)
             }
         }
         for (size_t k = 0; k < n_segs; ++k) {
@@ -1175,35 +1169,22 @@ static int batch_process_objects_any(ohs_batch *b, const float *d_in, float *d_o
         // the rows' staging slot (the scheduled calls'), each array packed and one behind the other
         const SchedRows ri{dir_idx, idx_stride * K, n_rows, n_segs * K}, rg{obj_gain, gain_stride * K, n_rows, n_segs * K};
         int rc;
-        if (tri) {          // indices, second and third indices, both weights, gains -- six planes of one size, the last possibly absent --, then prev
+        if (blend) {        // the directions, the weights, the gains -- 2 n_dirs planes of one size, the last possibly absent --, then prev
+            const int n_dirs = tri ? 3 : 2;
             const size_t plane = n_rows * n_segs * K;
             const SchedRows rj{dir_idx1, idx_stride * K, n_rows, n_segs * K}, rk{dir_idx2, idx_stride * K, n_rows, n_segs * K},
                 rw{weight, idx_stride * K, n_rows, n_segs * K}, rv{weight2, idx_stride * K, n_rows, n_segs * K},
                 pv{fade ? prev.data() : nullptr, prev.size(), 1, prev.size()};
-            const int rcs = sched_stage(b, {&ri, &rj, &rk, &rw, &rv, &rg, &pv}, st, lease);
+            const int rcs = sched_stage(b, {&ri, &rj, &rk, &rw, &rv, &rg, &pv}, st, lease);     // (two directions: rk and rv take no room)
             if (rcs) return rcs;
             ConvObjectBlendRows rows;
             rows.rows = lease.slot->d; rows.plane = (int)plane; rows.has_gain = obj_gain != nullptr;
-            if (fade) rows.prev = lease.slot->d + 5 * plane + rg.entries();
-            rows.prev_plane = (int)(n_rows * K);
-            rows.seg_blocks = (int)seg_blocks; rows.stream_stride = shared ? 0 : (int)(n_segs * K); rows.prev_stride = shared ? 0 : (int)K;
-            rows.fade = fade;
-            rc = conv_launch_objects_blend3(c, b->ctx, d_in, (long long)in_stream_stride, (long long)in_channel_stride, d_out,
-                                            (long long)out_stream_stride, (long long)out_channel_stride, (int)n_blocks, b->gain, st, (int)K, rows);
-        } else if (blend) { // indices, second indices, weights, gains -- four planes of one size, the last possibly absent --, then prev
-            const size_t plane = n_rows * n_segs * K;
-            const SchedRows rj{dir_idx1, idx_stride * K, n_rows, n_segs * K}, rw{weight, idx_stride * K, n_rows, n_segs * K},
-                pv{fade ? prev.data() : nullptr, prev.size(), 1, prev.size()};
-            const int rcs = sched_stage(b, {&ri, &rj, &rw, &rg, &pv}, st, lease);
-            if (rcs) return rcs;
-            ConvObjectBlendRows rows;
-            rows.rows = lease.slot->d; rows.plane = (int)plane; rows.has_gain = obj_gain != nullptr;
-            if (fade) rows.prev = lease.slot->d + 3 * plane + rg.entries();
+            if (fade) rows.prev = lease.slot->d + (2 * n_dirs - 1) * plane + rg.entries();
             rows.prev_plane = (int)(n_rows * K);
             rows.seg_blocks = (int)seg_blocks; rows.stream_stride = shared ? 0 : (int)(n_segs * K); rows.prev_stride = shared ? 0 : (int)K;
             rows.fade = fade;
             rc = conv_launch_objects_blend(c, b->ctx, d_in, (long long)in_stream_stride, (long long)in_channel_stride, d_out,
-                                           (long long)out_stream_stride, (long long)out_channel_stride, (int)n_blocks, b->gain, st, (int)K, rows);
+                                           (long long)out_stream_stride, (long long)out_channel_stride, (int)n_blocks, b->gain, st, (int)K, n_dirs, rows);
         } else {            // indices, gains, prev_idx, prev_gain
             const SchedRows pi{prev_idx, K, n_rows, K}, pg{prev_gain, K, n_rows, K};
             const int rcs = sched_stage(b, {&ri, &rg, &pi, &pg}, st, lease);

@@ -967,37 +967,25 @@ int conv_launch_objects(ConvState &c, DeviceCtx *ctx, const float *in, long long
     return OHS_OK;
 }
 
-// The blended scene call: conv_launch_objects's plan on the same table, every object between two directions (k_conv_p1_objects_blend)
+// The blended scene calls: conv_launch_objects's plan on the same table, every object between two directions (n_dirs = 2:
+// k_conv_p1_objects_blend) or inside a triangle of three (n_dirs = 3: k_conv_p1_objects_blend3)
 int conv_launch_objects_blend(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out, long long out_ss,
-                              long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, const ConvObjectBlendRows &rows)
+                              long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, int n_dirs,
+                              const ConvObjectBlendRows &rows)
 {
-    if (!c.d_obj_ah || c.obj_n == 0) return fail(OHS_ERR_INVALID_ARG, "no direction table uploaded (ohs_scene2_set_direction_irs)");
+    const bool tri = n_dirs == 3;
+    if (!c.d_obj_ah || c.obj_n == 0)
+        return fail(OHS_ERR_INVALID_ARG, tri ? "no direction table uploaded (ohs_scene3_set_direction_irs)"
+                                             : "no direction table uploaded (ohs_scene2_set_direction_irs)");
     if (n_blocks <= 0) return OHS_OK;
     const ConvP1Args a = layout_launch_args(c, ctx, in, in_ss, in_cs, out, out_ss, out_cs, n_blocks, gain);
     ConvObjectsBlendArgs l;
     l.ahalf = c.d_obj_ah; l.zero_dir = (unsigned)c.obj_n; l.n_objects = n_objects; l.n_pairs = (n_objects + 1) / 2;
     l.rows = rows.rows; l.plane = rows.plane; l.has_gain = rows.has_gain ? 1 : 0; l.stream = rows.stream_stride; l.seg = rows.seg_blocks;
     l.prev = rows.fade ? rows.prev : nullptr; l.prev_plane = rows.prev_plane; l.prev_stream = rows.prev_stride; l.fade = rows.fade ? 1 : 0;
-    const hipError_t e = launch_conv_p1_objects_blend(a, l, st);
-    if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_objects_blend launch: ") + hipGetErrorString(e));
-    std::swap(c.d_lay_ov, c.d_lay_ov_alt);
-    c.last_obj_pairs = l.n_pairs; c.last_obj_ranges = a.chunks;
-    return OHS_OK;
-}
-
-// The three-direction scene call: conv_launch_objects's plan on the same table, every object inside a triangle (k_conv_p1_objects_blend3)
-int conv_launch_objects_blend3(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out, long long out_ss,
-                               long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, const ConvObjectBlendRows &rows)
-{
-    if (!c.d_obj_ah || c.obj_n == 0) return fail(OHS_ERR_INVALID_ARG, "no direction table uploaded (ohs_scene3_set_direction_irs)");
-    if (n_blocks <= 0) return OHS_OK;
-    const ConvP1Args a = layout_launch_args(c, ctx, in, in_ss, in_cs, out, out_ss, out_cs, n_blocks, gain);
-    ConvObjectsBlend3Args l;
-    l.ahalf = c.d_obj_ah; l.zero_dir = (unsigned)c.obj_n; l.n_objects = n_objects; l.n_pairs = (n_objects + 1) / 2;
-    l.rows = rows.rows; l.plane = rows.plane; l.has_gain = rows.has_gain ? 1 : 0; l.stream = rows.stream_stride; l.seg = rows.seg_blocks;
-    l.prev = rows.fade ? rows.prev : nullptr; l.prev_plane = rows.prev_plane; l.prev_stream = rows.prev_stride; l.fade = rows.fade ? 1 : 0;
-    const hipError_t e = launch_conv_p1_objects_blend3(a, l, st);
-    if (e != hipSuccess) return fail(OHS_ERR_HIP, std::string("conv_p1_objects_blend3 launch: ") + hipGetErrorString(e));
+    const hipError_t e = tri ? launch_conv_p1_objects_blend3(a, l, st) : launch_conv_p1_objects_blend(a, l, st);
+    if (e != hipSuccess)
+        return fail(OHS_ERR_HIP, std::string(tri ? "conv_p1_objects_blend3 launch: " : "conv_p1_objects_blend launch: ") + hipGetErrorString(e));
     std::swap(c.d_lay_ov, c.d_lay_ov_alt);
     c.last_obj_pairs = l.n_pairs; c.last_obj_ranges = a.chunks;
     return OHS_OK;

@@ -345,21 +345,19 @@ struct ConvObjectRows {
 // n_blocks of every stream's n_objects channels -> two ears, times gain: one launch of k_conv_p1_objects.  Out of place, asynchronous on st
 int conv_launch_objects(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out, long long out_ss,
                         long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, const ConvObjectRows &rows);
-// the blended scene call's rows (device memory; validated by the caller), as ConvObjectsBlendArgs reads them: four planes -- first
-// direction, second direction, weight, gain (if has_gain) -- `plane` entries apart, and in front of the call four planes of
-// [row][n_objects], `prev_plane` apart (all four staged whenever fade is set)
+// the blended scene calls' rows (device memory; validated by the caller), as ConvObjectsBlendArgs reads them: 2 n_dirs planes -- the
+// n_dirs directions, the n_dirs - 1 weights, the gain (if has_gain) -- `plane` entries apart, and in front of the call as many planes
+// of [row][n_objects], `prev_plane` apart (all staged whenever fade is set)
 struct ConvObjectBlendRows {
     const unsigned *rows = nullptr, *prev = nullptr;
     int plane = 0, prev_plane = 0, seg_blocks = 1, stream_stride = 0, prev_stride = 0;
     bool has_gain = false, fade = false;
 };
-// conv_launch_objects with two directions and a weight per object: one launch of k_conv_p1_objects_blend
+// conv_launch_objects with n_dirs = 2 directions and a weight per object (one launch of k_conv_p1_objects_blend) or n_dirs = 3
+// directions and two weights (k_conv_p1_objects_blend3)
 int conv_launch_objects_blend(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out, long long out_ss,
-                              long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, const ConvObjectBlendRows &rows);
-// conv_launch_objects with three directions and two weights per object: one launch of k_conv_p1_objects_blend3.  The rows are
-// ConvObjectBlendRows with six planes each -- first, second, third direction, w1, w2, gain (if has_gain)
-int conv_launch_objects_blend3(ConvState &c, DeviceCtx *ctx, const float *in, long long in_ss, long long in_cs, float *out, long long out_ss,
-                               long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, const ConvObjectBlendRows &rows);
+                              long long out_cs, int n_blocks, float gain, hipStream_t st, int n_objects, int n_dirs,
+                              const ConvObjectBlendRows &rows);
 // the handle's four responses become set `set` of the table, overlaps and history untouched (asynchronous on st)
 int conv_adopt_schedule_set(ConvState &c, size_t set, hipStream_t st);
 // the per-path overlaps from the lazy state with the CURRENT spectra, the lazy state kept valid beside them (tails_both)

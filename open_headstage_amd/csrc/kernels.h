@@ -294,7 +294,7 @@ struct ConvLayoutIrArgs {
 };
 // a.chunks as for launch_conv_p1_layout; the host has checked every index against the table
 hipError_t launch_conv_p1_layout_irs(const ConvP1Args &a, const ConvLayoutIrArgs &l, hipStream_t st);
-// the layout kernels' workgroup shape, shared by conv_kernels.hip and conv_objects_kernels.hip: waves per workgroup (one per SIMD),
+// the layout kernels' workgroup shape, shared by conv_kernels.hip and conv_objects_body.hpp: waves per workgroup (one per SIMD),
 // resident waves per SIMD
 #ifndef OHS_LAYOUT_WAVES
 #define OHS_LAYOUT_WAVES 4
@@ -303,7 +303,8 @@ hipError_t launch_conv_p1_layout_irs(const ConvP1Args &a, const ConvLayoutIrArgs
 #define OHS_LAYOUT_WAVES_PER_SIMD 3
 #endif
 // K moving sources per stream -> two ears (ohs_scene_process; library-internal, no entry of ohs_hip.h): k_conv_p1_objects
-// (conv_objects_kernels.hip), the body of
+// (conv_objects_kernels.hip; its helpers, two-row pass and launch are conv_objects_body.hpp's, shared with the two kernels below; the
+// block loop is the unit's own), the body of
 // k_conv_p1_layout_irs with a table per DIRECTION instead of per set -- the pair's (C, D) is formed per pass from the two objects' rows
 // of `ahalf` -- and with one direction index and one gain per object, stream and segment: block t uses entry
 // [s * stream + (t / seg) * n_objects + c] of `idx` and `gain`.  A struct of its own, so that the layout kernels' stay what they are.
@@ -327,52 +328,35 @@ struct ConvObjectsArgs {
 hipError_t launch_conv_p1_objects(const ConvP1Args &a, const ConvObjectsArgs &l, hipStream_t st);
 // H[dir][2][1024] (launch_ir_spectrum: left ear, right ear) -> dst[dir][1024] = 0.5 (Hl.x - Hr.y, Hl.y + Hr.x) in the block loop's layout
 hipError_t launch_object_tables(const float2 *H, int n_dirs, float2 *dst, hipStream_t st);
-// K moving sources per stream, each between TWO directions (ohs_scene2_process_blended; library-internal): k_conv_p1_objects_blend
-// (conv_objects_blend_kernels.hip), the body of k_conv_p1_objects on the same direction table, with a second index and a weight per
-// object, stream and segment: the object's row is (1 - w) ahalf[idx] + w ahalf[idx1].  idx1 and the weight have the shape and the
-// stride rule of idx and the gain, and stand in one staging buffer with them.  A struct of its own, so that ConvObjectsArgs and its kernel stay what they are.
+// K moving sources per stream, each between TWO directions (ohs_scene2_process_blended: k_conv_p1_objects_blend,
+// conv_objects_blend_kernels.hip) or inside a triangle of THREE (ohs_scene3_process_blended3: k_conv_p1_objects_blend3,
+// conv_objects_blend3_kernels.hip); library-internal.  conv_objects_body.hpp's block loop on k_conv_p1_objects's direction table, with
+// NDIR = 2 or 3 direction indices and NDIR - 1 weights per object, stream and segment: the object's row is
+// (1 - w) ahalf[idx] + w ahalf[idx1], or (u ahalf[idx] + w1 ahalf[idx1]) + w2 ahalf[idx2] with u = (1 - w1) - w2.  The further indices
+// and the weights have the shape and the stride rule of idx and the gain, and stand in one staging buffer with them: 2 NDIR planes.
+// One struct for both kernels; ConvObjectsArgs, whose row pointers are separate and nullable one by one, stays what it is.
 struct ConvObjectsBlendArgs {
     const float2 *ahalf;        // ConvObjectsArgs's table, row n_dirs all zero
     unsigned zero_dir;          // n_dirs
     int n_pairs;                // ceil(n_objects / 2)
     int n_objects;
-    const unsigned *rows;       // four planes of [row][segment][n_objects] 32-bit entries, `plane` entries apart: first direction, second
-                                // direction, weight (f32 bits in [0, 1]: the second direction's share), gain (f32 bits)
+    const unsigned *rows;       // 2 NDIR planes of [row][segment][n_objects] 32-bit entries, `plane` entries apart: the NDIR directions, the
+                                // NDIR - 1 weights (f32 bits; two directions: w in [0, 1], the second direction's share; three: each >= 0
+                                // and w1 + w2 <= 1), the gain (f32 bits)
     int plane;
     int has_gain;               // 0: the gain plane is not there, 1.0 everywhere
     int stream;                 // stream s reads its rows at rows + s * stream (0: one row for all streams)
     int seg;                    // blocks per segment
-    const unsigned *prev;       // four planes of [row][n_objects] in front of the call's first block, `prev_plane` apart; under CROSSFADE the
-                                // host always stages them (the first segment's own entries where the caller names none); else nullptr
+    const unsigned *prev;       // as many planes of [row][n_objects] in front of the call's first block, `prev_plane` apart; under CROSSFADE
+                                // the host always stages them (the first segment's own entries where the caller names none); else nullptr
     int prev_plane;
     int prev_stream;            // stream s reads prev + s * prev_stream (0: one row for all streams)
     int fade;                   // 1: CROSSFADE; 0: RING_OUT, no pair fades (prev is not read)
 };
-// a.chunks as for launch_conv_p1_layout; the host has checked every index against the table and every weight against [0, 1]
-hipError_t launch_conv_p1_objects_blend(const ConvP1Args &a, const ConvObjectsBlendArgs &l, hipStream_t st);
-// K moving sources per stream, each between THREE directions (ohs_scene3_process_blended3; library-internal): k_conv_p1_objects_blend3
-// (conv_objects_blend3_kernels.hip), the body of k_conv_p1_objects_blend with a third index and a second weight per object, stream and
-// segment: the object's row is (u ahalf[idx] + w1 ahalf[idx1]) + w2 ahalf[idx2], u = (1 - w1) - w2.  A struct of its own, so that
-// the two kernels in front stay what they are.
-struct ConvObjectsBlend3Args {
-    const float2 *ahalf;        // ConvObjectsArgs's table, row n_dirs all zero
-    unsigned zero_dir;          // n_dirs
-    int n_pairs;                // ceil(n_objects / 2)
-    int n_objects;
-    const unsigned *rows;       // six planes of [row][segment][n_objects] 32-bit entries, `plane` entries apart: first, second, third
-                                // direction, w1, w2 (f32 bits, each >= 0 and w1 + w2 <= 1), gain (f32 bits)
-    int plane;
-    int has_gain;               // 0: the gain plane is not there, 1.0 everywhere
-    int stream;                 // stream s reads its rows at rows + s * stream (0: one row for all streams)
-    int seg;                    // blocks per segment
-    const unsigned *prev;       // six planes of [row][n_objects] in front of the call's first block, `prev_plane` apart; under CROSSFADE the
-                                // host always stages them (the first segment's own entries where the caller names none); else nullptr
-    int prev_plane;
-    int prev_stream;            // stream s reads prev + s * prev_stream (0: one row for all streams)
-    int fade;                   // 1: CROSSFADE; 0: RING_OUT, no pair fades (prev is not read)
-};
-// a.chunks as for launch_conv_p1_layout; the host has checked every index against the table and every weight pair against the triangle
-hipError_t launch_conv_p1_objects_blend3(const ConvP1Args &a, const ConvObjectsBlend3Args &l, hipStream_t st);
+// a.chunks as for launch_conv_p1_layout; the host has checked every index against the table and every weight against [0, 1] (three
+// directions: every weight pair against the triangle)
+hipError_t launch_conv_p1_objects_blend(const ConvP1Args &a, const ConvObjectsBlendArgs &l, hipStream_t st);      // l.rows: four planes
+hipError_t launch_conv_p1_objects_blend3(const ConvP1Args &a, const ConvObjectsBlendArgs &l, hipStream_t st);     // l.rows: six planes
 // cd[set][2][1024] (launch_build_cd per set) -> dst[set][1024] in the block loop's layout, times `scale`
 hipError_t launch_irs_tables(const float2 *cd, int n_sets, float4 *dst, hipStream_t st, float scale = 1.0f);
 // The layout kernels' tables are built with this scale: launch_build_cd's 1/N taken out again, which launch_conv_p1_layout and

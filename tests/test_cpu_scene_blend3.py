@@ -249,9 +249,14 @@ def test_kernel_resources():
     assert k["scratch_bytes_per_lane"] == 0 and k["agprs"] == 0 and k["occupancy_waves_per_simd"] == 3 and k["vgprs"] <= 168, k
     # ... and the figures as built, with the six-row pass's window at four rows
     assert {f: k[f] for f in fields} == {"vgprs": 168, "agprs": 0, "sgprs": 106, "scratch_bytes_per_lane": 0, "occupancy_waves_per_simd": 3}, k
-    src = open(os.path.join(PKG, "csrc", "conv_objects_blend3_kernels.hip")).read()
-    assert re.search(r"#define OHS_P1_BLEND3_ROWS 4\b", src)
-    assert "asm volatile(\"\" :" in src and not re.search(r"asm\s+volatile\s*\(\s*\"[^\"]", src)     # (register fences only)
+    # the three object kernels' text is one header's; the units hold a stub each
+    body = open(os.path.join(PKG, "csrc", "conv_objects_body.hpp")).read()
+    assert re.search(r"#define OHS_P1_BLEND3_ROWS 4\b", body)
+    assert "asm volatile(\"\" :" in body
+    for name in ("conv_objects_body.hpp", "conv_objects_kernels.hip", "conv_objects_blend_kernels.hip", "conv_objects_blend3_kernels.hip"):
+        src = open(os.path.join(PKG, "csrc", name)).read()
+        assert "conv_objects_body.hpp" in src
+        assert not re.search(r"asm\s+volatile\s*\(\s*\"[^\"]", src), name       # (register fences only)
     assert build.is_current() and os.path.exists(build.SCENE3_LIB)
     assert {os.path.basename(p) for p in (build.LIB, build.SCENE_LIB, build.SCENE2_LIB, build.SCENE3_LIB, build.LOOKUP_LIB)} == \
         {"libohs_hip.so", "libohs_scene.so", "libohs_scene2.so", "libohs_scene3.so", "libohs_lookup.so"}
