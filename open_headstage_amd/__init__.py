@@ -16,6 +16,7 @@ from .scene import SceneError, SceneProcessor, nearest_directions, rotate_source
 from .scene2 import BlendSceneProcessor, bracket_directions
 from .scene3 import TriSceneProcessor, triangle_directions, triangulate_directions
 from .lookup import DirectionLookup, DirectionLookupError
+from .lookup3 import TriangleLookup, TriangleLookupError
 from ._ffi import OhsError
 
 __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter", "ConvolutionEngine",
@@ -25,4 +26,5 @@ __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter
            "HeadTrack", "nearest_set", "yaw_rows", "plan_calls", "render_files", "WavReader", "pcm_decode_device",
            "pcm_encode_device", "SceneProcessor", "SceneError", "rotate_sources", "nearest_directions",
            "BlendSceneProcessor", "bracket_directions", "TriSceneProcessor", "triangle_directions",
-           "triangulate_directions", "DirectionLookup", "DirectionLookupError"]
+           "triangulate_directions", "DirectionLookup", "DirectionLookupError", "TriangleLookup",
+           "TriangleLookupError"]
