@@ -17,6 +17,7 @@ from .scene2 import BlendSceneProcessor, bracket_directions
 from .scene3 import TriSceneProcessor, triangle_directions, triangulate_directions
 from .lookup import DirectionLookup, DirectionLookupError
 from .lookup3 import TriangleLookup, TriangleLookupError
+from .lookup3p import PrunedTriangleLookup, PrunedTriangleLookupError
 from ._ffi import OhsError
 
 __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter", "ConvolutionEngine",
@@ -27,4 +28,4 @@ __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter
            "pcm_encode_device", "SceneProcessor", "SceneError", "rotate_sources", "nearest_directions",
            "BlendSceneProcessor", "bracket_directions", "TriSceneProcessor", "triangle_directions",
            "triangulate_directions", "DirectionLookup", "DirectionLookupError", "TriangleLookup",
-           "TriangleLookupError"]
+           "TriangleLookupError", "PrunedTriangleLookup", "PrunedTriangleLookupError"]

@@ -1,6 +1,7 @@
 """Builds libohs_hip.so (HIP kernels + C ABI), libohs_scene.so (the same objects + the ohs_scene_* entries), libohs_scene2.so (the
 same objects + the ohs_scene2_* entries), libohs_scene3.so (the same objects + the ohs_scene3_* entries), libohs_lookup.so (its
-own two objects and nothing of the product's) and libohs_lookup3.so (likewise its own two) for gfx950, in-tree.
+own two objects and nothing of the product's), libohs_lookup3.so (likewise its own two) and libohs_lookup3p.so (likewise) for
+gfx950, in-tree.
 
     python -m open_headstage_amd.build [--force]
 
@@ -71,6 +72,13 @@ LOOKUP_HEADERS = ("lookup_body.hpp", "lookup_internal.h")
 LOOKUP3_LIB = os.path.join(HERE, "libohs_lookup3.so")
 LOOKUP3_UNITS = [("lookup3_kernels.hip", ["-ffp-contract=off"]), ("api_lookup3.hip", ["-ffp-contract=off"])]
 LOOKUP3_HEADERS = ("lookup3_body.hpp", "lookup3_internal.h")
+# The third LOOKUP library (include/ohs_lookup3p.h): libohs_lookup3.so's rows with the walk pruned by a grid over the sphere, bit for
+# bit.  Its own two units once more, none of the product's objects and none of the other lookup libraries', exporting ohs_lookup3p_*
+# and nothing else (csrc/lookup3p_exports.map).  Untagged build only.  -ffp-contract=off as above.  The units include lookup3_body.hpp
+# and lookup_body.hpp as they are.
+LOOKUP3P_LIB = os.path.join(HERE, "libohs_lookup3p.so")
+LOOKUP3P_UNITS = [("lookup3p_kernels.hip", ["-ffp-contract=off"]), ("api_lookup3p.hip", ["-ffp-contract=off"])]
+LOOKUP3P_HEADERS = ("lookup3p_body.hpp", "lookup3p_internal.h")
 ARCH = "gfx950"
 
 
@@ -124,8 +132,12 @@ def _deps(src: str) -> list[str]:
         deps += [os.path.join(CSRC, f) for f in LOOKUP3_HEADERS + ("lookup_body.hpp",)]
         deps += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("ohs_hip.h", "ohs_lookup3.h")]
         return deps + [os.path.join(CSRC, "lookup3_exports.map"), os.path.abspath(__file__)]
+    if src in [u for u, _ in LOOKUP3P_UNITS]:           # (likewise, and the two older bodies it includes)
+        deps += [os.path.join(CSRC, f) for f in LOOKUP3P_HEADERS + ("lookup3_body.hpp", "lookup_body.hpp")]
+        deps += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("ohs_hip.h", "ohs_lookup3p.h")]
+        return deps + [os.path.join(CSRC, "lookup3p_exports.map"), os.path.abspath(__file__)]
     deps += sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)
-                   if f.endswith((".h", ".hpp", ".inc")) and f not in LOOKUP_HEADERS + LOOKUP3_HEADERS)
+                   if f.endswith((".h", ".hpp", ".inc")) and f not in LOOKUP_HEADERS + LOOKUP3_HEADERS + LOOKUP3P_HEADERS)
     exp_dir = os.path.join(CSRC, "experiments")         # (included under -DOHS_EXPERIMENTS only)
     if os.path.isdir(exp_dir):
         deps += sorted(os.path.join(exp_dir, f) for f in os.listdir(exp_dir) if f.endswith((".h", ".hpp", ".inc")))
@@ -155,13 +167,13 @@ def _unit_hash(src: str, extra: list[str]) -> str:
 
 
 def _all_units():
-    """the product's units, and behind them the three scene libraries' own and the two lookup libraries' (untagged build only)"""
-    return _units() + ([] if TAG else [SCENE_UNIT, SCENE2_UNIT, SCENE3_UNIT] + LOOKUP_UNITS + LOOKUP3_UNITS)
+    """the product's units, and behind them the three scene libraries' own and the three lookup libraries' (untagged build only)"""
+    return _units() + ([] if TAG else [SCENE_UNIT, SCENE2_UNIT, SCENE3_UNIT] + LOOKUP_UNITS + LOOKUP3_UNITS + LOOKUP3P_UNITS)
 
 
 def _libs_exist() -> bool:
     return os.path.exists(LIB) and (bool(TAG) or all(os.path.exists(p) for p in (SCENE_LIB, SCENE2_LIB, SCENE3_LIB, LOOKUP_LIB,
-                                                                               LOOKUP3_LIB)))
+                                                                               LOOKUP3_LIB, LOOKUP3P_LIB)))
 
 
 def _current_hashes() -> dict:
@@ -177,8 +189,8 @@ def _read_stamp() -> dict:
 
 
 def is_current() -> bool:
-    """True when libohs_hip.so (and, untagged, libohs_scene.so, libohs_scene2.so, libohs_scene3.so, libohs_lookup.so and
-    libohs_lookup3.so) exists and was built from exactly the sources in the tree."""
+    """True when libohs_hip.so (and, untagged, libohs_scene.so, libohs_scene2.so, libohs_scene3.so, libohs_lookup.so,
+    libohs_lookup3.so and libohs_lookup3p.so) exists and was built from exactly the sources in the tree."""
     return _libs_exist() and _read_stamp() == _current_hashes()
 
 
@@ -223,7 +235,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         links.append((SCENE3_LIB, product_objs + [objs[n_product + 2]], "scene3_exports.map"))
         n_lookup = n_product + 3
         links.append((LOOKUP_LIB, objs[n_lookup:n_lookup + len(LOOKUP_UNITS)], "lookup_exports.map"))      # (its own objects only)
-        links.append((LOOKUP3_LIB, objs[n_lookup + len(LOOKUP_UNITS):], "lookup3_exports.map"))            # (likewise)
+        n_lookup3 = n_lookup + len(LOOKUP_UNITS)
+        links.append((LOOKUP3_LIB, objs[n_lookup3:n_lookup3 + len(LOOKUP3_UNITS)], "lookup3_exports.map"))  # (likewise)
+        links.append((LOOKUP3P_LIB, objs[n_lookup3 + len(LOOKUP3_UNITS):], "lookup3p_exports.map"))         # (likewise)
     for lib, lib_objs, vscript in links:
         cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib, *lib_objs,
                "-Wl,--version-script=" + os.path.join(CSRC, vscript), "-lz", "-ldl", "-lpthread"]
