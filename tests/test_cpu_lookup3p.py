@@ -98,6 +98,19 @@ def mixed_queries(xyz, tris, G, n, seed):
     return np.ascontiguousarray(np.concatenate([l3.soup_queries(xyz, tris, n, seed), seam_queries(G or l3p.choose_grid(len(tris)), seed + 1)]))
 
 
+def widest_grid_case():
+    """the level-6 octahedron mesh (32 768 triangles) at grid = 256, the widest: about 1 000 queries -- 400 of mixed_queries and a
+    seeded sample of 600 of the 18 500 seams of that grid -> (xyz, tris, q, 256).  tests/test_gpu_lookup_chunks.py runs the same on
+    the device."""
+    from open_headstage_amd import lookup, lookup3
+    pos, tris = lookup3.octahedron_mesh(6)
+    xyz = lookup.table_xyz(pos)
+    seams = seam_queries(256, seed=257)
+    pick = np.sort(np.random.default_rng(256).choice(len(seams), 600, replace=False))
+    q = np.concatenate([mixed_queries(xyz, tris, 256, 400, seed=6)[:400], seams[pick]])
+    return xyz, tris, np.ascontiguousarray(q), 256
+
+
 # ---- 1. the surface --------------------------------------------------------------------------------------------------------------
 ENTRIES = ["ohs_lookup3p_create", "ohs_lookup3p_destroy", "ohs_lookup3p_index", "ohs_lookup3p_last_error", "ohs_lookup3p_last_launch",
            "ohs_lookup3p_mesh", "ohs_lookup3p_points", "ohs_lookup3p_rows", "ohs_lookup3p_status_string"]
@@ -303,6 +316,22 @@ def test_lookup3p_body_on_the_host(tmp_path, host_cases):
         assert 0.25 * T < len(by_name[name]["everywhere"]) < 0.75 * T, (name, len(by_name[name]["everywhere"]))
     assert len(by_name["octahedron5 at G = 0"]["everywhere"]) == 0 and by_name["octahedron5 at G = 0"]["G"] == 37
     assert len(by_name["octahedron0 at G = 16"]["everywhere"]) == 8       # (each cap would touch more than 64 cells)
+
+
+def test_the_widest_grid_on_the_host(tmp_path):
+    """level 6 at G = 256, one case more for the host program: the three checks of _hold_to_the_model, the conservative property
+    included, where some triangles lie on the everywhere list and the others in cell lists"""
+    exe = str(tmp_path / "lookup3p_host_check")
+    assert _compile(exe).returncode == 0
+    case = widest_grid_case()
+    assert len(case[1]) == 32768 and len(case[2]) == 1000
+    got, = _run(exe, [case], tmp_path)
+    n, fb, walked = _hold_to_the_model(case, got, "level 6 at G = 256")
+    entries, everywhere, longest = len(got["cell_tris"]), len(got["everywhere"]), int(np.diff(got["cell_start"]).max())
+    print(f"level 6 at G = 256: {entries} entries, longest list {longest}, everywhere {everywhere}; {n} queries, {fb} to pass 2, "
+          f"{walked / n:.1f} candidates per query in pass 1")
+    assert got["G"] == 256 and (everywhere, entries, longest) == (6728, 953688, 8)         # as built: both lists are walked, merged
+    assert 0 < fb < n
 
 
 def test_the_fallback_set_is_the_same_at_every_grid(tmp_path):

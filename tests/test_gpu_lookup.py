@@ -46,8 +46,9 @@ def _sizes(lk):
     return T, Q
 
 
-def assert_model_bits(xyz, q, got, blend, what=""):
-    m = lm.lookup(xyz, q, blend)
+def assert_model_bits(xyz, q, got, blend, what="", model=None):
+    """model: lm.lookup(xyz, q, blend) where the caller has it already (tests/test_gpu_lookup_chunks.py)"""
+    m = lm.lookup(xyz, q, blend) if model is None else model
     if blend:
         i0, i1, w = (np.asarray(v).reshape(-1) for v in got)
         bad = np.flatnonzero((i0 != m["idx0"]) | (i1 != m["idx1"]) | (lm.bits(w) != lm.bits(m["w"])))

@@ -32,9 +32,10 @@ def _sizes(lk):
     return TT, Q
 
 
-def assert_model_bits(xyz, tris, q, got, what=""):
-    """got: (idx0, idx1, idx2, w1, w2, tri)"""
-    m = l3.lookup3(xyz, tris, q)
+def assert_model_bits(xyz, tris, q, got, what="", model=None):
+    """got: (idx0, idx1, idx2, w1, w2, tri); model: l3.lookup3(xyz, tris, q) where the caller has it already
+    (tests/test_gpu_lookup_chunks.py)"""
+    m = l3.lookup3(xyz, tris, q) if model is None else model
     got = [np.asarray(g).reshape(-1) for g in got]
     bad = np.flatnonzero(~l3.same_rows(got[:5], m) | (got[5] != m["tri"]))
     assert bad.size == 0, (what, bad[:8], [g[bad[:8]] for g in got], [m[k][bad[:8]] for k in l3.FIELDS + ("tri",)])
