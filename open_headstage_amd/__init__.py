@@ -18,6 +18,7 @@ from .scene3 import TriSceneProcessor, triangle_directions, triangulate_directio
 from .lookup import DirectionLookup, DirectionLookupError
 from .lookup3 import TriangleLookup, TriangleLookupError
 from .lookup3p import PrunedTriangleLookup, PrunedTriangleLookupError
+from .tracked import TrackedSceneProcessor
 from ._ffi import OhsError
 
 __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter", "ConvolutionEngine",
@@ -28,4 +29,5 @@ __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter
            "pcm_encode_device", "SceneProcessor", "SceneError", "rotate_sources", "nearest_directions",
            "BlendSceneProcessor", "bracket_directions", "TriSceneProcessor", "triangle_directions",
            "triangulate_directions", "DirectionLookup", "DirectionLookupError", "TriangleLookup",
-           "TriangleLookupError", "PrunedTriangleLookup", "PrunedTriangleLookupError"]
+           "TriangleLookupError", "PrunedTriangleLookup", "PrunedTriangleLookupError",
+           "TrackedSceneProcessor"]

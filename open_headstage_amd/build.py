@@ -1,7 +1,7 @@
 """Builds libohs_hip.so (HIP kernels + C ABI), libohs_scene.so (the same objects + the ohs_scene_* entries), libohs_scene2.so (the
 same objects + the ohs_scene2_* entries), libohs_scene3.so (the same objects + the ohs_scene3_* entries), libohs_lookup.so (its
-own two objects and nothing of the product's), libohs_lookup3.so (likewise its own two) and libohs_lookup3p.so (likewise) for
-gfx950, in-tree.
+own two objects and nothing of the product's), libohs_lookup3.so (likewise its own two), libohs_lookup3p.so (likewise) and
+libohs_tracked.so (the product's objects + lookup3p_kernels.o + its own two units, the ohs_tracked_* entries) for gfx950, in-tree.
 
     python -m open_headstage_amd.build [--force]
 
@@ -79,6 +79,13 @@ LOOKUP3_HEADERS = ("lookup3_body.hpp", "lookup3_internal.h")
 LOOKUP3P_LIB = os.path.join(HERE, "libohs_lookup3p.so")
 LOOKUP3P_UNITS = [("lookup3p_kernels.hip", ["-ffp-contract=off"]), ("api_lookup3p.hip", ["-ffp-contract=off"])]
 LOOKUP3P_HEADERS = ("lookup3p_body.hpp", "lookup3p_internal.h")
+# The TRACKED library (include/ohs_tracked.h): sources and poses in, two ears out, the rows found, sealed and rendered on the device
+# on one stream.  The product's object files, as libohs_scene3.so links them, plus lookup3p_kernels.o and two units of its own,
+# exporting ohs_tracked_* and nothing else (csrc/tracked_exports.map).  Untagged build only.  api_tracked.hip builds the mesh's
+# inverses and index on the host as api_lookup3p.hip does: -ffp-contract=off, the same bits.
+TRACKED_LIB = os.path.join(HERE, "libohs_tracked.so")
+TRACKED_UNITS = [("scene_rows_kernels.hip", []), ("api_tracked.hip", ["-ffp-contract=off"])]
+TRACKED_HEADERS = ("scene_rows_body.hpp", "scene_rows_internal.h")
 ARCH = "gfx950"
 
 
@@ -136,8 +143,11 @@ def _deps(src: str) -> list[str]:
         deps += [os.path.join(CSRC, f) for f in LOOKUP3P_HEADERS + ("lookup3_body.hpp", "lookup_body.hpp")]
         deps += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("ohs_hip.h", "ohs_lookup3p.h")]
         return deps + [os.path.join(CSRC, "lookup3p_exports.map"), os.path.abspath(__file__)]
+    tracked = src in [u for u, _ in TRACKED_UNITS]      # (the product's headers, its own, and the pruned lookup's with the bodies it includes)
     deps += sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)
-                   if f.endswith((".h", ".hpp", ".inc")) and f not in LOOKUP_HEADERS + LOOKUP3_HEADERS + LOOKUP3P_HEADERS)
+                   if f.endswith((".h", ".hpp", ".inc")) and f not in LOOKUP_HEADERS + LOOKUP3_HEADERS + LOOKUP3P_HEADERS + TRACKED_HEADERS)
+    if tracked:
+        deps += [os.path.join(CSRC, f) for f in TRACKED_HEADERS + LOOKUP3P_HEADERS + ("lookup3_body.hpp", "lookup_body.hpp")]
     exp_dir = os.path.join(CSRC, "experiments")         # (included under -DOHS_EXPERIMENTS only)
     if os.path.isdir(exp_dir):
         deps += sorted(os.path.join(exp_dir, f) for f in os.listdir(exp_dir) if f.endswith((".h", ".hpp", ".inc")))
@@ -152,6 +162,9 @@ def _deps(src: str) -> list[str]:
     if src == SCENE3_UNIT[0]:
         deps.append(os.path.join(os.path.dirname(HERE), "include", "ohs_scene3.h"))
         deps.append(os.path.join(CSRC, "scene3_exports.map"))
+    if tracked:
+        deps.append(os.path.join(os.path.dirname(HERE), "include", "ohs_tracked.h"))
+        deps.append(os.path.join(CSRC, "tracked_exports.map"))
     deps.append(os.path.abspath(__file__))
     return deps
 
@@ -167,13 +180,14 @@ def _unit_hash(src: str, extra: list[str]) -> str:
 
 
 def _all_units():
-    """the product's units, and behind them the three scene libraries' own and the three lookup libraries' (untagged build only)"""
-    return _units() + ([] if TAG else [SCENE_UNIT, SCENE2_UNIT, SCENE3_UNIT] + LOOKUP_UNITS + LOOKUP3_UNITS + LOOKUP3P_UNITS)
+    """the product's units, and behind them the three scene libraries' own, the three lookup libraries' and the tracked library's
+    (untagged build only)"""
+    return _units() + ([] if TAG else [SCENE_UNIT, SCENE2_UNIT, SCENE3_UNIT] + LOOKUP_UNITS + LOOKUP3_UNITS + LOOKUP3P_UNITS + TRACKED_UNITS)
 
 
 def _libs_exist() -> bool:
     return os.path.exists(LIB) and (bool(TAG) or all(os.path.exists(p) for p in (SCENE_LIB, SCENE2_LIB, SCENE3_LIB, LOOKUP_LIB,
-                                                                               LOOKUP3_LIB, LOOKUP3P_LIB)))
+                                                                               LOOKUP3_LIB, LOOKUP3P_LIB, TRACKED_LIB)))
 
 
 def _current_hashes() -> dict:
@@ -190,7 +204,7 @@ def _read_stamp() -> dict:
 
 def is_current() -> bool:
     """True when libohs_hip.so (and, untagged, libohs_scene.so, libohs_scene2.so, libohs_scene3.so, libohs_lookup.so,
-    libohs_lookup3.so and libohs_lookup3p.so) exists and was built from exactly the sources in the tree."""
+    libohs_lookup3.so, libohs_lookup3p.so and libohs_tracked.so) exists and was built from exactly the sources in the tree."""
     return _libs_exist() and _read_stamp() == _current_hashes()
 
 
@@ -237,7 +251,11 @@ def build(force: bool = False, verbose: bool = False) -> str:
         links.append((LOOKUP_LIB, objs[n_lookup:n_lookup + len(LOOKUP_UNITS)], "lookup_exports.map"))      # (its own objects only)
         n_lookup3 = n_lookup + len(LOOKUP_UNITS)
         links.append((LOOKUP3_LIB, objs[n_lookup3:n_lookup3 + len(LOOKUP3_UNITS)], "lookup3_exports.map"))  # (likewise)
-        links.append((LOOKUP3P_LIB, objs[n_lookup3 + len(LOOKUP3_UNITS):], "lookup3p_exports.map"))         # (likewise)
+        n_lookup3p = n_lookup3 + len(LOOKUP3_UNITS)
+        links.append((LOOKUP3P_LIB, objs[n_lookup3p:n_lookup3p + len(LOOKUP3P_UNITS)], "lookup3p_exports.map"))   # (likewise)
+        # the tracked library: the product's objects, the pruned lookup's kernels (not its C ABI) and its own two units
+        n_tracked = n_lookup3p + len(LOOKUP3P_UNITS)
+        links.append((TRACKED_LIB, product_objs + [objs[n_lookup3p]] + objs[n_tracked:], "tracked_exports.map"))
     for lib, lib_objs, vscript in links:
         cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib, *lib_objs,
                "-Wl,--version-script=" + os.path.join(CSRC, vscript), "-lz", "-ldl", "-lpthread"]
