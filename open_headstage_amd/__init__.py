@@ -19,6 +19,7 @@ from .lookup import DirectionLookup, DirectionLookupError
 from .lookup3 import TriangleLookup, TriangleLookupError
 from .lookup3p import PrunedTriangleLookup, PrunedTriangleLookupError
 from .tracked import TrackedSceneProcessor
+from .delay import ObjectDelay, ObjectDelayError, distance_rows, render_with_distance
 from ._ffi import OhsError
 
 __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter", "ConvolutionEngine",
@@ -30,4 +31,4 @@ __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter
            "BlendSceneProcessor", "bracket_directions", "TriSceneProcessor", "triangle_directions",
            "triangulate_directions", "DirectionLookup", "DirectionLookupError", "TriangleLookup",
            "TriangleLookupError", "PrunedTriangleLookup", "PrunedTriangleLookupError",
-           "TrackedSceneProcessor"]
+           "TrackedSceneProcessor", "ObjectDelay", "ObjectDelayError", "distance_rows", "render_with_distance"]
