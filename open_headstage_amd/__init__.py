@@ -20,6 +20,7 @@ from .lookup3 import TriangleLookup, TriangleLookupError
 from .lookup3p import PrunedTriangleLookup, PrunedTriangleLookupError
 from .tracked import TrackedSceneProcessor
 from .delay import ObjectDelay, ObjectDelayError, distance_rows, render_with_distance
+from .delay2 import FilteredObjectDelay, FilteredObjectDelayError, air_absorption_taps, render_with_distance_air
 from ._ffi import OhsError
 
 __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter", "ConvolutionEngine",
@@ -31,4 +32,5 @@ __all__ = ["BLOCK_SIZE", "FFT_SIZE", "NUM_EQ_BANDS", "BandConfig", "BiquadFilter
            "BlendSceneProcessor", "bracket_directions", "TriSceneProcessor", "triangle_directions",
            "triangulate_directions", "DirectionLookup", "DirectionLookupError", "TriangleLookup",
            "TriangleLookupError", "PrunedTriangleLookup", "PrunedTriangleLookupError",
-           "TrackedSceneProcessor", "ObjectDelay", "ObjectDelayError", "distance_rows", "render_with_distance"]
+           "TrackedSceneProcessor", "ObjectDelay", "ObjectDelayError", "distance_rows", "render_with_distance",
+           "FilteredObjectDelay", "FilteredObjectDelayError", "air_absorption_taps", "render_with_distance_air"]

@@ -1,8 +1,9 @@
 """Builds libohs_hip.so (HIP kernels + C ABI), libohs_scene.so (the same objects + the ohs_scene_* entries), libohs_scene2.so (the
 same objects + the ohs_scene2_* entries), libohs_scene3.so (the same objects + the ohs_scene3_* entries), libohs_lookup.so (its
 own two objects and nothing of the product's), libohs_lookup3.so (likewise its own two), libohs_lookup3p.so (likewise),
-libohs_tracked.so (the product's objects + lookup3p_kernels.o + its own two units, the ohs_tracked_* entries) and libohs_delay.so
-(its own two objects and nothing of the product's, the ohs_delay_* entries) for gfx950, in-tree.
+libohs_tracked.so (the product's objects + lookup3p_kernels.o + its own two units, the ohs_tracked_* entries), libohs_delay.so
+(its own two objects and nothing of the product's, the ohs_delay_* entries) and libohs_delay2.so (likewise its own two, the
+ohs_delay2_* entries) for gfx950, in-tree.
 
     python -m open_headstage_amd.build [--force]
 
@@ -94,6 +95,13 @@ TRACKED_HEADERS = ("scene_rows_body.hpp", "scene_rows_internal.h")
 DELAY_LIB = os.path.join(HERE, "libohs_delay.so")
 DELAY_UNITS = [("delay_kernels.hip", ["-ffp-contract=off"]), ("api_delay.hip", ["-ffp-contract=off"])]
 DELAY_HEADERS = ("delay_body.hpp", "delay_internal.h")
+# The second DELAY library (include/ohs_delay2.h): the same stage with a distance-dependent symmetric FIR fused into it
+# (k_object_delay2).  Its own two units again, none of the product's objects and none of libohs_delay.so's, exporting ohs_delay2_* and
+# nothing else (csrc/delay2_exports.map).  Untagged build only.  -ffp-contract=off: the answers are tests/delay2_model.py's bits, and
+# its unfiltered call has libohs_delay.so's.  The units include delay_body.hpp as it is.
+DELAY2_LIB = os.path.join(HERE, "libohs_delay2.so")
+DELAY2_UNITS = [("delay2_kernels.hip", ["-ffp-contract=off"]), ("api_delay2.hip", ["-ffp-contract=off"])]
+DELAY2_HEADERS = ("delay2_body.hpp", "delay2_internal.h")
 ARCH = "gfx950"
 
 
@@ -155,9 +163,14 @@ def _deps(src: str) -> list[str]:
         deps += [os.path.join(CSRC, f) for f in DELAY_HEADERS]
         deps += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("ohs_hip.h", "ohs_delay.h")]
         return deps + [os.path.join(CSRC, "delay_exports.map"), os.path.abspath(__file__)]
+    if src in [u for u, _ in DELAY2_UNITS]:             # (likewise, and the older body it includes)
+        deps += [os.path.join(CSRC, f) for f in DELAY2_HEADERS + ("delay_body.hpp",)]
+        deps += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("ohs_hip.h", "ohs_delay2.h")]
+        return deps + [os.path.join(CSRC, "delay2_exports.map"), os.path.abspath(__file__)]
     tracked = src in [u for u, _ in TRACKED_UNITS]      # (the product's headers, its own, and the pruned lookup's with the bodies it includes)
     deps += sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)
-                   if f.endswith((".h", ".hpp", ".inc")) and f not in LOOKUP_HEADERS + LOOKUP3_HEADERS + LOOKUP3P_HEADERS + TRACKED_HEADERS + DELAY_HEADERS)
+                   if f.endswith((".h", ".hpp", ".inc")) and f not in LOOKUP_HEADERS + LOOKUP3_HEADERS + LOOKUP3P_HEADERS + TRACKED_HEADERS + DELAY_HEADERS +
+                   DELAY2_HEADERS)
     if tracked:
         deps += [os.path.join(CSRC, f) for f in TRACKED_HEADERS + LOOKUP3P_HEADERS + ("lookup3_body.hpp", "lookup_body.hpp")]
     exp_dir = os.path.join(CSRC, "experiments")         # (included under -DOHS_EXPERIMENTS only)
@@ -193,14 +206,15 @@ def _unit_hash(src: str, extra: list[str]) -> str:
 
 def _all_units():
     """the product's units, and behind them the three scene libraries' own, the three lookup libraries', the tracked library's and
-    the delay library's (untagged build only)"""
+    the two delay libraries' (untagged build only)"""
     return _units() + ([] if TAG else [SCENE_UNIT, SCENE2_UNIT, SCENE3_UNIT] + LOOKUP_UNITS + LOOKUP3_UNITS + LOOKUP3P_UNITS + TRACKED_UNITS +
-                       DELAY_UNITS)
+                       DELAY_UNITS + DELAY2_UNITS)
 
 
 def _libs_exist() -> bool:
     return os.path.exists(LIB) and (bool(TAG) or all(os.path.exists(p) for p in (SCENE_LIB, SCENE2_LIB, SCENE3_LIB, LOOKUP_LIB,
-                                                                               LOOKUP3_LIB, LOOKUP3P_LIB, TRACKED_LIB, DELAY_LIB)))
+                                                                               LOOKUP3_LIB, LOOKUP3P_LIB, TRACKED_LIB, DELAY_LIB,
+                                                                               DELAY2_LIB)))
 
 
 def _current_hashes() -> dict:
@@ -217,7 +231,7 @@ def _read_stamp() -> dict:
 
 def is_current() -> bool:
     """True when libohs_hip.so (and, untagged, libohs_scene.so, libohs_scene2.so, libohs_scene3.so, libohs_lookup.so,
-    libohs_lookup3.so, libohs_lookup3p.so, libohs_tracked.so and libohs_delay.so) exists and was built from exactly the sources in the tree."""
+    libohs_lookup3.so, libohs_lookup3p.so, libohs_tracked.so, libohs_delay.so and libohs_delay2.so) exists and was built from exactly the sources in the tree."""
     return _libs_exist() and _read_stamp() == _current_hashes()
 
 
@@ -271,6 +285,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         n_delay = n_tracked + len(TRACKED_UNITS)
         links.append((TRACKED_LIB, product_objs + [objs[n_lookup3p]] + objs[n_tracked:n_delay], "tracked_exports.map"))
         links.append((DELAY_LIB, objs[n_delay:n_delay + len(DELAY_UNITS)], "delay_exports.map"))      # (its own objects only)
+        n_delay2 = n_delay + len(DELAY_UNITS)
+        links.append((DELAY2_LIB, objs[n_delay2:n_delay2 + len(DELAY2_UNITS)], "delay2_exports.map"))  # (likewise)
     for lib, lib_objs, vscript in links:
         cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib, *lib_objs,
                "-Wl,--version-script=" + os.path.join(CSRC, vscript), "-lz", "-ldl", "-lpthread"]
